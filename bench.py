@@ -22,6 +22,7 @@ import argparse
 import ctypes
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -575,6 +576,8 @@ class StepRunner:
         # the step samples the paths of its masked nodes only (PathNet_run.py:345 picks them out of the epoch's file)
         self.ids_buf = torch.empty((1, self.S, W, L), dtype=torch.int32, device=dev)
         self.codes_buf = torch.empty((1, self.S, W, L), dtype=torch.uint8, device=dev)
+        self.keep_outputs = False       # measure(dump=True): the next step keeps its loss and logits in self.outputs
+        self.outputs = None
 
     def step(self, epoch):
         import pathnet_amd
@@ -599,7 +602,7 @@ class StepRunner:
         self.model.train()
         if self.runner is None and self.fused:
             # forward, CrossEntropyLoss and backward in one library call (pn_pagg_train_step): same kernels, same values
-            loss, _ = self.model.forward_loss(self.X, ids, W, L, self.sel32, codes, self.Ysel, fused=True)
+            loss, out = self.model.forward_loss(self.X, ids, W, L, self.sel32, codes, self.Ysel, fused=True)
         else:
             if self.runner is None:
                 out = self.model(self.X, ids, W, L, self.sel32, codes, None)
@@ -616,20 +619,74 @@ class StepRunner:
         if self.runner is not None:
             self.runner.allreduce_grads(average=True)
         self.opt.step()
+        if self.keep_outputs:
+            self.outputs = (loss, out)
         return loss
+
+    def restart(self, params):
+        """The seeded initial model again (`params`: copies of its parameters taken before the first step) and Adam's state
+        as before its first step (moments zeroed in place, step count 0): two launches on the step's stream, no
+        synchronisation, no allocation."""
+        with torch.no_grad():
+            torch._foreach_copy_(list(self.model.parameters()), params)
+            moments = [t for st in self.opt.state.values() for t in (st["exp_avg"], st["exp_avg_sq"])]
+            if moments:
+                torch._foreach_zero_(moments)
+        for st in self.opt.state.values():
+            st["step"] = 0
+
+    def output_arrays(self):
+        """What the step kept in self.outputs hands its caller, as float32 / float64 host arrays: the loss, the logits of the
+        masked nodes, the paths it sampled for them, every parameter gradient and every parameter after the Adam update."""
+        loss, out = self.outputs
+        arrays = {"loss": loss.detach().float().cpu().numpy(), "logits": out.detach().float().cpu().numpy(),
+                  "path_ids": self.ids_buf[0].cpu().numpy().astype(np.float64),
+                  "path_codes": self.codes_buf[0].cpu().numpy().astype(np.float32)}
+        for k, v in self.model.named_parameters():
+            if v.grad is not None:
+                arrays["grad." + k] = v.grad.detach().float().cpu().numpy()
+        for k, v in self.model.named_parameters():
+            arrays["param." + k] = v.detach().float().cpu().numpy()
+        return arrays
+
+
+DUMP_LIMIT_BYTES = 60 << 20     # --dump-outputs: at most this much array data (+ the .npy headers: < 64 MB in all)
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT_BYTES):
+    """arrays (name -> float32 / float64 host array) -> out_dir/<name>.npy.  When they hold more than `limit` bytes together,
+    every array above an equal share of it is replaced by a fixed sample of its elements (flattened, seeded, in index
+    order): the same arguments give the same sample in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    over = sum(a.nbytes for a in arrays.values()) > limit
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if over and a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 SETTLE_STEPS = 20
+SETTLE_STEPS_DUMP = 200     # --dump-outputs, one process: the most the stage-time sizing below can pick
 DOM_EVERY = 4       # the dominant kernel is bracketed by HIP events on every 4th step of the timed region
 
 
-def measure(sr, lib, ctx, names, steps, warmup, barrier, repeats=0):
+def measure(sr, lib, ctx, names, steps, warmup, barrier, repeats=0, dump=False):
     """warm-up with every stage bracketed (finds the dominant kernel) -> exactly `steps` timed steps with only the
-    dominant kernel carrying an event pair -> per-stage breakdown.  Returns a dict."""
+    dominant kernel carrying an event pair -> per-stage breakdown.  Returns a dict.
+    dump=True: the dict's "outputs" holds what the last timed step computed (StepRunner.output_arrays).  That step starts
+    from the seeded initial model and a fresh Adam (StepRunner.restart), and the settling steps are a fixed
+    SETTLE_STEPS_DUMP, so that its inputs -- parameters, optimizer state, paths, dropout seed -- are the same in every run:
+    after hundreds of Adam steps the parameters carry the rounding of every earlier step's atomic gradient sums."""
     from pathnet_amd import _lib
     _lib.check(lib.pn_profile_configure(ctx, 1, -1))
+    init = [p.detach().clone() for p in sr.model.parameters()] if dump else None
     for e in range(max(1, warmup)):
         sr.step(e)
+        if dump and e == 0:
+            sr.restart(init)            # (once here too: the first launch of a kernel loads its code, ~10 ms)
         if e == 0 and warmup > 1:       # the very first step loads code objects and grants LDS attributes: its stage
             torch.cuda.synchronize()    # times (a 5 ms plan_pack) must not pick the dominant kernel
             read_profile(lib, names, ctx)
@@ -657,7 +714,7 @@ def measure(sr, lib, ctx, names, steps, warmup, barrier, repeats=0):
     #  0.898 / 0.887 / 0.883 / 0.878 / 0.869 ms.  Several ranks: the fixed count, the same on every rank.)
     settle = SETTLE_STEPS
     if sr.world == 1:
-        settle = int(min(200, max(SETTLE_STEPS, 100.0 / max(1e-3, sum(kernel_stages.values())))))
+        settle = SETTLE_STEPS_DUMP if dump else int(min(200, max(SETTLE_STEPS, 100.0 / max(1e-3, sum(kernel_stages.values())))))
     for e in range(settle):
         sr.step(500 + e)
     barrier()
@@ -667,9 +724,17 @@ def measure(sr, lib, ctx, names, steps, warmup, barrier, repeats=0):
     t0 = time.perf_counter()
     for e in range(steps):
         _lib.check(lib.pn_profile_configure(ctx, 2 if e % DOM_EVERY == 0 else 0, dom_stage))
+        if dump and e == steps - 1:
+            sr.restart(init)
+            sr.keep_outputs = True
         sr.step(1000 + e)
     barrier()
     elapsed = time.perf_counter() - t0
+    outputs = None
+    if dump:                # (after the clock is read: the copies are not part of the timed region)
+        sr.keep_outputs = False
+        outputs = sr.output_arrays()
+        sr.outputs = None
     dom = read_profile(lib, names, ctx)[dominant]
     blocks = [elapsed / steps * 1e3]
     for r in range(max(0, repeats)):
@@ -706,7 +771,7 @@ def measure(sr, lib, ctx, names, steps, warmup, barrier, repeats=0):
     prof = read_profile(lib, names, ctx)
     _lib.check(lib.pn_profile_configure(ctx, 0, -1))
     return {"elapsed": elapsed, "dominant": dominant, "dom_ms": dom[0] / dom[1], "dom_launches": dom[1], "settle_steps": settle,
-            "stages_ms": {k: round(v[0] / v[1], 4) for k, v in prof.items()}, "dispersion": dispersion}
+            "stages_ms": {k: round(v[0] / v[1], 4) for k, v in prof.items()}, "dispersion": dispersion, "outputs": outputs}
 
 
 def measure_graph(wl, dev, steps, warmup, barrier):
@@ -1097,7 +1162,8 @@ def _shrunk_bgp():
 
 
 def spawn_ranks(args, dry_run=False):
-    """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU (the form the
+    """`python bench.py --gpus N` without a launcher: run torch.distributed.run as a child process, one rank per GPU, and
+    exit with its status (a fresh process: this one has already asked the runtime for its devices) (the form the
     driver uses for N > 1; a bare invocation must not fail for launch reasons).  Fewer visible GPUs than ranks (the
     one-GPU test box): the ranks share devices, which RCCL refuses -- the collectives then go through gloo, staged
     through the host, and the line says so (collectives.backend)."""
@@ -1114,7 +1180,7 @@ def spawn_ranks(args, dry_run=False):
     if dry_run:
         return cmd, env
     sys.stdout.flush()
-    os.execvpe(cmd[0], cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)
 
 
 def main():
@@ -1129,7 +1195,15 @@ def main():
                     help="cora = BASELINE.json configs[1], what `value` is quoted on; pubmed = configs[2] as the timed "
                          "workload (profiling runs: tools/pmc_passes.sh); bgp = configs[3] stand-in (hetero class, "
                          "node-sharded with --gpus N: strong scaling of one 63 977-node graph)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (loss, logits, sampled paths, "
+                         "gradients, updated parameters) to DIR/<name>.npy as float32 / float64, at most 64 MB in all.  So "
+                         "that the same arguments give that step the same inputs in every run, it starts from the seeded "
+                         "initial model and a fresh Adam, and the settling steps in front of the timed region are a fixed %d"
+                         % SETTLE_STEPS_DUMP)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1181,7 +1255,11 @@ def main():
         torch.cuda.synchronize()
 
     clk0 = clock_mhz(lib, dev)
-    m = measure(sr, lib, ctx, names, args.steps, args.warmup, barrier, repeats=4 if world == 1 else 0)
+    m = measure(sr, lib, ctx, names, args.steps, args.warmup, barrier, repeats=4 if world == 1 else 0,
+                dump=args.dump_outputs is not None)
+    outputs = m.pop("outputs")
+    if outputs is not None and rank == 0:
+        dump_outputs(outputs, args.dump_outputs)
     clk1 = clock_mhz(lib, dev)
     elapsed, dominant, dom_ms = m["elapsed"], m["dominant"], m["dom_ms"]
     collectives = None

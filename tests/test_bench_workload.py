@@ -124,3 +124,25 @@ def test_emit_prints_the_slim_line_last_on_stdout(tmp_path, capsys, monkeypatch)
     assert len(lines) == 1 and json.loads(lines[0])["metric"] == full["metric"]
     assert json.loads(cap.err.strip().split("\n")[-1]) == full                       # everything else: stderr ...
     assert json.load(open(tmp_path / "extras.json")) == full                          # ... and the extras file
+
+
+def test_dump_outputs_writes_float_arrays_under_the_size_cap(tmp_path):
+    """--dump-outputs: every array as DIR/<name>.npy, unchanged; past the size cap, the arrays above an equal share of it
+    become a seeded sample of their elements, the same one in every run"""
+    import pytest
+    small = {"loss": np.array(0.5, np.float32), "logits": np.arange(12, dtype=np.float32).reshape(3, 4),
+             "path_ids": np.arange(6, dtype=np.float64)}
+    bench.dump_outputs(small, str(tmp_path / "a"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["logits.npy", "loss.npy", "path_ids.npy"]
+    for k, v in small.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == v.dtype and got.shape == v.shape and (got == v).all()
+    big = {"ids": np.arange(3000, dtype=np.float64), "x": np.arange(100, dtype=np.float32)}
+    for d in ("b", "c"):
+        bench.dump_outputs(big, str(tmp_path / d), limit=8000)
+    ids = np.load(tmp_path / "b" / "ids.npy")
+    assert ids.nbytes == 4000 and (np.diff(ids) > 0).all() and np.isin(ids, big["ids"]).all()
+    assert (ids == np.load(tmp_path / "c" / "ids.npy")).all()
+    assert (np.load(tmp_path / "b" / "x.npy") == big["x"]).all()
+    with pytest.raises(AssertionError):
+        bench.dump_outputs({"codes": np.zeros(4, np.uint8)}, str(tmp_path / "d"))

@@ -113,11 +113,13 @@ def test_empty_table_is_reported():
     assert e.value.code == _lib.PN_ERR_EMPTY_TABLE
 
 
-@pytest.mark.skipif(not merw.have_ref(), reason="oracle/_ref not built")
 def test_cli_output_is_byte_identical_to_reference_program(tmp_path):
-    """python -m pathnet_amd.sampler <name> <W> <L> vs ./gen_merw <name> <W> <L> (same srand seed)."""
+    """python -m pathnet_amd.sampler <name> <W> <L> vs ./gen_merw <name> <W> <L> (same srand seed): the reference
+    program's output recorded by tests/golden/make_golden_refbin.py."""
     g = golden("sampler_synthetic97_12_5.npz")
     W, L, seed, epochs = 6, 4, 31337, 5
+    want = golden("refbin_synthetic97_6_4.npz")
+    assert (int(want["W"]), int(want["L"]), int(want["seed"]), int(want["epochs"])) == (W, L, seed, epochs)
     os.makedirs(os.path.join(tmp_path, "preprocess"))
     os.makedirs(os.path.join(tmp_path, "edge_input"))
     edge = os.path.join(tmp_path, "edge_input", "syn.in")
@@ -127,7 +129,7 @@ def test_cli_output_is_byte_identical_to_reference_program(tmp_path):
     subprocess.run([sys.executable, "-m", "pathnet_amd.sampler", "syn", str(W), str(L), "--seed", str(seed),
                     "--epochs", str(epochs)], cwd=cwd, env=env, check=True)
     mine = open(os.path.join(cwd, "syn_%d_%d_merw.txt" % (W, L)), "rb").read()
-    ref = merw.run_ref(edge, W, L, seed, max_bytes=len(mine))
+    ref = want["text"].tobytes()
     assert mine.count(b"\n") == epochs * int(g["n"]) * W and mine == ref
     # per-epoch variant (gen_epoch_merw.cpp): same stream, one file per epoch
     subprocess.run([sys.executable, "-m", "pathnet_amd.sampler", "syn", str(W), str(L), "--seed", str(seed),
@@ -325,8 +327,9 @@ def test_uniform_cli_output_is_byte_identical_to_reference_program(tmp_path):
     mine = open(os.path.join(cwd, "syn_%d_%d_nsl.txt" % (W, L)), "rb").read()
     want = merw.format_text(*merw.sample_uniform(n, g["u"], g["v"], W, L, merw.DRAW_GLIBC, seed, epoch_count=epochs))
     assert mine == want
-    if os.path.exists(merw.REF_GEN):
-        assert merw.run_ref_uniform(pair, W, L, seed, max_bytes=len(mine)) == mine
+    ref = golden("refbin_uniform_ring37_6_5.npz")              # the reference program gen's output
+    assert (int(ref["W"]), int(ref["L"]), int(ref["seed"]), int(ref["epochs"])) == (W, L, seed, epochs)
+    assert ref["text"].tobytes() == mine
     # gen_epoch.cpp: reads <name>.in, one file per epoch without a marker, prints "n m"
     merw.write_pair_file(os.path.join(tmp_path, "edge_input", "syn.in"), n, g["u"], g["v"])
     r = subprocess.run([sys.executable, "-m", "pathnet_amd.sampler", "syn", str(W), str(L), "--uniform", "--per-epoch",

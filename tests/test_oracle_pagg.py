@@ -1,5 +1,5 @@
 """The aggregator oracle (oracle/pagg_oracle.py) against the committed golden vectors produced by the
-reference classes, and against the reference classes themselves when /root/reference is mounted."""
+reference classes."""
 import numpy as np
 import pytest
 import torch
@@ -61,42 +61,31 @@ def test_plan_hetero_quirks():
     assert (node == ids).all() and (group == np.arange(P) // W).all()
 
 
-@pytest.mark.reference
 @pytest.mark.parametrize("variant,cname", [("hetero", "PathNet"), ("homo", "PathNet_homo"), ("pagg", "PAGG")])
 def test_oracle_matches_live_reference_classes(variant, cname):
-    import warnings
-    warnings.filterwarnings("ignore")
-    from ref_extract import reference_classes
-    cls = reference_classes(0.0)
-    torch.manual_seed(3)
-    rng = np.random.default_rng(3)
-    N, F, H, C, W, L, S = 64, 21, 128, 6, 40, 4, 29
-    model = cls[cname](F, H, C, L if variant != "pagg" else N)
-    X = torch.rand(N, F)
-    mask = np.zeros(N, bool)
-    mask[rng.permutation(N)[:S]] = True
-    sel = np.nonzero(mask)[0]
-    ids = rng.integers(0, N, size=(S, W, L))
-    ids[:, :, 0] = sel[:, None]
-    codes = rng.integers(0, L, size=(S, W, L))
-    model.eval()
-    ref = model(X, torch.tensor(ids.reshape(S, W * L)), W, L, torch.tensor(mask), torch.tensor(codes),
-                torch.arange(S * W * L))
-    got = po.forward(variant, dict(model.state_dict()), X, ids, codes, sel, W, L)
-    assert (ref - got).abs().max().item() < 2e-6
+    """the reference class `cname` itself, constructed under torch.manual_seed(3) and run in eval() on a hid-128 case;
+    its state_dict, inputs and output recorded by tests/golden/make_golden_refbin.py"""
+    g, params, _ = load_case("refclass_%s.npz" % variant)
+    assert str(g["variant"]) == variant
+    N, F, H, C, W, L, S = (int(g[k]) for k in "NFHCWLS")
+    assert (N, F, H, C, W, L, S) == (64, 21, 128, 6, 40, 4, 29)
+    sel = np.nonzero(g["mask"])[0]
+    got = po.forward(variant, params, torch.tensor(g["X"]), g["ids"].astype(np.int64), g["codes"].astype(np.int64),
+                     sel, W, L)
+    assert (torch.tensor(g["out"]) - got).abs().max().item() < 2e-6
 
 
-@pytest.mark.reference
 def test_state_dict_contract_cornell_pth():
-    """saved_models/cornell.pth pins the state_dict keys/shapes of PathNet(1703,128,5,4)."""
-    sd = torch.load("/root/reference/saved_models/cornell.pth", map_location="cpu")
+    """saved_models/cornell.pth pins the state_dict keys/shapes of PathNet(1703,128,5,4); its key ->
+    shape map is recorded in tests/golden/refmodel_cornell_pth.npz"""
+    sd = {k[len("shape/"):]: tuple(int(x) for x in v) for k, v in golden("refmodel_cornell_pth.npz").items()}
     want = {"fc0.weight": (128, 1703), "fc0.bias": (128,), "LSTM.weight_ih_l0": (512, 128),
             "LSTM.weight_hh_l0": (512, 128), "LSTM.bias_ih_l0": (512,), "LSTM.bias_hh_l0": (512,),
             "fc2.weight": (5, 256), "fc2.bias": (5,), "attw.weight": (1, 256), "attw.bias": (1,)}
     for d in range(4):
         want["nets.%d.weight" % d] = (128, 128)
         want["nets.%d.bias" % d] = (128,)
-    assert {k: tuple(v.shape) for k, v in sd.items()} == want
+    assert sd == want
 
 
 def test_oracle_gru_cell_is_torch_nn_gru():

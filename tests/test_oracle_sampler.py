@@ -1,5 +1,5 @@
 """The sampler oracle (oracle/merw_oracle.c) against (a) glibc, (b) the committed golden vectors that
-the unmodified reference binary produced, (c) the reference binary itself when it is available."""
+the unmodified reference binary produced."""
 import ctypes
 import hashlib
 import os
@@ -75,28 +75,30 @@ def test_structural_invariants_philox():
     assert (ids == ids2).all() and (ids != ids3).any()
 
 
-@pytest.mark.skipif(not merw.have_ref(), reason="oracle/_ref not built")
-def test_oracle_bit_exact_against_reference_binary(tmp_path):
-    """Live run of the unmodified reference program (needs only oracle/_ref, not /root/reference)."""
+def test_oracle_bit_exact_against_reference_binary():
+    """The unmodified reference program's output for this graph and seed (tests/golden/make_golden_refbin.py)."""
     g = golden("sampler_synthetic97_12_5.npz")
+    want = golden("refbin_synthetic97_9_3.npz")
     n, W, L = int(g["n"]), 9, 3
-    edge = os.path.join(tmp_path, "g.in")
-    merw.write_edge_file(edge, n, g["u"], g["v"], g["p"])
+    assert (int(want["W"]), int(want["L"]), int(want["seed"]), int(want["epochs"])) == (W, L, 77, 6)
     ids, codes = merw.sample_full(n, g["u"], g["v"], g["p"], W, L, merw.DRAW_GLIBC, 77, epoch_count=6)
     txt = merw.format_text(ids, codes)
-    ref = merw.run_ref(edge, W, L, 77, max_bytes=len(txt))
-    assert ref == txt
+    assert txt == want["text"].tobytes()
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not merw.have_ref(), reason="oracle/_ref not built")
 @pytest.mark.parametrize("name", ["cora", "citeseer", "cora_nsl"])
-def test_oracle_bit_exact_on_shipped_graphs(name):
-    f = "/root/reference/edge_input/%s.in" % name
+def test_oracle_bit_exact_on_shipped_graphs(name, tmp_path):
+    """edge_input/<name>.in as the reference ships it, and the md5 of the reference program's first two epochs on it"""
+    g = golden("refbin_shipped_%s.npz" % name)
+    W, L, seed, E = int(g["W"]), int(g["L"]), int(g["seed"]), int(g["epochs"])
+    assert (W, L, seed, E) == (40, 4, 5, 2)
+    f = os.path.join(tmp_path, "%s.in" % name)
+    with open(f, "wb") as fh:
+        fh.write(g["edge_file"].tobytes())
     n, u, v, p = merw.read_edge_file(f)
-    ids, codes = merw.sample_full(n, u, v, p, 40, 4, merw.DRAW_GLIBC, 5, epoch_count=2)
+    ids, codes = merw.sample_full(n, u, v, p, W, L, merw.DRAW_GLIBC, seed, epoch_count=E)
     txt = merw.format_text(ids, codes)
-    assert merw.run_ref(f, 40, 4, 5, max_bytes=len(txt)) == txt
+    assert len(txt) == int(g["nbytes"]) and hashlib.md5(txt).hexdigest() == str(g["md5"])
 
 
 # ---- the uniform random-walk sampler (gen.cpp), SURVEY.md §8 f-4 ------------------------------------------------
@@ -117,14 +119,14 @@ def test_uniform_graph_build_keeps_self_loop_first_and_parallel_edges():
     assert lists == [[0, 1, 1, 1, 3], [1, 0, 0, 0], [2], [3, 0]]
 
 
-@pytest.mark.skipif(not os.path.exists(merw.REF_GEN), reason="oracle/_ref/gen not built (reference sources absent)")
-def test_uniform_oracle_matches_reference_binary_on_a_fresh_graph(tmp_path):
+def test_uniform_oracle_matches_reference_binary_on_a_fresh_graph():
+    """the reference program gen's output on this graph (tests/golden/make_golden_refbin.py)"""
+    want = golden("refbin_uniform_fresh41_6_5.npz")
+    assert (int(want["W"]), int(want["L"]), int(want["seed"]), int(want["epochs"])) == (6, 5, 31337, 2)
     rng = np.random.default_rng(77)
     n = 41
     u = np.concatenate([np.arange(n), rng.integers(0, n, 60)]).astype(np.int32)
     v = np.concatenate([(np.arange(n) + 1) % n, rng.integers(0, n, 60)]).astype(np.int32)
-    f = os.path.join(tmp_path, "x_nsl.in")
-    merw.write_pair_file(f, n, u, v)
     ids, codes = merw.sample_uniform(n, u, v, 6, 5, merw.DRAW_GLIBC, 31337, epoch_count=2)
     txt = merw.format_text(ids, codes)
-    assert merw.run_ref_uniform(f, 6, 5, 31337, max_bytes=len(txt)) == txt
+    assert txt == want["text"].tobytes()
