@@ -36,8 +36,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <memory>
 #include <type_traits>
 
 #include "pn_gemm.h"
@@ -591,7 +589,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(PoolParams p) {
 // ================================================================================================
 // BACKWARD
 // ================================================================================================
-// ---- pooling / attention / classifier backward: one wavefront per group -------------------------
+// ---- pooling / attention / classifier backward: the parameters of pool_bwd_wg_kernel and of the pooling step ------------
 struct PoolBwdParams {
     int variant, S, W, H, C, N;
     int64_t goff;
@@ -606,162 +604,18 @@ struct PoolBwdParams {
     float *dXh;        // [N, H]  (+= ego of the classifier input; HETERO: += attention ego)
     float *dego;       // table the attention-ego gradient goes to: dZ (HOMO) or dXh (HETERO)
     float *g_att_w, *g_att_b;
-    // deterministic mode (all three set, else null): instead of atomics the kernel stores the ego half of d layer1 per
-    // group, d score per path and the attention-weight terms per workgroup; det_scatter_kernel / det_att_reduce_kernel add
+    // instead of atomics the kernel stores the attention-weight terms per workgroup (always) and, in deterministic mode
+    // (else null), the ego half of d layer1 per group and d score per path; det_att_reduce_kernel / det_scatter_kernel add
     float *det_sel;    // [S, H]
     float *det_ds;     // [P]
     float *det_att;    // [workgroups][2H + 4]
 };
 
+// A workgroup per group: the W members of a group split over the four waves.  (A wavefront per group ran its ~50 dependent
+// memory round trips alone on its SIMD -- 1 299 waves on 1 024 SIMDs at the headline shape; four times the waves hide them:
+// 0.052 -> 0.031 ms.  Round 2 had rejected this layout for quadrupling the atomics on the 2H + 1 attention-weight
+// addresses; those go through per-workgroup partials, det_att: [groups][2H + 4].)
 // HI: 64-column chunks of H a lane walks (4 covers H <= 256, the fused kernels' range; 16 covers the generic path's H <= 1024)
-template <int HI>
-__global__ __launch_bounds__(256) void pool_bwd_kernel(PoolBwdParams p) {
-    extern __shared__ float lds[];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int H = p.H, W = p.W;
-    float *dco = lds + wave * (2 * W + H);   // [W] d coef, then [W] d score, then [H] d pooled / W
-    float *dsc = dco + W;
-    float *dp = dsc + W;
-    float *red = lds + 4 * (2 * W + H);      // [4][2H] per-wave attention-weight partials
-    int *s_erow = reinterpret_cast<int *>(lds + 4 * (2 * W + H) + 8 * H) + wave * W;   // [4][W] ego rows of the group
-    float *s_coef = lds + 4 * (2 * W + H) + 8 * H + 4 * W + wave * W;                  // [4][W]
-    const int g = blockIdx.x * 4 + wave;
-    const bool active = g < p.S;
-    const float inv_w = 1.0f / (float)W;
-    float gaw_h[HI], gaw_e[HI], gab = 0.0f;
-#pragma unroll
-    for (int i = 0; i < HI; i++) gaw_h[i] = gaw_e[i] = 0.0f;
-
-    if (active) {
-        for (int mem = lane; mem < W; mem += 64) {
-            const int64_t s = (int64_t)g * W + mem;
-            s_erow[mem] = p.variant == PN_VARIANT_PAGG ? 0 : p.egoidx[s];
-            s_coef[mem] = p.coef[s];
-        }
-    }
-    if (active) {
-        for (int j = lane; j < H; j += 64) {
-            float a = 0.0f, b = 0.0f;
-            for (int c = 0; c < p.C; c++) {
-                const float go = p.g_out[(int64_t)g * p.C + c];
-                a += go * p.fc2_w[(int64_t)c * 2 * H + j];
-                b += go * p.fc2_w[(int64_t)c * 2 * H + H + j];
-            }
-            const uint64_t gg = (uint64_t)(p.goff + g);
-            if (p.mask) {
-                a *= p.mask[gg * 2 * H + j];
-                b *= p.mask[gg * 2 * H + H + j];
-            } else if (p.p_drop > 0.0f) {
-                const uint64_t seed = p.dyn ? p.dyn->seed : p.seed;
-                a *= dropout1(seed, gg * 2 * H + j, 2u, p.p_drop);
-                b *= dropout1(seed, gg * 2 * H + H + j, 2u, p.p_drop);
-            }
-            if (p.det_sel)
-                p.det_sel[(int64_t)g * H + j] = a;
-            else
-                atomicAdd(&p.dXh[(int64_t)min(max(p.sel[g], 0), p.N - 1) * H + j], a);
-            dp[j] = b * inv_w;
-        }
-        __builtin_amdgcn_wave_barrier();
-        {
-            const int m8 = lane >> 3, part = lane & 7, jw = H / 8;
-            for (int m0 = 0; m0 < W; m0 += 8) {
-                const int mem = m0 + m8;
-                const float4 *h4 =
-                    reinterpret_cast<const float4 *>(p.hn + ((int64_t)g * W + min(mem, W - 1)) * H + part * jw);
-                float acc = 0.0f;
-                for (int j = 0; j < jw / 4; j++) {
-                    const float4 hv = h4[j];
-                    const float *d = dp + part * jw + 4 * j;
-                    acc += hv.x * d[0] + hv.y * d[1] + hv.z * d[2] + hv.w * d[3];
-                }
-                acc += __shfl_xor(acc, 1, 64);
-                acc += __shfl_xor(acc, 2, 64);
-                acc += __shfl_xor(acc, 4, 64);
-                if (part == 0 && mem < W) dco[mem] = acc;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (p.variant == PN_VARIANT_HETERO) {
-            float tot = 0.0f;
-            for (int mem = lane; mem < W; mem += 64) tot += p.coef[(int64_t)g * W + mem] * dco[mem];
-            tot = wave_sum(tot);
-            for (int mem = lane; mem < W; mem += 64) {
-                const int64_t s = (int64_t)g * W + mem;
-                dsc[mem] = p.coef[s] * (dco[mem] - tot) * (p.rawsc[s] > 0.0f ? 1.0f : 0.01f);
-            }
-        } else {
-            for (int mem = lane; mem < W; mem += 64) dsc[mem] = p.variant == PN_VARIANT_HOMO ? dco[mem] : 0.0f;
-        }
-        __builtin_amdgcn_wave_barrier();
-        // The attention-ego gradient of consecutive members usually lands on the same table row (all W paths of a
-        // node start at that node): it is accumulated in registers and flushed with one atomic per row change.
-        int64_t cur_row = -1;
-        float ego_acc[HI];
-#pragma unroll
-        for (int i = 0; i < HI; i++) ego_acc[i] = 0.0f;
-        auto flush = [&]() {
-            if (cur_row < 0 || p.det_ds) return;
-#pragma unroll
-            for (int i = 0; i < HI; i++) {
-                const int j = lane + 64 * i;
-                if (j < H) atomicAdd(&p.dego[cur_row + j], ego_acc[i]);
-                ego_acc[i] = 0.0f;
-            }
-        };
-#pragma unroll 4
-        for (int mem = 0; mem < W; mem++) {
-            const int64_t s = (int64_t)g * W + mem;
-            const float ds = dsc[mem], cf = s_coef[mem];
-            const int64_t erow = (int64_t)s_erow[mem] * H;
-            if (p.variant != PN_VARIANT_PAGG && erow != cur_row) {   // wave-uniform
-                flush();
-                cur_row = erow;
-            }
-#pragma unroll
-            for (int i = 0; i < HI; i++) {
-                const int j = lane + 64 * i;
-                if (j < H) {
-                    float dh = cf * dp[j];
-                    if (p.variant != PN_VARIANT_PAGG) {
-                        dh += ds * p.att_w[j];
-                        gaw_h[i] += ds * p.hn[s * H + j];
-                        gaw_e[i] += ds * p.ego_tab[erow + j];
-                        ego_acc[i] += ds * p.att_w[H + j];
-                    }
-                    p.dhn[s * H + j] = dh;
-                }
-            }
-            gab += ds;
-            if (p.det_ds && lane == 0) p.det_ds[s] = ds;
-        }
-        if (p.variant != PN_VARIANT_PAGG) flush();
-    }
-    if (p.variant == PN_VARIANT_PAGG) return;   // block-uniform
-#pragma unroll
-    for (int i = 0; i < HI; i++) {
-        const int j = lane + 64 * i;
-        if (j < H) {
-            red[wave * 2 * H + j] = gaw_h[i];
-            red[wave * 2 * H + H + j] = gaw_e[i];
-        }
-    }
-    __syncthreads();
-    if (p.det_att) {
-        float *out = p.det_att + (int64_t)blockIdx.x * (2 * H + 4);
-        for (int j = threadIdx.x; j < 2 * H; j += 256) out[j] = red[j] + red[2 * H + j] + red[4 * H + j] + red[6 * H + j];
-        if (lane == 0) out[2 * H + wave] = active ? gab : 0.0f;
-        return;
-    }
-    for (int j = threadIdx.x; j < 2 * H; j += 256)
-        atomicAdd(&p.g_att_w[j], red[j] + red[2 * H + j] + red[4 * H + j] + red[6 * H + j]);
-    if (lane == 0 && active) atomicAdd(p.g_att_b, gab);
-}
-
-// ---- the same with a workgroup per group: the W members of a group split over the four waves.  One wave per group runs
-//      its ~50 dependent memory round trips alone on its SIMD (1 299 waves on 1 024 SIMDs at the headline shape); four
-//      times the waves hide them.  (Round 2 had rejected this layout for quadrupling the atomics on the 2H + 1
-//      attention-weight addresses; those now go through per-workgroup partials, det_att: [groups][2H + 4].)
 template <int HI>
 __device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *lds) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1713,6 +1567,28 @@ struct JoinGuard {
     ~JoinGuard() { (void)join(); }
 };
 
+// every buffer a backward accumulates into (atomics / += / split-K), cleared by ONE launch
+struct ZeroFill {
+    pn_context *ctx;
+    ZeroList zl{};
+    int add(float *ptr, size_t count) {
+        if (!ptr || !count) return PN_OK;
+        if (zl.n >= (int)(sizeof zl.ptr / sizeof zl.ptr[0])) PN_FAIL(PN_ERR_ARG, "internal: zero list overflow");
+        zl.ptr[zl.n] = ptr;
+        zl.count[zl.n] = count;
+        zl.n++;
+        return PN_OK;
+    }
+    int flush(hipStream_t s) {
+        if (!zl.n) return PN_OK;
+        StageTimer tm(ctx, ST_ZERO_FILL, s);       // (d Z and d Xh are the bulk: rows of the graph, not paths)
+        hipLaunchKernelGGL(zero_kernel, dim3(512), dim3(256), 0, s, zl);
+        PN_CHECK_HIP(hipGetLastError());
+        zl.n = 0;
+        return PN_OK;
+    }
+};
+
 
 // ---- one aggregator call, resolved: shapes, workspace pointers, and the stages that run once per micro-batch ---------
 struct Call {
@@ -1973,14 +1849,14 @@ int run_seq_fwd(const Call &c, int b, bool save) {
     if (!save && use_zw(c)) {
         sp.range = c.at<SeqRange>(c.w.range);
         sp.ZW = c.at<const float>(c.w.saved);
-        return launch_seq_fwdzw(c.ctx, c.stream, d.H, d.cell == CELL_GRU ? 3 : d.cell == CELL_LSTM ? 4 : 1, sp);
+        return launch_seq_fwdzw(c.ctx, c.stream, d.H, d.Gw, sp);
     }
     if (d.math == PN_SEQ_MATH_F16X2) {
         sp.range = c.at<SeqRange>(c.w.range);
         sp.xmul = seq_xmul(a);
-        return launch_seq_fwdh(c.ctx, c.stream, d.H, d.cell == CELL_GRU ? 3 : d.cell == CELL_LSTM ? 4 : 1, sp);
+        return launch_seq_fwdh(c.ctx, c.stream, d.H, d.Gw, sp);
     }
-    return launch_seq_fwd3(c.ctx, c.stream, d.H, d.cell == CELL_GRU ? 3 : d.cell == CELL_LSTM ? 4 : 1, sp);
+    return launch_seq_fwd3(c.ctx, c.stream, d.H, d.Gw, sp);
 }
 
 PoolParams pool_fwd_params(const Call &c, int b, float *out) {
@@ -2036,8 +1912,8 @@ int check_forward_args(const Call &c, const char *who) {
 
 // What a forward does before its first micro-batch: the touched rows, the index plan of micro-batch 0 and the packed
 // weights (second stream), Xh = fc0(X), Z = bank(Xh); joined, so that the recurrence can follow.
-// side_extra: one more launch for the second stream (pn_pagg_train_step: the zero fill of the backward's accumulators)
-int run_tables(const Call &c, JoinGuard &joiner, const std::function<int(hipStream_t)> *side_extra = nullptr) {
+// zero_fill: flushed on the second stream behind the packing (pn_pagg_train_step: the zero fill of the backward's accumulators)
+int run_tables(const Call &c, JoinGuard &joiner, ZeroFill *zero_fill = nullptr) {
     pn_context *ctx = c.ctx;
     hipStream_t stream = c.stream;
     const pn_pagg_args *a = c.a;
@@ -2059,8 +1935,8 @@ int run_tables(const Call &c, JoinGuard &joiner, const std::function<int(hipStre
         if (int rc = run_plan(c, pstream, 0)) return rc;
         if (int rc = run_pack_fwd(c, pstream)) return rc;
     }
-    if (side_extra)
-        if (int rc = (*side_extra)(pstream)) return rc;
+    if (zero_fill)
+        if (int rc = zero_fill->flush(pstream)) return rc;
     if (pstream != stream)
         if (int rc = joiner.mark()) return rc;
     if (!a->reuse_tables) {
@@ -2159,31 +2035,48 @@ inline DetOrder det_order(const Call &c, int which, int b) {
     }
 }
 
-int prepare_det_orders(const Call &c, hipStream_t s, int b) {
+// the one sort's three segments for micro-batch b: their keys, lengths (EGO is empty without attention), offsets in the sorted
+// output (the running sum of the lengths), the largest key of a present segment and the bits it takes
+struct DetSegments {
+    DetOrder o[3];
+    int64_t n[3], off[3], total, max_key;
+    int bits;
+};
+DetSegments det_segments(const Call &c, int b) {
     const bool has_att = c.d.variant != PN_VARIANT_PAGG;
-    DetKeys3 q{};
-    int64_t total = 0, max_key = 0;
+    DetSegments g{};
     for (int which = 0; which < 3; which++) {
-        const DetOrder o = det_order(c, which, b);
-        q.keys[which] = o.keys;
-        q.n[which] = (which == DET_EGO && !has_att) ? 0 : std::max<int64_t>(o.K, 0);
-        q.hi[which] = (int32_t)o.max_key;
-        total += q.n[which];
-        if (q.n[which]) max_key = std::max(max_key, o.max_key);
+        g.o[which] = det_order(c, which, b);
+        g.n[which] = (which == DET_EGO && !has_att) ? 0 : std::max<int64_t>(g.o[which].K, 0);
+        g.off[which] = g.total;
+        g.total += g.n[which];
+        if (g.n[which]) g.max_key = std::max(g.max_key, g.o[which].max_key);
     }
-    if (total <= 0) return PN_OK;
-    int bits = 1;
-    while (bits < 31 && (max_key >> bits) != 0) bits++;
-    if (bits + 2 > 31) PN_FAIL(PN_ERR_ARG, "deterministic mode: %lld table rows leave no room for the scatters' segment bits", (long long)max_key + 1);
-    q.shift = bits;
+    g.bits = 1;
+    while (g.bits < 31 && (g.max_key >> g.bits) != 0) g.bits++;
+    return g;
+}
+
+int prepare_det_orders(const Call &c, hipStream_t s, int b) {
+    const DetSegments g = det_segments(c, b);
+    if (g.total <= 0) return PN_OK;
+    if (g.bits + 2 > 31)
+        PN_FAIL(PN_ERR_ARG, "deterministic mode: %lld table rows leave no room for the scatters' segment bits", (long long)g.max_key + 1);
+    DetKeys3 q{};
+    for (int which = 0; which < 3; which++) {
+        q.keys[which] = g.o[which].keys;
+        q.n[which] = g.n[which];
+        q.hi[which] = (int32_t)g.o[which].max_key;
+    }
+    q.shift = g.bits;
     int32_t *ck = c.at<int32_t>(c.w.keys), *pos = c.at<int32_t>(c.w.skey);
-    hipLaunchKernelGGL(det_keys3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, q, ck, pos);
+    hipLaunchKernelGGL(det_keys3_kernel, dim3((unsigned)((g.total + 255) / 256)), dim3(256), 0, s, q, ck, pos);
     PN_CHECK_HIP(hipGetLastError());
     // (okey / osrc are the heads of the two contiguous output blocks; an empty EGO segment leaves its slot unused: the
     //  segments that follow start where the sort puts them only if the layout matches -- so the outputs are addressed by the
     //  running sum of the ACTUAL counts, which equals the layout's whenever a segment is present)
-    return sort_pairs_i32(c.at<void>(c.w.stmp), c.w.stmp_bytes, ck, c.at<int32_t>(c.w.okey), pos, c.at<int32_t>(c.w.osrc), total,
-                          bits + 2, s);
+    return sort_pairs_i32(c.at<void>(c.w.stmp), c.w.stmp_bytes, ck, c.at<int32_t>(c.w.okey), pos, c.at<int32_t>(c.w.osrc),
+                          g.total, g.bits + 2, s);
 }
 
 // the orders of micro-batch b on the second stream when there is one (joined by the guard on the way out), else in line
@@ -2196,21 +2089,12 @@ int fork_det_orders(const Call &c, JoinGuard &joiner, int b) {
     return PN_OK;
 }
 
-// where the one sort left scatter `which` of micro-batch b: its offset is the sum of the segments before it that exist
+// where the one sort left scatter `which` of micro-batch b
 DetScatterParams det_params(const Call &c, int which, int b, const float *rows, const float *scal, const float *vec, float *dst) {
-    const bool has_att = c.d.variant != PN_VARIANT_PAGG;
-    int64_t off = 0, max_key = 0;
-    for (int w = 0; w < 3; w++) {
-        const DetOrder o = det_order(c, w, b);
-        const int64_t n = (w == DET_EGO && !has_att) ? 0 : std::max<int64_t>(o.K, 0);
-        if (w < which) off += n;
-        if (n) max_key = std::max(max_key, o.max_key);
-    }
-    int bits = 1;
-    while (bits < 31 && (max_key >> bits) != 0) bits++;
-    const int64_t K = (which == DET_EGO && !has_att) ? 0 : std::max<int64_t>(det_order(c, which, b).K, 0);
-    return DetScatterParams{c.at<int32_t>(c.w.okey) + off, c.at<int32_t>(c.w.osrc) + off, (int32_t)((1u << bits) - 1u), K,
-                            off / DET_CHUNK + which, rows, scal, vec, dst, c.at<float>(c.w.cpart), c.d.H};
+    const DetSegments g = det_segments(c, b);
+    const int64_t off = g.off[which];
+    return DetScatterParams{c.at<int32_t>(c.w.okey) + off, c.at<int32_t>(c.w.osrc) + off, (int32_t)((1u << g.bits) - 1u),
+                            g.n[which], off / DET_CHUNK + which, rows, scal, vec, dst, c.at<float>(c.w.cpart), c.d.H};
 }
 
 // one or two scatters (the pooling backward's pair) per launch: pass 1, then pass 2
@@ -2231,6 +2115,364 @@ int run_det_scatters(const Call &c, const DetScatterParams *list, int count) {
 int run_det_scatter(const Call &c, int which, int b, const float *rows, const float *scal, const float *vec, float *dst) {
     const DetScatterParams p = det_params(c, which, b, rows, scal, vec, dst);
     return run_det_scatters(c, &p, 1);
+}
+
+// ---- the backward's stages (pagg_backward_impl) ---------------------------------------------------------------------------
+// d Xh: the caller's g_Xh in a node-sharded call (Xh_in), else the workspace's
+inline float *grad_xh(const Call &c) { return c.a->Xh_in ? c.a->g_Xh : c.at<float>(c.w.dXh); }
+
+// the context's second stream, forked from the call's, when `fork` and there is one -- else the call's stream
+inline hipStream_t fork_if(const Call &c, bool fork) {
+    if (fork)
+        if (void *side = context_fork(c.ctx, c.stream)) return (hipStream_t)side;
+    return c.stream;
+}
+
+// classifier of micro-batch b on `s`: g_fc2_w += g_out^T . layer1, g_fc2_b += colsum(g_out) -- nothing later reads them.
+// loss (behind the fused pooling step): first the fixed-order sum of the per-node loss terms into loss[0].
+// On the second stream the end is marked for the join.
+int run_fc2_grad(const Call &c, int b, JoinGuard &joiner, hipStream_t s, const float *g_out, float *loss, float grad_scale) {
+    const Dims &d = c.d;
+    const pn_pagg_args *a = c.a;
+    const int H = d.H, Sb = c.groups(b);
+    if (loss) {
+        hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, s, c.at<const float>(c.w.outb), Sb, grad_scale, loss,
+                           d.nb == 1 ? 1 : 0);
+        PN_CHECK_HIP(hipGetLastError());
+    }
+    {
+        StageTimer tm(c.ctx, ST_FC2_GRAD, s);
+        if (a->g_fc2_w && d.det) {
+            if (int rc = launch_gemm_det(s, g_out, 1, d.C, nullptr, c.at<float>(c.w.layer1), 1, 2 * H, a->g_fc2_w, 2 * H, d.C,
+                                         2 * H, Sb, (Sb + 127) / 128, a->g_fc2_b, c.at<float>(c.w.dgemm)))
+                return rc;
+        } else if (a->g_fc2_w) {        // g_fc2_b = row sums of the A operand (g_out^T)
+            if (int rc = launch_gemm(s, g_out, 1, d.C, nullptr, c.at<float>(c.w.layer1), 1, 2 * H, a->g_fc2_w, 2 * H, nullptr,
+                                     d.C, 2 * H, Sb, 0, GEMM_ATOMIC, (Sb + 127) / 128, a->g_fc2_b))
+                return rc;
+        } else if (a->g_fc2_b) {
+            if (int rc = launch_colsum(s, g_out, nullptr, d.C, Sb, d.C, a->g_fc2_b, d.det)) return rc;
+        }
+    }
+    return s != c.stream ? joiner.mark() : PN_OK;
+}
+
+// pooling / attention backward of micro-batch b -> dhn, dXh (ego rows), dZ or dXh (attention ego), g_att_*
+PoolBwdParams pool_bwd_params(const Call &c, int b, const float *g_out) {
+    const Dims &d = c.d;
+    const pn_pagg_args *a = c.a;
+    const int homo = d.variant == PN_VARIANT_HOMO;
+    float *dXh = grad_xh(c), *scratch = c.at<float>(c.w.dl1);
+    PoolBwdParams pp{};
+    pp.variant = d.variant;
+    pp.S = c.groups(b);
+    pp.W = d.W;
+    pp.H = d.H;
+    pp.C = d.C;
+    pp.N = d.N;
+    pp.goff = c.group0(b);
+    pp.hn = c.at<float>(c.w.hn);
+    pp.ego_tab = homo ? c.Z : c.Xh;
+    pp.egoidx = c.at<int32_t>(c.w.egoidx);
+    pp.sel = c.sel(b);
+    pp.att_w = a->att_w;
+    pp.fc2_w = a->fc2_w;
+    pp.g_out = g_out;
+    pp.coef = c.at<float>(c.w.coef);
+    pp.rawsc = c.at<float>(c.w.rawsc);
+    pp.p_drop = a->p_cls;
+    pp.seed = a->seed;
+    pp.dyn = a->step_state;
+    pp.mask = a->mask_cls;
+    pp.dhn = c.at<float>(c.w.dhn);
+    pp.dXh = dXh;
+    pp.dego = homo ? c.at<float>(c.w.dZ) : dXh;
+    // attention gradients are optional outputs: fall back to scratch so the kernel needs no branches
+    pp.g_att_w = a->g_att_w ? a->g_att_w : scratch;
+    pp.g_att_b = a->g_att_b ? a->g_att_b : scratch + 2 * d.H;
+    // the attention-weight terms always go through per-workgroup partials + an ordered reduce: 325 workgroups adding
+    // to the same 2H + 1 addresses with atomics serialise
+    pp.det_att = c.at<float>(c.w.datt);
+    if (d.det) {
+        pp.det_sel = c.at<float>(c.w.dsel);
+        pp.det_ds = c.at<float>(c.w.dds);
+    }
+    return pp;
+}
+inline size_t pool_bwd_lds_bytes(const Dims &d) { return (size_t)(4 * (2 * d.W + d.H) + 8 * d.H + 8 * d.W) * sizeof(float); }
+
+// pn_pagg_train_step, default mode: pooling forward, loss and pooling backward of micro-batch b in one launch
+int run_pool_step(const Call &c, int b, const PoolBwdParams &pp, const int64_t *target, float grad_scale) {
+    const Dims &d = c.d;
+    const int H = d.H, Sb = pp.S, knob = knobs_of(c.ctx).pool_step;
+    PoolStepParams ps{};
+    ps.f = pool_fwd_params(c, b, c.a->out + (size_t)b * d.Sb * d.C);
+    ps.b = pp;
+    ps.target = target + (size_t)b * d.Sb;
+    ps.scale = grad_scale;
+    ps.gout = c.at<float>(c.w.gout);
+    ps.b.g_out = ps.gout;
+    ps.lossg = c.at<float>(c.w.outb);       // (the fused step's logits go to the caller: the slot is free)
+    const size_t lds_step = std::max(pool_bwd_lds_bytes(d), pool_fwd_lds_bytes(d));
+    StageTimer tm(c.ctx, ST_POOL_FWD, c.stream);
+    if (d.W <= 40 && H <= 128 && H >= 32 && knob >= 1 && knob != 2) {
+        // the node's rows in registers (pool_step2_kernel); PN_POOL_STEP=2: the three bodies back to back
+        hipLaunchKernelGGL((pool_step2_kernel<10, 2>), dim3(Sb), dim3(256), pool_step2_lds_bytes(10, H, d.C), c.stream, ps);
+    } else if (H <= 256) {
+        hipLaunchKernelGGL(pool_step_kernel<4>, dim3(Sb), dim3(256), lds_step, c.stream, ps);
+    } else {
+        if (int rc = ensure_dynamic_lds(c.ctx, reinterpret_cast<const void *>(pool_step_kernel<16>), (int)lds_step)) return rc;
+        hipLaunchKernelGGL(pool_step_kernel<16>, dim3(Sb), dim3(256), lds_step, c.stream, ps);
+    }
+    PN_CHECK_HIP(hipGetLastError());
+    return PN_OK;
+}
+
+// the pooling backward (pool_bwd_wg_kernel) in its stage bracket -- an empty bracket behind the pooling step, which did it
+int run_pool_bwd(const Call &c, const PoolBwdParams &pp, bool pool_step) {
+    StageTimer tm(c.ctx, ST_POOL_BWD, c.stream);
+    if (pool_step) return PN_OK;
+    const size_t lds_bytes = pool_bwd_lds_bytes(c.d);
+    if (pp.H <= 256) {
+        hipLaunchKernelGGL(pool_bwd_wg_kernel<4>, dim3(pp.S), dim3(256), lds_bytes, c.stream, pp);
+    } else {
+        if (int rc = ensure_dynamic_lds(c.ctx, reinterpret_cast<const void *>(pool_bwd_wg_kernel<16>), (int)lds_bytes)) return rc;
+        hipLaunchKernelGGL(pool_bwd_wg_kernel<16>, dim3(pp.S), dim3(256), lds_bytes, c.stream, pp);
+    }
+    PN_CHECK_HIP(hipGetLastError());
+    return PN_OK;
+}
+
+// the attention weights' terms in workgroup order (a partial per workgroup of the pooling backward) on `s`; on the second
+// stream the end is marked for the join
+int run_att_reduce(const Call &c, JoinGuard &joiner, hipStream_t s, const PoolBwdParams &pp) {
+    if (c.d.variant != PN_VARIANT_PAGG) {
+        hipLaunchKernelGGL(det_att_reduce_kernel, dim3((2 * pp.H + 4 + 63) / 64), dim3(1024), 0, s, pp.det_att, pp.S, pp.H,
+                           pp.g_att_w, pp.g_att_b);
+        PN_CHECK_HIP(hipGetLastError());
+    }
+    return s != c.stream ? joiner.mark() : PN_OK;
+}
+
+// deterministic mode: the ego half of d layer1 onto the masked nodes' rows of dXh; the attention-ego term onto the ego rows
+// (one launch per pass for the two: they write different rows -- or, for the hetero / PAGG classes whose ego rows live in
+//  dXh as well, the same rows in a fixed order: SEL, then EGO in launches of its own)
+int run_pool_scatters(const Call &c, int b, const PoolBwdParams &pp) {
+    const bool has_att = c.d.variant != PN_VARIANT_PAGG;
+    const DetScatterParams two[2] = {det_params(c, DET_SEL, b, pp.det_sel, nullptr, nullptr, pp.dXh),
+                                     det_params(c, DET_EGO, b, nullptr, pp.det_ds, c.a->att_w + c.d.H, pp.dego)};
+    if (has_att && pp.dego != pp.dXh) return run_det_scatters(c, two, 2);
+    if (int rc = run_det_scatters(c, two, 1)) return rc;
+    return has_att ? run_det_scatters(c, two + 1, 1) : PN_OK;
+}
+
+// BPTT of micro-batch b and the gather-backward scatter (mean / sum encoders: the scatter alone) -- run_seq_fwd's counterpart
+int run_seq_bwd(const Call &c, int b) {
+    const Dims &d = c.d;
+    const pn_pagg_args *a = c.a;
+    const bool f16 = d.math == PN_SEQ_MATH_F16X2;
+    const int64_t Pb = (int64_t)c.groups(b) * d.W;
+    float *dZ = c.at<float>(c.w.dZ);
+    // (deterministic mode: the fp16 BPTT stores its dx rows outright; the other kernels add into a zero-filled buffer)
+    if (d.det && !f16) PN_CHECK_HIP(hipMemsetAsync(c.at<float>(c.w.dx), 0, (size_t)Pb * d.L * d.H * sizeof(float), c.stream));
+    if (d.G == 0) {
+        if (int rc = run_seq_reduce(c, b, true)) return rc;
+    } else if (d.generic) {
+        if (int rc = run_seq_bwd_generic(c, b)) return rc;
+    } else {
+        StageTimer tm(c.ctx, ST_SEQ_BWD, c.stream);
+        SeqBwdParams sp{};
+        sp.saved = c.at<float>(c.w.saved);
+        sp.keep = (a->mask_seq || !(a->p_seq > 0.0f)) ? nullptr : c.at<const uint8_t>(c.w.keep);
+        sp.dhn = c.at<float>(c.w.dhn);
+        sp.rowidx = c.at<int32_t>(c.w.rowidx);
+        sp.slotof = c.at<int32_t>(c.w.slotof);
+        sp.WpT = c.at<float>(c.w.WpT);
+        sp.dG = c.at<float>(c.w.dG);
+        sp.dZ = dZ;
+        sp.P = (int)Pb;
+        sp.L = d.L;
+        sp.Pmask = d.P_total;
+        sp.p_drop = a->p_seq;
+        sp.seed = a->seed;
+        sp.mask = a->mask_seq;
+        sp.merge0 = d.variant != PN_VARIANT_HETERO && !d.det;   // (the hetero plan's step-0 rows are other paths' far ends: no runs)
+        if (d.det) sp.rowidx = c.at<int32_t>(c.w.iota), sp.dZ = c.at<float>(c.w.dx);     // (see det_scatter_kernel)
+        sp.range = c.at<SeqRange>(c.w.range);
+        sp.store_dx = d.det && f16;
+        if (int rc = f16 ? launch_seq_bwdh(c.ctx, c.stream, d.H, d.Gw, sp) : launch_seq_bwd3(c.ctx, c.stream, d.H, d.Gw, sp))
+            return rc;
+    }
+    if (d.det) {        // the stored mask * dx rows onto their table rows, in the order of the path steps
+        StageTimer tm(c.ctx, ST_SEQ_BWD, c.stream);
+        return run_det_scatter(c, DET_ROW, b, c.at<float>(c.w.dx), nullptr, nullptr, dZ);
+    }
+    return PN_OK;
+}
+
+// recurrent weight / bias gradients: [g_W_ih | g_W_hh] (+)= dG^T . XH, g_b (+)= colsum(dG) over the Pb * L rows of micro-batch
+// b: K-split partials into `wpart`, then their reduction.  Second stream (also in deterministic mode: the partials are
+// reduced in a fixed order, streams do not reorder a kernel's sums); the call's stream waits for it on the way out.
+int run_wgrad(const Call &c, int b, JoinGuard &joiner) {
+    const Dims &d = c.d;
+    const pn_pagg_args *a = c.a;
+    const int H = d.H, GH = d.G * H;
+    const hipStream_t ws = fork_if(c, !profiling_every_stage(c.ctx));
+    WgradParams wp{};
+    wp.dG = c.at<float>(c.w.dG);
+    wp.xh = c.at<const float>(c.w.xh);
+    wp.R = (int64_t)c.groups(b) * d.W * d.L;
+    wp.GH = GH;
+    wp.H2 = 2 * H;
+    int nz = c.w.wgrad_split;
+    // a node-sharded caller runs its reduce-scatter of d Xh (RCCL's kernels) and fc0's backward under this launch
+    // (g_Xh_ready): they need CUs whose registers are not all taken, whatever the launch's length
+    if (a->Xh_in && a->g_Xh_ready) nz = std::min(nz, std::max(1, (WGRAD_CUS_SHARED + c.w.wgrad_tiles - 1) / c.w.wgrad_tiles));
+    int64_t rps = (wp.R + nz - 1) / nz;
+    rps = (rps + WG_KT - 1) / WG_KT * WG_KT;
+    wp.rows_per_split = rps;
+    const int64_t ntiles = (wp.R + WG_KT - 1) / WG_KT;
+    const int nz_used = (int)(ntiles < nz ? ntiles : nz);
+    wp.part_w = c.at<float>(c.w.wpart);
+    wp.part_b = wp.part_w + (size_t)nz * GH * 2 * H;
+    {
+        StageTimer tm(c.ctx, ST_WGRAD, ws);
+        int nz_red = nz_used;
+        wp.range = c.at<SeqRange>(c.w.range);
+        wp.xmul = seq_xmul(a);
+        if (d.math == PN_SEQ_MATH_F16X2) {      // the two-stage pipeline on fp16 planes (pn_seqh.hip)
+            const int64_t nt16 = (wp.R + 15) / 16;
+            nz_red = (int)(nt16 < nz ? nt16 : nz);
+            if (int rc = launch_wgradh(c.ctx, ws, wp, H, nz_red)) return rc;
+        } else if (seq4_select(c.ctx, H, d.G, d.L) & SEQ4_WGRAD) {     // two-stage pipeline over K tiles of 16 rows (pn_seq4.hip)
+            const int64_t nt16 = (wp.R + 15) / 16;
+            nz_red = (int)(nt16 < nz ? nt16 : nz);
+            if (int rc = launch_wgrad4(c.ctx, ws, wp, nz_red)) return rc;
+        } else {
+            if (int rc = launch_wgrad3(c.ctx, ws, wp, nz_used)) return rc;
+        }
+        if (int rc = launch_wgrad_reduce(ws, wp.part_w, wp.part_b, nz_red, GH, H, b > 0 ? 1 : 0, d.cell == CELL_GRU ? 1 : 0,
+                                         a->g_w_ih, a->g_w_hh, a->g_b_ih, a->g_b_hh))
+            return rc;
+    }
+    return ws != c.stream ? joiner.mark() : PN_OK;
+}
+
+// distance bank backward (ReLU gate for HOMO): dXh += dZ' . bank_w ; g_bank_w = dZ'^T . Xh.  First every code's
+// contribution to d Xh (what a sharded caller's reduce-scatter waits for: g_Xh_ready), then the weight gradients.
+int run_bank_bwd(const Call &c, float *dXh, const float *dZ) {
+    pn_context *ctx = c.ctx;
+    hipStream_t stream = c.stream;
+    const pn_pagg_args *a = c.a;
+    const Dims &d = c.d;
+    const int H = d.H, L = d.L;
+    const float *Xh = c.Xh, *zgate = d.variant == PN_VARIANT_HOMO ? c.Z : nullptr;
+    float *dgemm = d.det ? c.at<float>(c.w.dgemm) : nullptr;
+    StageTimer tm(ctx, ST_BANK_BWD, stream);
+    if (d.compact) {
+        // over the touched rows, code by code (the compact rows of a code are distinct nodes: += without atomics):
+        //   dXh[node] += dZ'[row] . bank_w[code],   g_bank_w[code] += dZ'[rows]^T . Xh[nodes],   g_bank_b[code] += colsum
+        if (a->g_bank_b && !a->g_bank_w) PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: compact rows need g_bank_w with g_bank_b");
+        const int mmax = (int)std::min<int64_t>(d.N, d.ZR);
+        const int32_t *seg = c.at<const int32_t>(c.w.seg), *list = c.at<const int32_t>(c.w.list);
+        // (measured at the 10 M-node shape: the 128 x 128 tiles' read-modify-write of scattered dXh rows at two workgroups
+        //  per CU is slower than the 64 x 64 kernel's, 24.1 vs 21.6 ms for the stage; PN_NODE_GEMM3 bit 3 switches it on)
+        const bool g3 = (knobs_of(ctx).node_gemm3 & 8) && gemm3_pays(ctx, mmax, H, H, G3_BANK_DX);
+        float *bankT = c.at<float>(c.w.bankT);
+        if (g3)             // bank_w[code] [out, in] -> [in, out]: the reduction index (out) contiguous
+            for (int code = 0; code < L; code++)
+                launch_transpose(stream, a->bank_w + (size_t)code * H * H, H, H, bankT + (size_t)code * H * H);
+        for (int code = 0; code < L; code++) {
+            if (g3) {
+                if (int rc = launch_gemm3(stream, dZ, H, bankT + (size_t)code * H * H, H, dXh, H, nullptr, mmax, H, H, 0, 1, zgate,
+                                          GEMM_IND_C_ROWS, seg + code, list))
+                    return rc;
+            } else if (int rc = launch_gemm(stream, dZ, H, 1, zgate, a->bank_w + (size_t)code * H * H, 1, H, dXh, H, nullptr, mmax,
+                                            H, H, 0, GEMM_ADD, 1, nullptr, GEMM_IND_C_ROWS, seg + code, list))
+                return rc;
+        }
+        if (a->Xh_in && a->g_Xh_ready) PN_CHECK_HIP(hipEventRecord((hipEvent_t)a->g_Xh_ready, stream));
+        for (int code = 0; code < L; code++) {
+            if (a->g_bank_w && d.det) {
+                if (int rc = launch_gemm_det(stream, dZ, 1, H, zgate, Xh, 1, H, a->g_bank_w + (size_t)code * H * H, H, H, H, mmax,
+                                             (mmax + 255) / 256, a->g_bank_b ? a->g_bank_b + (size_t)code * H : nullptr, dgemm,
+                                             GEMM_IND_K, seg + code, list))
+                    return rc;
+            } else if (a->g_bank_w && rgrad_pays(ctx, mmax, H, H)) {         // large graphs: the bf16 x 3 row-reduction kernel
+                const RgradParams rp{dZ, zgate, Xh, H, H, mmax, H, H, a->g_bank_w + (size_t)code * H * H, H,
+                                     a->g_bank_b ? a->g_bank_b + (size_t)code * H : nullptr, seg + code, list};
+                if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
+            } else if (a->g_bank_w)
+                if (int rc = launch_gemm(stream, dZ, 1, H, zgate, Xh, 1, H, a->g_bank_w + (size_t)code * H * H, H, nullptr, H,
+                                         H, mmax, 0, GEMM_ATOMIC, (mmax + 255) / 256,
+                                         a->g_bank_b ? a->g_bank_b + (size_t)code * H : nullptr, GEMM_IND_K, seg + code, list))
+                    return rc;
+        }
+        return PN_OK;
+    }
+    if (gemm3_pays(ctx, d.N, H, L * H, G3_BANK_DX)) {        // bank_w [L*H, H] -> [H, L*H]
+        float *bankT = c.at<float>(c.w.bankT);
+        launch_transpose(stream, a->bank_w, L * H, H, bankT);
+        if (int rc = launch_gemm3(stream, dZ, (int64_t)L * H, bankT, (int64_t)L * H, dXh, H, nullptr, d.N, H, L * H, 0, 1, zgate))
+            return rc;
+    } else if (int rc = launch_gemm_split(stream, dZ, (int64_t)L * H, 1, zgate, a->bank_w, 1, H, dXh, H, nullptr, d.N, H, L * H,
+                                          0, GEMM_ADD, c.at<float>(c.w.gpart)))
+        return rc;
+    if (a->Xh_in && a->g_Xh_ready) PN_CHECK_HIP(hipEventRecord((hipEvent_t)a->g_Xh_ready, stream));
+    if (a->g_bank_w && d.det) {
+        if (int rc = launch_gemm_det(stream, dZ, 1, (int64_t)L * H, zgate, Xh, 1, H, a->g_bank_w, H, L * H, H, d.N,
+                                     (d.N + 255) / 256, a->g_bank_b, dgemm))
+            return rc;
+    } else if (a->g_bank_w && rgrad_pays(ctx, d.N, L * H, H)) {
+        const RgradParams rp{dZ, zgate, Xh, (int64_t)L * H, H, d.N, L * H, H, a->g_bank_w, H, a->g_bank_b, nullptr, nullptr};
+        if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
+    } else if (a->g_bank_w) {       // g_bank_b rides along as the row sums of the same (gated) A operand
+        if (int rc = launch_gemm(stream, dZ, 1, (int64_t)L * H, zgate, Xh, 1, H, a->g_bank_w, H, nullptr, L * H, H, d.N,
+                                 0, GEMM_ATOMIC, (d.N + 255) / 256, a->g_bank_b))
+            return rc;
+    } else if (a->g_bank_b) {
+        if (int rc = launch_colsum(stream, dZ, zgate, (int64_t)L * H, d.N, L * H, a->g_bank_b, d.det)) return rc;
+    }
+    return PN_OK;
+}
+
+// fc0 backward (ReLU gate for HOMO): g_fc0_w / g_fc0_b from dXh and X, then g_X = dXh' . fc0_w
+int run_fc0_bwd(const Call &c, const float *dXh) {
+    pn_context *ctx = c.ctx;
+    hipStream_t stream = c.stream;
+    const pn_pagg_args *a = c.a;
+    const Dims &d = c.d;
+    const int H = d.H;
+    const float *xgate = d.variant == PN_VARIANT_HOMO ? c.Xh : nullptr;
+    StageTimer tm(ctx, ST_FC0_BWD, stream);
+    if (a->g_fc0_w && d.det) {
+        if (int rc = launch_gemm_det(stream, dXh, 1, H, xgate, a->X, 1, d.F, a->g_fc0_w, d.F, H, d.F, d.N, (d.N + 255) / 256,
+                                     a->g_fc0_b, c.at<float>(c.w.dgemm)))
+            return rc;
+    } else if (a->g_fc0_w && d.F % 4 == 0 && rgrad_pays(ctx, d.N, H, d.F)) {
+        const RgradParams rp{dXh, xgate, a->X, H, d.F, d.N, H, d.F, a->g_fc0_w, d.F, a->g_fc0_b, nullptr, nullptr};
+        if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
+    } else if (a->g_fc0_w && xpad_floats(d) > 0 && rgrad_pays(ctx, d.N, H, (d.F + 3) / 4 * 4)) {
+        // rows of X padded to 16 bytes first (see xpad_floats); the padding columns are zeros, and outputs past F are not stored
+        const int F4 = (d.F + 3) / 4 * 4;
+        float *Xp = c.at<float>(c.w.xpad);
+        const int64_t n4 = (int64_t)d.N * (F4 / 4);
+        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, a->X, (int64_t)d.N, d.F, F4, Xp);
+        PN_CHECK_HIP(hipGetLastError());
+        const RgradParams rp{dXh, xgate, Xp, H, F4, d.N, H, d.F, a->g_fc0_w, d.F, a->g_fc0_b, nullptr, nullptr};
+        if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
+    } else if (a->g_fc0_w) {
+        if (int rc = launch_gemm(stream, dXh, 1, H, xgate, a->X, 1, d.F, a->g_fc0_w, d.F, nullptr, H, d.F, d.N, 0,
+                                 GEMM_ATOMIC, (d.N + 255) / 256, a->g_fc0_b))
+            return rc;
+    } else if (a->g_fc0_b) {
+        if (int rc = launch_colsum(stream, dXh, xgate, H, d.N, H, a->g_fc0_b, d.det)) return rc;
+    }
+    if (a->g_X)
+        if (int rc = launch_gemm(stream, dXh, H, 1, xgate, a->fc0_w, 1, d.F, a->g_X, d.F, nullptr, d.N, d.F, H, 0,
+                                 GEMM_STORE, 1))
+            return rc;
+    return PN_OK;
 }
 
 }  // namespace
@@ -2429,104 +2671,71 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
     if (a->Xh_in && !a->g_Xh) PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: g_Xh is required with Xh_in");
     if (d.nb > 1 && !fused && ((d.G > 0 && (!a->b_ih || !a->b_hh)) || !a->fc2_b || (d.variant != PN_VARIANT_PAGG && !a->att_b)))
         PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: micro-batches re-run the forward and need every forward tensor");
-    const int H = d.H, L = d.L, G = d.G, GH = G * H, GwH = d.Gw * H;     // GH: gate slots, GwH: rows of the caller's weights
-    const int homo = d.variant == PN_VARIANT_HOMO;
+    const int H = d.H, L = d.L, GwH = d.Gw * H;     // GwH: rows of the caller's recurrent weights
     const bool has_att = d.variant != PN_VARIANT_PAGG;
-    const float *Xh = c.Xh;
-    float *Z = c.Z;
-    float *dZ = c.at<float>(c.w.dZ);
-    float *dXh = a->Xh_in ? a->g_Xh : c.at<float>(c.w.dXh);
-    float *dhn = c.at<float>(c.w.dhn), *dG = c.at<float>(c.w.dG);
-    // every buffer the kernels below accumulate into (atomics / += / split-K) is cleared by ONE launch
-    ZeroList zl{};
-    auto zero = [&](float *ptr, size_t count) -> int {
-        if (ptr && count) {
-            if (zl.n >= 12) PN_FAIL(PN_ERR_ARG, "internal: zero list overflow");
-            zl.ptr[zl.n] = ptr;
-            zl.count[zl.n] = count;
-            zl.n++;
-        }
-        return PN_OK;
-    };
-    auto flush_zero = [&](hipStream_t zs = nullptr) -> int {
-        if (!zs) zs = stream;
-        if (zl.n) {
-            StageTimer tm(ctx, ST_ZERO_FILL, zs);       // (d Z and d Xh are the bulk: rows of the graph, not paths)
-            hipLaunchKernelGGL(zero_kernel, dim3(512), dim3(256), 0, zs, zl);
-            PN_CHECK_HIP(hipGetLastError());
-            zl.n = 0;
-        }
-        return PN_OK;
-    };
-    float *scratch = c.at<float>(c.w.dl1);
-    if (int rc = zero(dZ, (size_t)d.ZR * H)) return rc;
-    if (int rc = zero(dXh, (size_t)d.N * H)) return rc;
-    if (int rc = zero(a->g_att_w, has_att ? (size_t)2 * H : 0)) return rc;
-    if (int rc = zero(a->g_att_b, has_att ? 1 : 0)) return rc;
-    if (has_att && (!a->g_att_w || !a->g_att_b))
-        if (int rc = zero(scratch, (size_t)2 * H + 1)) return rc;
-    if (int rc = zero(a->g_fc2_b, (size_t)d.C)) return rc;
-    if (int rc = zero(a->g_fc2_w, (size_t)d.C * 2 * H)) return rc;
-    if (int rc = zero(a->g_bank_w, (size_t)L * H * H)) return rc;
-    if (int rc = zero(a->g_bank_b, (size_t)L * H)) return rc;
+    float *dZ = c.at<float>(c.w.dZ), *dXh = grad_xh(c);
+    ZeroFill zf{ctx};
+    if (int rc = zf.add(dZ, (size_t)d.ZR * H)) return rc;
+    if (int rc = zf.add(dXh, (size_t)d.N * H)) return rc;
+    if (int rc = zf.add(a->g_att_w, has_att ? (size_t)2 * H : 0)) return rc;
+    if (int rc = zf.add(a->g_att_b, has_att ? 1 : 0)) return rc;
+    if (has_att && (!a->g_att_w || !a->g_att_b))        // (pool_bwd_params: the attention gradients' stand-in)
+        if (int rc = zf.add(c.at<float>(c.w.dl1), (size_t)2 * H + 1)) return rc;
+    if (int rc = zf.add(a->g_fc2_b, (size_t)d.C)) return rc;
+    if (int rc = zf.add(a->g_fc2_w, (size_t)d.C * 2 * H)) return rc;
+    if (int rc = zf.add(a->g_bank_w, (size_t)L * H * H)) return rc;
+    if (int rc = zf.add(a->g_bank_b, (size_t)L * H)) return rc;
     if (!a->Xh_in) {
-        if (int rc = zero(a->g_fc0_w, (size_t)H * d.F)) return rc;
-        if (int rc = zero(a->g_fc0_b, (size_t)H)) return rc;
+        if (int rc = zf.add(a->g_fc0_w, (size_t)H * d.F)) return rc;
+        if (int rc = zf.add(a->g_fc0_b, (size_t)H)) return rc;
     }
     if (d.S == 0) {
-        if (int rc = flush_zero()) return rc;
-        if (int rc = zero(a->g_w_ih, (size_t)GwH * H)) return rc;
-        if (int rc = zero(a->g_w_hh, (size_t)GwH * H)) return rc;
-        if (int rc = zero(a->g_b_ih, (size_t)GwH)) return rc;
-        if (int rc = zero(a->g_b_hh, (size_t)GwH)) return rc;
-        if (int rc = zero(a->g_X, (size_t)d.N * d.F)) return rc;
-        if (int rc = flush_zero()) return rc;
+        if (int rc = zf.flush(stream)) return rc;
+        if (int rc = zf.add(a->g_w_ih, (size_t)GwH * H)) return rc;
+        if (int rc = zf.add(a->g_w_hh, (size_t)GwH * H)) return rc;
+        if (int rc = zf.add(a->g_b_ih, (size_t)GwH)) return rc;
+        if (int rc = zf.add(a->g_b_hh, (size_t)GwH)) return rc;
+        if (int rc = zf.add(a->g_X, (size_t)d.N * d.F)) return rc;
+        if (int rc = zf.flush(stream)) return rc;
         if (a->Xh_in && a->g_Xh_ready) PN_CHECK_HIP(hipEventRecord((hipEvent_t)a->g_Xh_ready, stream));    // (zeros: complete)
         return PN_OK;
     }
-    // (the fused step clears them after the forward of its first micro-batch instead: the forward's gigabyte of saved
-    //  tensors would push the freshly zeroed dZ out of the caches the scatter atomics want it in)
-    if (!fused)
-        if (int rc = flush_zero()) return rc;
-
     JoinGuard joiner{ctx, stream};
-    if (fused) {
-        // the zero fill rides on the second stream with the index plan (joined before the recurrence): off the chain
-        // recurrence -> pooling -> BPTT, where it used to sit because the forward's gigabyte of saved tensors evicts the
-        // freshly zeroed d Z -- 7 MB to fetch again, ~1 us of HBM time, against 5 us of launch in the chain
-        const std::function<int(hipStream_t)> zero_side = [&](hipStream_t zs) { return flush_zero(zs); };
-        if (int rc = run_tables(c, joiner, knobs_of(ctx).zero_early ? &zero_side : nullptr)) return rc;
-    }
+    // (pn_pagg_train_step: the zero fill rides on the second stream with the index plan, joined before the recurrence -- off
+    //  the chain recurrence -> pooling -> BPTT, where the forward's gigabyte of saved tensors would evict the freshly zeroed
+    //  d Z: 7 MB to fetch again, ~1 us of HBM time, against 5 us of launch in the chain)
+    if (int rc = fused ? run_tables(c, joiner, &zf) : zf.flush(stream)) return rc;
     // (per-stage timings are taken serially.  Deterministic mode: the classifier's weight gradient shares the chunk-sum
-    //  buffer `dgemm` with the bank / fc0 backward and stays in line; the recurrent weight gradient -- its own partials,
-    //  reduced in a fixed order -- goes to the second stream as in the default mode: streams do not reorder a kernel's sums)
-    const bool overlap_ok = !profiling_every_stage(ctx);
-    const bool side_ok = overlap_ok && !d.det;
-    // pn_pagg_train_step, default mode: pooling forward + loss + pooling backward of a node as one launch (pool_step_kernel)
-    const bool pool_step = fused && !d.det && knobs_of(ctx).pool_step != 0 && knobs_of(ctx).pool_bwd_wg != 0;
-    const bool f16 = d.math == PN_SEQ_MATH_F16X2;
-    const int seq4 = f16 ? 0 : seq4_select(ctx, H, G, L);
-    SeqRange *range = c.at<SeqRange>(c.w.range);
-    float *dgemm = d.det ? c.at<float>(c.w.dgemm) : nullptr;
+    //  buffer `dgemm` with the bank / fc0 backward and stays in line; the recurrent weight gradient goes to the second stream
+    //  as in the default mode: run_wgrad)
+    const bool side_ok = !profiling_every_stage(ctx) && !d.det;
+    // pn_pagg_train_step, default mode: pooling forward + loss + pooling backward of a node as one launch (run_pool_step)
+    const bool pool_step = fused && !d.det && knobs_of(ctx).pool_step != 0;
     if (d.det) {        // the identity the BPTT kernels index the contribution buffer with
         const int64_t n = std::max<int64_t>((int64_t)d.Sb * d.W * L, d.Sb);
         hipLaunchKernelGGL(det_iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c.at<int32_t>(c.w.iota), n);
         PN_CHECK_HIP(hipGetLastError());
     }
-    if (G > 0 && !d.generic) {
+    if (d.G > 0 && !d.generic) {
         StageTimer tm(ctx, ST_PLAN_PACK, stream);      // (its own bracket: ST_SEQ_BWD times the BPTT kernel alone)
-        if (f16) {
-            // (packed by the forward that left its saved tensors on this workspace -- run_pack_fwd; the fused step's
-            //  run_tables above did the same)
-        } else {
-            if (int rc = launch_pack_bwd3(stream, a->w_ih, a->w_hh, H, G, d.cell == CELL_GRU ? 1 : 0, c.at<void>(c.w.WpT))) return rc;
-        }
+        // (fp16: packed by the forward that left its saved tensors on this workspace -- run_pack_fwd, or run_tables above)
+        if (d.math != PN_SEQ_MATH_F16X2)
+            if (int rc = launch_pack_bwd3(stream, a->w_ih, a->w_hh, H, d.G, d.cell == CELL_GRU ? 1 : 0, c.at<void>(c.w.WpT))) return rc;
     }
+    // Where the launches nothing waits for go -- the loss sum behind the pooling step, the classifier gradient and the attention
+    // reduce (every fork / join is an event between two kernels of the queue and costs ~6 us of idle time there):
+    //  - the recurrent weight gradient forks off behind the BPTT anyway: the three behind ONE fork after the pooling backward,
+    //    on the second stream under the BPTT (profiles/r06_glue.txt sections 7 and 10);
+    //  - mean / sum encoders, no recurrent gradient wanted, or no context: the classifier gradient (with the loss sum) forks
+    //    on its own, ahead of the pooling backward or right behind the pooling step; the attention reduce stays in line;
+    //  - deterministic mode or every stage timed: all three in line.
+    const bool wgrad_wanted = d.G > 0 && (a->g_w_ih || a->g_w_hh || a->g_b_ih || a->g_b_hh);
+    const bool small_behind_pool = side_ok && wgrad_wanted && ctx != nullptr;
+    const bool rerun = fused || d.nb > 1;
     for (int b = 0; b < d.nb; b++) {
-        const int Sb = c.groups(b);
-        const int64_t Pb = (int64_t)Sb * d.W;
         const float *g_out = fused ? c.at<const float>(c.w.gout) : a->g_out + (size_t)b * d.Sb * d.C;
-        if (fused || d.nb > 1) {
+        float *loss_sum = pool_step ? loss : nullptr;
+        if (rerun) {
             // pn_pagg_backward with micro-batches: this micro-batch's recurrence again (same seed and positions in the
             // batch -> same dropout masks), now keeping what the BPTT needs.  pn_pagg_train_step: its one and only
             // forward, the logits go to the caller, their loss gradient to the workspace.
@@ -2537,387 +2746,41 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
             if (d.det)                      // the scatters' destination orders: second stream, under this forward
                 if (int rc = fork_det_orders(c, joiner, b)) return rc;
             if (int rc = run_seq_fwd(c, b, true)) return rc;
-            float *out_b = fused ? a->out + (size_t)b * d.Sb * d.C : c.at<float>(c.w.outb);
             if (!pool_step) {
+                float *out_b = fused ? a->out + (size_t)b * d.Sb * d.C : c.at<float>(c.w.outb);
                 if (int rc = run_pool_fwd(c, b, out_b)) return rc;
                 if (fused)
-                    if (int rc = launch_cross_entropy(out_b, target + (size_t)b * d.Sb, Sb, d.C, grad_scale, loss,
+                    if (int rc = launch_cross_entropy(out_b, target + (size_t)b * d.Sb, c.groups(b), d.C, grad_scale, loss,
                                                       c.at<float>(c.w.gout), stream, d.nb == 1))
                         return rc;
             }
-            if (fused && b == 0)
-                if (int rc = flush_zero()) return rc;
         }
-        // classifier: g_fc2_w += g_out^T . layer1, g_fc2_b += colsum(g_out) -- nothing below reads them: second stream
-        // (after the fused pooling step also the loss: the fixed-order sum of the per-node terms)
-        // Where it runs: on the second stream, forked here -- or, when the recurrent weight gradient forks off behind the BPTT
-        // anyway (defer_small), on `stream` right behind that fork together with the attention-weight reduction: every
-        // fork / join is an event between two kernels of the queue and costs ~6 us of idle time there, and the BPTT waits
-        // for none of the three (profiles/r06_glue.txt).
-        const bool wgrad_wanted = G > 0 && (a->g_w_ih || a->g_w_hh || a->g_b_ih || a->g_b_hh);
-        // (small_side, round 6: ONE fork behind the pooling backward instead -- the three small launches then run on the second
-        //  stream while the BPTT runs, where defer_small put them in front of the node-level GEMMs, the longer of the two chains
-        //  behind the BPTT.  Context knob PN_SMALL_SIDE, profiles/r06_glue.txt section 7)
-        const bool small_side = side_ok && wgrad_wanted && ctx != nullptr && knobs_of(ctx).small_side != 0;
-        const bool defer_small = side_ok && wgrad_wanted && ctx != nullptr && !small_side;
-        hipStream_t small_stream = nullptr;     // set: where run_fc2_grad / att_reduce go (small_side)
-        auto run_fc2_grad = [&]() -> int {
-        hipStream_t cstream = small_stream ? small_stream : stream;
-        if (side_ok && !defer_small && !small_stream)
-            if (void *side = context_fork(ctx, stream)) cstream = (hipStream_t)side;
-        if (pool_step) {
-            hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, cstream, c.at<const float>(c.w.outb), Sb, grad_scale, loss,
-                               d.nb == 1 ? 1 : 0);
-            PN_CHECK_HIP(hipGetLastError());
+        const PoolBwdParams pp = pool_bwd_params(c, b, g_out);
+        if (pool_step)
+            if (int rc = run_pool_step(c, b, pp, target, grad_scale)) return rc;
+        if (!small_behind_pool)
+            if (int rc = run_fc2_grad(c, b, joiner, fork_if(c, side_ok), g_out, loss_sum, grad_scale)) return rc;
+        if (int rc = run_pool_bwd(c, pp, pool_step)) return rc;
+        const hipStream_t small = fork_if(c, small_behind_pool);
+        if (small_behind_pool)
+            if (int rc = run_fc2_grad(c, b, joiner, small, g_out, loss_sum, grad_scale)) return rc;
+        if (int rc = run_att_reduce(c, joiner, small, pp)) return rc;
+        if (d.det) {
+            // (this micro-batch's orders were sorted on the second stream under its forward, when the backward re-ran it)
+            if (rerun)
+                if (int rc = joiner.join()) return rc;
+            if (int rc = run_pool_scatters(c, b, pp)) return rc;
         }
-        {
-            StageTimer tm(ctx, ST_FC2_GRAD, cstream);
-            if (a->g_fc2_w && d.det) {
-                if (int rc = launch_gemm_det(cstream, g_out, 1, d.C, nullptr, c.at<float>(c.w.layer1), 1, 2 * H, a->g_fc2_w,
-                                             2 * H, d.C, 2 * H, Sb, (Sb + 127) / 128, a->g_fc2_b, dgemm))
-                    return rc;
-            } else if (a->g_fc2_w) {        // g_fc2_b = row sums of the A operand (g_out^T)
-                if (int rc = launch_gemm(cstream, g_out, 1, d.C, nullptr, c.at<float>(c.w.layer1), 1, 2 * H, a->g_fc2_w,
-                                         2 * H, nullptr, d.C, 2 * H, Sb, 0, GEMM_ATOMIC, (Sb + 127) / 128, a->g_fc2_b))
-                    return rc;
-            } else if (a->g_fc2_b) {
-                if (int rc = launch_colsum(cstream, g_out, nullptr, d.C, Sb, d.C, a->g_fc2_b, d.det)) return rc;
-            }
-        }
-        if (cstream != stream)
-            if (int rc = joiner.mark()) return rc;
-        return PN_OK;
-        };
-        if (!pool_step && !defer_small && !small_side)
-            if (int rc = run_fc2_grad()) return rc;
-
-        // pooling / attention backward -> dhn, dXh (ego rows), dZ or dXh (attention ego), g_att_*
-        std::function<int()> att_reduce = [] { return PN_OK; };
-        {
-            PoolBwdParams pp{};
-            pp.variant = d.variant;
-            pp.S = Sb;
-            pp.W = d.W;
-            pp.H = H;
-            pp.C = d.C;
-            pp.N = d.N;
-            pp.goff = c.group0(b);
-            pp.hn = c.at<float>(c.w.hn);
-            pp.ego_tab = homo ? Z : Xh;
-            pp.egoidx = c.at<int32_t>(c.w.egoidx);
-            pp.sel = c.sel(b);
-            pp.att_w = a->att_w;
-            pp.fc2_w = a->fc2_w;
-            pp.g_out = g_out;
-            pp.coef = c.at<float>(c.w.coef);
-            pp.rawsc = c.at<float>(c.w.rawsc);
-            pp.p_drop = a->p_cls;
-            pp.seed = a->seed;
-            pp.dyn = a->step_state;
-            pp.mask = a->mask_cls;
-            pp.dhn = dhn;
-            pp.dXh = dXh;
-            pp.dego = homo ? dZ : dXh;
-            // attention gradients are optional outputs: fall back to scratch so the kernel needs no branches
-            pp.g_att_w = a->g_att_w ? a->g_att_w : scratch;
-            pp.g_att_b = a->g_att_b ? a->g_att_b : scratch + 2 * H;
-            // the attention-weight terms always go through per-workgroup partials + an ordered reduce: 325 workgroups adding
-            // to the same 2H + 1 addresses with atomics serialise
-            pp.det_att = c.at<float>(c.w.datt);
-            if (d.det) {
-                pp.det_sel = c.at<float>(c.w.dsel);
-                pp.det_ds = c.at<float>(c.w.dds);
-            }
-            const size_t lds_bytes = (size_t)(4 * (2 * d.W + H) + 8 * H + 8 * d.W) * sizeof(float);
-            // a workgroup per group (four waves share its members) unless PN_POOL_BWD_WG=0; it needs the partials buffer
-            const bool wg = (!has_att || pp.det_att) && knobs_of(ctx).pool_bwd_wg != 0;
-            int att_blocks = (Sb + 3) / 4;
-            if (pool_step) {        // pooling forward, loss and this backward in one launch (pool_step_kernel)
-                if (!wg) PN_FAIL(PN_ERR_ARG, "internal: the fused pooling step needs the workgroup-per-node backward");
-                att_blocks = Sb;
-                PoolStepParams ps{};
-                ps.f = pool_fwd_params(c, b, a->out + (size_t)b * d.Sb * d.C);
-                ps.b = pp;
-                ps.b.g_out = c.at<float>(c.w.gout);
-                ps.target = target + (size_t)b * d.Sb;
-                ps.scale = grad_scale;
-                ps.gout = c.at<float>(c.w.gout);
-                ps.lossg = c.at<float>(c.w.outb);       // (the fused step's logits go to the caller: the slot is free)
-                const size_t lds_step = std::max(lds_bytes, pool_fwd_lds_bytes(d));
-                {
-                    StageTimer tm(ctx, ST_POOL_FWD, stream);
-                    if (d.W <= 40 && H <= 128 && H >= 32 && knobs_of(ctx).pool_step >= 1 && knobs_of(ctx).pool_step != 2) {
-                        // the node's rows in registers (pool_step2_kernel); PN_POOL_STEP=2: the three bodies back to back
-                        hipLaunchKernelGGL((pool_step2_kernel<10, 2>), dim3(Sb), dim3(256), pool_step2_lds_bytes(10, H, d.C), stream, ps);
-#ifdef PN_POOL_TRACE_TWICE      // (timing experiment only: the launch again, its rows now read a second time -- results are wrong)
-                        hipLaunchKernelGGL((pool_step2_kernel<10, 2>), dim3(Sb), dim3(256), pool_step2_lds_bytes(10, H, d.C), stream, ps);
-#endif
-                    } else if (H <= 256) {
-                        hipLaunchKernelGGL(pool_step_kernel<4>, dim3(Sb), dim3(256), lds_step, stream, ps);
-                    } else {
-                        if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(pool_step_kernel<16>), (int)lds_step)) return rc;
-                        hipLaunchKernelGGL(pool_step_kernel<16>, dim3(Sb), dim3(256), lds_step, stream, ps);
-                    }
-                    PN_CHECK_HIP(hipGetLastError());
-                }
-                if (!defer_small && !small_side)
-                    if (int rc = run_fc2_grad()) return rc;
-            }
-            {
-            StageTimer tm(ctx, ST_POOL_BWD, stream);
-            if (pool_step) {
-            } else if (wg) {
-                att_blocks = Sb;
-                if (H <= 256) {
-                    hipLaunchKernelGGL(pool_bwd_wg_kernel<4>, dim3(Sb), dim3(256), lds_bytes, stream, pp);
-                } else {
-                    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(pool_bwd_wg_kernel<16>), (int)lds_bytes)) return rc;
-                    hipLaunchKernelGGL(pool_bwd_wg_kernel<16>, dim3(Sb), dim3(256), lds_bytes, stream, pp);
-                }
-            } else if (H <= 256) {
-                hipLaunchKernelGGL(pool_bwd_kernel<4>, dim3((Sb + 3) / 4), dim3(256), lds_bytes, stream, pp);
-            } else {
-                if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(pool_bwd_kernel<16>), (int)lds_bytes)) return rc;
-                hipLaunchKernelGGL(pool_bwd_kernel<16>, dim3((Sb + 3) / 4), dim3(256), lds_bytes, stream, pp);
-            }
-            PN_CHECK_HIP(hipGetLastError());
-            }
-            att_reduce = [=, &small_stream]() -> int {        // the attention weights' terms in workgroup order
-                if (has_att && pp.det_att) {
-                    hipLaunchKernelGGL(det_att_reduce_kernel, dim3((2 * H + 4 + 63) / 64), dim3(1024), 0,
-                                       small_stream ? small_stream : stream, pp.det_att, att_blocks, H, pp.g_att_w, pp.g_att_b);
-                    PN_CHECK_HIP(hipGetLastError());
-                }
-                return PN_OK;
-            };
-            if (small_side) {       // behind the pooling backward: loss sum, classifier gradient, attention reduce -> second stream
-                if (void *side = context_fork(ctx, stream)) small_stream = (hipStream_t)side;
-                if (int rc = run_fc2_grad()) return rc;
-                if (int rc = att_reduce()) return rc;
-                if (small_stream)
-                    if (int rc = joiner.mark()) return rc;
-                small_stream = nullptr;
-            } else if (!defer_small)
-                if (int rc = att_reduce()) return rc;
-            if (d.det) {
-                // (this micro-batch's orders were sorted on the second stream under its forward, when the backward re-ran it)
-                if (fused || d.nb > 1)
-                    if (int rc = joiner.join()) return rc;
-                // the ego half of d layer1 onto the masked nodes' rows of dXh; the attention-ego term onto the ego rows
-                // (one launch per pass for the two: they write different rows -- or, for the hetero / PAGG classes whose ego rows
-                //  live in dXh as well, the same rows in a fixed order: SEL first would need a launch boundary, see below)
-                const DetScatterParams two[2] = {det_params(c, DET_SEL, b, pp.det_sel, nullptr, nullptr, dXh),
-                                                 det_params(c, DET_EGO, b, nullptr, pp.det_ds, a->att_w + H, pp.dego)};
-                if (has_att && pp.dego != dXh) {
-                    if (int rc = run_det_scatters(c, two, 2)) return rc;
-                } else {        // both add into dXh: one after the other
-                    if (int rc = run_det_scatters(c, two, 1)) return rc;
-                    if (has_att)
-                        if (int rc = run_det_scatters(c, two + 1, 1)) return rc;
-                }
-            }
-        }
-
-        // recurrent weight / bias gradients: [g_W_ih | g_W_hh] (+)= dG^T . XH, g_b (+)= colsum(dG) over the Pb * L rows of this
-        // micro-batch: K-split partials into `wpart`, then their reduction.  Second stream, forked off `stream` where it is called.
-        auto run_wgrad = [&]() -> int {
-            hipStream_t wstream = stream;
-            if (overlap_ok)
-                if (void *side = context_fork(ctx, stream)) wstream = (hipStream_t)side;
-            WgradParams wp{};
-            wp.dG = dG;
-            wp.xh = c.at<const float>(c.w.xh);
-            wp.R = Pb * L;
-            wp.GH = GH;
-            wp.H2 = 2 * H;
-            int nz = c.w.wgrad_split;
-            // a node-sharded caller runs its reduce-scatter of d Xh (RCCL's kernels) and fc0's backward under this launch
-            // (g_Xh_ready): they need CUs whose registers are not all taken, whatever the launch's length
-            if (a->Xh_in && a->g_Xh_ready) nz = std::min(nz, std::max(1, (WGRAD_CUS_SHARED + c.w.wgrad_tiles - 1) / c.w.wgrad_tiles));
-            int64_t rps = (wp.R + nz - 1) / nz;
-            rps = (rps + WG_KT - 1) / WG_KT * WG_KT;
-            wp.rows_per_split = rps;
-            const int64_t ntiles = (wp.R + WG_KT - 1) / WG_KT;
-            const int nz_used = (int)(ntiles < nz ? ntiles : nz);
-            wp.part_w = c.at<float>(c.w.wpart);
-            wp.part_b = wp.part_w + (size_t)nz * GH * 2 * H;
-            {
-                StageTimer tm(ctx, ST_WGRAD, wstream);
-                int nz_red = nz_used;
-                wp.range = range;
-                wp.xmul = seq_xmul(a);
-                if (f16 && !d.generic) {        // the two-stage pipeline on fp16 planes (pn_seqh.hip)
-                    const int64_t nt16 = (wp.R + 15) / 16;
-                    nz_red = (int)(nt16 < nz ? nt16 : nz);
-                    if (int rc = launch_wgradh(ctx, wstream, wp, H, nz_red)) return rc;
-                } else if (seq4 & SEQ4_WGRAD) {        // two-stage pipeline over K tiles of 16 rows (pn_seq4.hip)
-                    const int64_t nt16 = (wp.R + 15) / 16;
-                    nz_red = (int)(nt16 < nz ? nt16 : nz);
-                    if (int rc = launch_wgrad4(ctx, wstream, wp, nz_red)) return rc;
-                } else {
-                    if (int rc = launch_wgrad3(ctx, wstream, wp, nz_used)) return rc;
-                }
-                if (int rc = launch_wgrad_reduce(wstream, wp.part_w, wp.part_b, nz_red, GH, H, b > 0 ? 1 : 0, d.cell == CELL_GRU ? 1 : 0,
-                                                 a->g_w_ih, a->g_w_hh, a->g_b_ih, a->g_b_hh))
-                    return rc;
-            }
-            if (wstream != stream)
-                if (int rc = joiner.mark()) return rc;   // `stream` waits for the weight gradients on the way out
-            return PN_OK;
-        };
-
-        // BPTT + gather-backward scatter (mean / sum encoders: the scatter alone)
-        // (the fp16 BPTT stores its rows outright; the other kernels add into a zero-filled buffer)
-        if (d.det && !(f16 && G > 0 && !d.generic))
-            PN_CHECK_HIP(hipMemsetAsync(c.at<float>(c.w.dx), 0, (size_t)Pb * L * H * sizeof(float), stream));
-        if (G == 0) {
-            if (int rc = run_seq_reduce(c, b, true)) return rc;
-        } else if (d.generic) {
-            if (int rc = run_seq_bwd_generic(c, b)) return rc;
-        } else {
-            StageTimer tm(ctx, ST_SEQ_BWD, stream);
-            SeqBwdParams sp{};
-            sp.saved = c.at<float>(c.w.saved);
-            sp.keep = (a->mask_seq || !(a->p_seq > 0.0f)) ? nullptr : c.at<const uint8_t>(c.w.keep);
-            sp.dhn = dhn;
-            sp.rowidx = c.at<int32_t>(c.w.rowidx);
-            sp.slotof = c.at<int32_t>(c.w.slotof);
-            sp.WpT = c.at<float>(c.w.WpT);
-            sp.dG = dG;
-            sp.dZ = dZ;
-            sp.P = (int)Pb;
-            sp.L = L;
-            sp.Pmask = d.P_total;
-            sp.p_drop = a->p_seq;
-            sp.seed = a->seed;
-            sp.mask = a->mask_seq;
-            sp.merge0 = d.variant != PN_VARIANT_HETERO && !d.det;   // (the hetero plan's step-0 rows are other paths' far ends: no runs)
-            if (d.det) sp.rowidx = c.at<int32_t>(c.w.iota), sp.dZ = c.at<float>(c.w.dx);     // (see det_scatter_kernel)
-            sp.range = range;
-            sp.store_dx = d.det && f16;
-            if (f16) {
-                const int gc = d.cell == CELL_GRU ? 3 : d.cell == CELL_LSTM ? 4 : 1;
-                if (int rc = launch_seq_bwdh(ctx, stream, H, gc, sp)) return rc;
-            } else if (int rc = launch_seq_bwd3(ctx, stream, H, d.cell == CELL_GRU ? 3 : d.cell == CELL_LSTM ? 4 : 1, sp))
-                return rc;
-        }
-        if (d.det) {        // the stored mask * dx rows onto their table rows, in the order of the path steps
-            StageTimer tm(ctx, ST_SEQ_BWD, stream);
-            if (int rc = run_det_scatter(c, DET_ROW, b, c.at<float>(c.w.dx), nullptr, nullptr, dZ)) return rc;
-        }
-
+        if (int rc = run_seq_bwd(c, b)) return rc;
         if (wgrad_wanted)
-            if (int rc = run_wgrad()) return rc;
-        if (defer_small) {      // behind the fork: beside the weight-gradient GEMM, ahead of the node-level GEMMs
-            if (int rc = run_fc2_grad()) return rc;
-            if (int rc = att_reduce()) return rc;
-        }
+            if (int rc = run_wgrad(c, b, joiner)) return rc;
         // the next micro-batch rewrites the [x|h] rows and dG the weight-gradient GEMM is reading
         if (b + 1 < d.nb)
             if (int rc = joiner.join()) return rc;
     }
-    // distance bank backward (ReLU gate for HOMO): dXh += dZ' . bank_w ; g_bank_w = dZ'^T . Xh
-    const float *zgate = homo ? Z : nullptr;
-    auto tm_bank = std::make_unique<StageTimer>(ctx, ST_BANK_BWD, stream);
-    if (d.compact) {
-        // over the touched rows, code by code (the compact rows of a code are distinct nodes: += without atomics):
-        //   dXh[node] += dZ'[row] . bank_w[code],   g_bank_w[code] += dZ'[rows]^T . Xh[nodes],   g_bank_b[code] += colsum
-        if (a->g_bank_b && !a->g_bank_w) PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: compact rows need g_bank_w with g_bank_b");
-        const int mmax = (int)std::min<int64_t>(d.N, d.ZR);
-        const int32_t *seg = c.at<const int32_t>(c.w.seg), *list = c.at<const int32_t>(c.w.list);
-        // (measured at the 10 M-node shape: the 128 x 128 tiles' read-modify-write of scattered dXh rows at two workgroups
-        //  per CU is slower than the 64 x 64 kernel's, 24.1 vs 21.6 ms for the stage; PN_NODE_GEMM3 bit 3 switches it on)
-        const bool g3 = (knobs_of(ctx).node_gemm3 & 8) && gemm3_pays(ctx, mmax, H, H, G3_BANK_DX);
-        float *bankT = c.at<float>(c.w.bankT);
-        if (g3)             // bank_w[code] [out, in] -> [in, out]: the reduction index (out) contiguous
-            for (int code = 0; code < L; code++)
-                launch_transpose(stream, a->bank_w + (size_t)code * H * H, H, H, bankT + (size_t)code * H * H);
-        // first every code's contribution to d Xh (what a sharded caller's reduce-scatter waits for), then the weight gradients
-        for (int code = 0; code < L; code++) {
-            if (g3) {
-                if (int rc = launch_gemm3(stream, dZ, H, bankT + (size_t)code * H * H, H, dXh, H, nullptr, mmax, H, H, 0, 1, zgate,
-                                          GEMM_IND_C_ROWS, seg + code, list))
-                    return rc;
-            } else if (int rc = launch_gemm(stream, dZ, H, 1, zgate, a->bank_w + (size_t)code * H * H, 1, H, dXh, H, nullptr, mmax,
-                                            H, H, 0, GEMM_ADD, 1, nullptr, GEMM_IND_C_ROWS, seg + code, list))
-                return rc;
-        }
-        if (a->Xh_in && a->g_Xh_ready) PN_CHECK_HIP(hipEventRecord((hipEvent_t)a->g_Xh_ready, stream));
-        for (int code = 0; code < L; code++) {
-            if (a->g_bank_w && d.det) {
-                if (int rc = launch_gemm_det(stream, dZ, 1, H, zgate, Xh, 1, H, a->g_bank_w + (size_t)code * H * H, H, H, H, mmax,
-                                             (mmax + 255) / 256, a->g_bank_b ? a->g_bank_b + (size_t)code * H : nullptr, dgemm,
-                                             GEMM_IND_K, seg + code, list))
-                    return rc;
-            } else if (a->g_bank_w && rgrad_pays(ctx, mmax, H, H)) {         // large graphs: the bf16 x 3 row-reduction kernel
-                const RgradParams rp{dZ, zgate, Xh, H, H, mmax, H, H, a->g_bank_w + (size_t)code * H * H, H,
-                                     a->g_bank_b ? a->g_bank_b + (size_t)code * H : nullptr, seg + code, list};
-                if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
-            } else if (a->g_bank_w)
-                if (int rc = launch_gemm(stream, dZ, 1, H, zgate, Xh, 1, H, a->g_bank_w + (size_t)code * H * H, H, nullptr, H,
-                                         H, mmax, 0, GEMM_ATOMIC, (mmax + 255) / 256,
-                                         a->g_bank_b ? a->g_bank_b + (size_t)code * H : nullptr, GEMM_IND_K, seg + code, list))
-                    return rc;
-        }
-    } else {
-    if (gemm3_pays(c.ctx, d.N, H, L * H, G3_BANK_DX)) {        // bank_w [L*H, H] -> [H, L*H]
-        float *bankT = c.at<float>(c.w.bankT);
-        launch_transpose(stream, a->bank_w, L * H, H, bankT);
-        if (int rc = launch_gemm3(stream, dZ, (int64_t)L * H, bankT, (int64_t)L * H, dXh, H, nullptr, d.N, H, L * H, 0, 1, zgate))
-            return rc;
-    } else if (int rc = launch_gemm_split(stream, dZ, (int64_t)L * H, 1, zgate, a->bank_w, 1, H, dXh, H, nullptr, d.N, H, L * H,
-                                          0, GEMM_ADD, c.at<float>(c.w.gpart)))
-        return rc;
-    if (a->Xh_in && a->g_Xh_ready) PN_CHECK_HIP(hipEventRecord((hipEvent_t)a->g_Xh_ready, stream));
-    if (a->g_bank_w && d.det) {
-        if (int rc = launch_gemm_det(stream, dZ, 1, (int64_t)L * H, zgate, Xh, 1, H, a->g_bank_w, H, L * H, H, d.N,
-                                     (d.N + 255) / 256, a->g_bank_b, dgemm))
-            return rc;
-    } else if (a->g_bank_w && rgrad_pays(ctx, d.N, L * H, H)) {
-        const RgradParams rp{dZ, zgate, Xh, (int64_t)L * H, H, d.N, L * H, H, a->g_bank_w, H, a->g_bank_b, nullptr, nullptr};
-        if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
-    } else if (a->g_bank_w) {       // g_bank_b rides along as the row sums of the same (gated) A operand
-        if (int rc = launch_gemm(stream, dZ, 1, (int64_t)L * H, zgate, Xh, 1, H, a->g_bank_w, H, nullptr, L * H, H, d.N,
-                                 0, GEMM_ATOMIC, (d.N + 255) / 256, a->g_bank_b))
-            return rc;
-    } else if (a->g_bank_b) {
-        if (int rc = launch_colsum(stream, dZ, zgate, (int64_t)L * H, d.N, L * H, a->g_bank_b, d.det)) return rc;
-    }
-    }
-
-    tm_bank.reset();
+    if (int rc = run_bank_bwd(c, dXh, dZ)) return rc;
     if (a->Xh_in) return PN_OK;   // the caller finishes fc0 after the reduce-scatter of g_Xh
-    // fc0 backward (ReLU gate for HOMO)
-    const float *xgate = homo ? Xh : nullptr;
-    StageTimer tm_fc0(ctx, ST_FC0_BWD, stream);
-    if (a->g_fc0_w && d.det) {
-        if (int rc = launch_gemm_det(stream, dXh, 1, H, xgate, a->X, 1, d.F, a->g_fc0_w, d.F, H, d.F, d.N, (d.N + 255) / 256,
-                                     a->g_fc0_b, dgemm))
-            return rc;
-    } else if (a->g_fc0_w && d.F % 4 == 0 && rgrad_pays(ctx, d.N, H, d.F)) {
-        const RgradParams rp{dXh, xgate, a->X, H, d.F, d.N, H, d.F, a->g_fc0_w, d.F, a->g_fc0_b, nullptr, nullptr};
-        if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
-    } else if (a->g_fc0_w && xpad_floats(d) > 0 && rgrad_pays(ctx, d.N, H, (d.F + 3) / 4 * 4)) {
-        // rows of X padded to 16 bytes first (see xpad_floats); the padding columns are zeros, and outputs past F are not stored
-        const int F4 = (d.F + 3) / 4 * 4;
-        float *Xp = c.at<float>(c.w.xpad);
-        const int64_t n4 = (int64_t)d.N * (F4 / 4);
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, a->X, (int64_t)d.N, d.F, F4, Xp);
-        PN_CHECK_HIP(hipGetLastError());
-        const RgradParams rp{dXh, xgate, Xp, H, F4, d.N, H, d.F, a->g_fc0_w, d.F, a->g_fc0_b, nullptr, nullptr};
-        if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
-    } else if (a->g_fc0_w) {
-        if (int rc = launch_gemm(stream, dXh, 1, H, xgate, a->X, 1, d.F, a->g_fc0_w, d.F, nullptr, H, d.F, d.N, 0,
-                                 GEMM_ATOMIC, (d.N + 255) / 256, a->g_fc0_b))
-            return rc;
-    } else if (a->g_fc0_b) {
-        if (int rc = launch_colsum(stream, dXh, xgate, H, d.N, H, a->g_fc0_b, d.det)) return rc;
-    }
-    if (a->g_X)
-        if (int rc = launch_gemm(stream, dXh, H, 1, xgate, a->fc0_w, 1, d.F, a->g_X, d.F, nullptr, d.N, d.F, H, 0,
-                                 GEMM_STORE, 1))
-            return rc;
-    return PN_OK;
+    return run_fc0_bwd(c, dXh);
 }
 
 int pn_pagg_backward(pn_context *ctx, const pn_pagg_args *a, void *stream) {

@@ -217,6 +217,24 @@ def test_workspace_query_and_shape_validation():
         modules.workspace_bytes("homo", 100, 16, 256, 3, 10, 833, 4)      # pooling kernels' LDS
 
 
+def test_context_knobs_defaults_and_retired_names():
+    """pn_context_get_knob with a NULL context (no GPU needed) reports the defaults a NULL context runs with
+    (include/pathnet_hip.h); the retired A/B knobs are no longer knobs."""
+    import ctypes
+    lib = _lib.load()
+    defaults = {"PN_NODE_GEMM3": 7, "PN_EVAL_ZW": 1, "PN_POOL_STEP": 1, "PN_EVENT_DEVICE_SCOPE": 1, "PN_NODE_RGRAD": 1,
+                "PN_SAMPLER_STAGE": -1, "PN_SEQ4": 4, "PN_SEQH_TAIL": 0}
+    for name, want in defaults.items():
+        v = ctypes.c_int32(12345)
+        _lib.check(lib.pn_context_get_knob(None, name.encode(), ctypes.byref(v)))
+        assert v.value == want, name
+    for name in ("PN_POOL_BWD_WG", "PN_SMALL_SIDE", "PN_ZERO_EARLY"):
+        v = ctypes.c_int32(12345)
+        with pytest.raises(_lib.PnError, match="no knob named " + name):
+            _lib.check(lib.pn_context_get_knob(None, name.encode(), ctypes.byref(v)))
+        assert v.value == 12345
+
+
 def test_sampler_cli_wrong_argc(capsys):
     assert sampler.main(["only", "two"]) == 0      # reference prints to stderr and returns 0 (gen_merw.cpp:128-132)
     assert "Incorrect number of parameters" in capsys.readouterr().err
