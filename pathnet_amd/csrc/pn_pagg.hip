@@ -2215,9 +2215,13 @@ int run_pool_step(const Call &c, int b, const PoolBwdParams &pp, const int64_t *
     ps.lossg = c.at<float>(c.w.outb);       // (the fused step's logits go to the caller: the slot is free)
     const size_t lds_step = std::max(pool_bwd_lds_bytes(d), pool_fwd_lds_bytes(d));
     StageTimer tm(c.ctx, ST_POOL_FWD, c.stream);
-    if (d.W <= 40 && H <= 128 && H >= 32 && knob >= 1 && knob != 2) {
+    // pool_step2_kernel holds the logits and their gradient in LDS (2 C floats; 6 144 + 8 C bytes at H = 128), which
+    // make_dims does not bound: past 64 KiB (C > 7 424 at H = 128) the node goes to pool_step_kernel<4>, whose LDS does
+    // not depend on C (64 W + 48 H bytes, within 64 KiB by make_dims)
+    const size_t lds_step2 = pool_step2_lds_bytes(10, H, d.C);
+    if (d.W <= 40 && H <= 128 && H >= 32 && lds_step2 <= 64 * 1024 && knob >= 1 && knob != 2) {
         // the node's rows in registers (pool_step2_kernel); PN_POOL_STEP=2: the three bodies back to back
-        hipLaunchKernelGGL((pool_step2_kernel<10, 2>), dim3(Sb), dim3(256), pool_step2_lds_bytes(10, H, d.C), c.stream, ps);
+        hipLaunchKernelGGL((pool_step2_kernel<10, 2>), dim3(Sb), dim3(256), lds_step2, c.stream, ps);
     } else if (H <= 256) {
         hipLaunchKernelGGL(pool_step_kernel<4>, dim3(Sb), dim3(256), lds_step, c.stream, ps);
     } else {

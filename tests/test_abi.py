@@ -254,16 +254,27 @@ def test_csr_build_sorted_unique_both_directions():
 
 def test_no_kernel_spills_registers():
     """The recurrent kernels prefetch weight fragments with asm loads whose destination registers the compiler must
-    not spill between the load and its wait (cdna_hip_programming.md §5.7): require zero scratch in every kernel."""
+    not spill between the load and its wait (cdna_hip_programming.md §5.7): require zero scratch in every kernel of every
+    source file under csrc/ -- the asm-load kernels live in pn_seqh / pn_seq3 / pn_seq4 / pn_gemm / pn_rgrad since the
+    round-6 split, and a glob keeps the next split covered.  (Eleven hipcc compiles: a minute or two of the CPU suite.)
+    The rocPRIM radix sort that pn_sort.hip instantiates is the library's code, not ours: its onesweep kernels keep 80
+    bytes per lane of scratch (ROCm 7.2) and are left out of the check."""
+    import glob
     import subprocess
     src = os.path.join(ROOT, "pathnet_amd", "csrc")
-    for f in ("pn_pagg.hip", "pn_sampler.hip", "pn_train.hip", "pn_merw.hip"):
+    files = sorted(os.path.basename(f) for f in glob.glob(os.path.join(src, "*.hip")))
+    # (a rename must not empty the loop: the kernels the test exists for are named here)
+    assert {"pn_seqh.hip", "pn_seq3.hip", "pn_seq4.hip", "pn_gemm.hip", "pn_rgrad.hip"} <= set(files), files
+    for f in files:
         r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
                             "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(src, f), "-o", "/dev/null"],
                            capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-500:]
-        sizes = re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)
-        assert sizes and all(int(x) == 0 for x in sizes), (f, sizes)
+        # (every kernel's remarks: its name, then its resources)
+        kernels = re.findall(r"Function Name: (\S+) .*?ScratchSize \[bytes/lane\]: (\d+)", r.stderr, re.S)
+        assert kernels, f
+        spills = [(name, int(n)) for name, n in kernels if int(n) != 0 and "rocprim" not in name]
+        assert not spills, (f, spills)
 
 
 def test_binary_path_file_is_lossless_and_rejects_garbage(tmp_path):
