@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the path-aggregation hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline line needs and nothing more: set-up, warm-up, the K timed steps, --dump-outputs if
+given, and the stdout line.  --full adds everything else the benchmark measures, after the timed region: the stage
+breakdown and the run-to-run dispersion, the shader clock probe, the hipGraph replay, the other single-GPU
+configurations and microbenchmarks, the CPU baselines, and with N > 1 the per-collective times and the multi-rank
+configurations; it also writes the whole record to bench_extras.json and stderr.
 
 One "step" = one pass of the hot path over one batch, i.e. one training step of the reference loop
 (/root/reference/PathNet_run.py:336-352) on the workload BASELINE.json's metric is quoted on
@@ -232,9 +238,10 @@ def _num(v, nd=4):
     return round(v, nd) if isinstance(v, float) else v
 
 
-def slim_line(full):
+def slim_line(full, extras=True):
     """The ONE stdout line: numbers only, every key the bench contract names, nothing else.  Everything bench.py measures
-    beyond it (other configurations, stage tables, notes) is in `full`, which goes to bench_extras.json and to stderr."""
+    beyond it (other configurations, stage tables, notes) is in `full`, which goes to bench_extras.json and to stderr
+    (extras=False: a plain run, which writes neither and names no extras file)."""
     out = _pick(full, "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "seq_math", "step_api", "data")
     cfg = full.get("config", {})
@@ -253,8 +260,8 @@ def slim_line(full):
     sb = full.get("cpu_baseline_sampler")
     if sb:
         out["cpu_baseline_sampler"] = _pick(sb, "value", "unit", "cores", "kind")
-    d = full.get("dispersion", {}).get("block_ms_per_step", {})
-    out["dispersion"] = {"block_ms_per_step": _pick(d, "min", "median", "max")}
+    if "dispersion" in full:
+        out["dispersion"] = {"block_ms_per_step": _pick(full["dispersion"].get("block_ms_per_step", {}), "min", "median", "max")}
     if "stages_ms" in full:
         out["stages_ms"] = full["stages_ms"]
     if "sampler" in full:
@@ -277,7 +284,8 @@ def slim_line(full):
         if isinstance(full.get(k), dict):
             out[k] = _pick(full[k], "value", "unit", "ms_per_step", "scaling")
     out["library_source_hash"] = full.get("library_source_hash")
-    out["extras"] = "bench_extras.json"
+    if extras:
+        out["extras"] = "bench_extras.json"
 
     def rnd(o):
         if isinstance(o, float):
@@ -298,8 +306,13 @@ def slim_line(full):
     return line
 
 
-def emit(full):
-    """extras file + stderr first, the slim stdout line LAST (so it is the last line of either stream)"""
+def emit(full, extras=True):
+    """extras file + stderr first, the slim stdout line LAST (so it is the last line of either stream); extras=False: the
+    stdout line alone"""
+    if not extras:
+        sys.stdout.write(slim_line(full, extras=False) + "\n")
+        sys.stdout.flush()
+        return
     path = os.environ.get("PN_BENCH_EXTRAS", os.path.join(ROOT, "bench_extras.json"))
     text = json.dumps(full)
     try:
@@ -673,9 +686,11 @@ SETTLE_STEPS_DUMP = 200     # --dump-outputs, one process: the most the stage-ti
 DOM_EVERY = 4       # the dominant kernel is bracketed by HIP events on every 4th step of the timed region
 
 
-def measure(sr, lib, ctx, names, steps, warmup, barrier, repeats=0, dump=False):
+def measure(sr, lib, ctx, names, steps, warmup, barrier, repeats=0, dump=False, breakdown=True):
     """warm-up with every stage bracketed (finds the dominant kernel) -> exactly `steps` timed steps with only the
     dominant kernel carrying an event pair -> per-stage breakdown.  Returns a dict.
+    breakdown=False: return right after the timed region (and the dump) -- no `repeats` regions, no dispersion, no
+    per-stage times; the steps up to the end of the timed region are the same either way.
     dump=True: the dict's "outputs" holds what the last timed step computed (StepRunner.output_arrays).  That step starts
     from the seeded initial model and a fresh Adam (StepRunner.restart), and the settling steps are a fixed
     SETTLE_STEPS_DUMP, so that its inputs -- parameters, optimizer state, paths, dropout seed -- are the same in every run:
@@ -736,6 +751,11 @@ def measure(sr, lib, ctx, names, steps, warmup, barrier, repeats=0, dump=False):
         outputs = sr.output_arrays()
         sr.outputs = None
     dom = read_profile(lib, names, ctx)[dominant]
+    res = {"elapsed": elapsed, "dominant": dominant, "dom_ms": dom[0] / dom[1], "dom_launches": dom[1], "settle_steps": settle,
+           "outputs": outputs}
+    if not breakdown:
+        _lib.check(lib.pn_profile_configure(ctx, 0, -1))
+        return res
     blocks = [elapsed / steps * 1e3]
     for r in range(max(0, repeats)):
         torch.cuda.synchronize()
@@ -770,8 +790,8 @@ def measure(sr, lib, ctx, names, steps, warmup, barrier, repeats=0, dump=False):
     torch.cuda.synchronize()
     prof = read_profile(lib, names, ctx)
     _lib.check(lib.pn_profile_configure(ctx, 0, -1))
-    return {"elapsed": elapsed, "dominant": dominant, "dom_ms": dom[0] / dom[1], "dom_launches": dom[1], "settle_steps": settle,
-            "stages_ms": {k: round(v[0] / v[1], 4) for k, v in prof.items()}, "dispersion": dispersion, "outputs": outputs}
+    res.update(stages_ms={k: round(v[0] / v[1], 4) for k, v in prof.items()}, dispersion=dispersion)
+    return res
 
 
 def measure_graph(wl, dev, steps, warmup, barrier):
@@ -1188,9 +1208,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline configuration only")
-    ap.add_argument("--no-graph", action="store_true", help="skip the hipGraph replay of the step (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures (stage breakdown, dispersion, clock "
+                         "probe, hipGraph replay, other configurations, CPU baselines, per-collective times); the whole "
+                         "record also goes to bench_extras.json and stderr.  Without it: the headline line alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other configurations")
+    ap.add_argument("--no-graph", action="store_true", help="with --full: skip the hipGraph replay of the step (N = 1 only)")
     ap.add_argument("--workload", choices=["cora", "pubmed", "bgp"], default="cora",
                     help="cora = BASELINE.json configs[1], what `value` is quoted on; pubmed = configs[2] as the timed "
                          "workload (profiling runs: tools/pmc_passes.sh); bgp = configs[3] stand-in (hetero class, "
@@ -1236,8 +1260,6 @@ def main():
     lib = _lib.load()
     ctx = _lib.context(dev)
     names = stage_names(lib)
-    info = _lib.DeviceInfo()
-    _lib.check(lib.pn_device_query(ctypes.byref(info)))
 
     if args.workload == "pubmed" and world > 1:
         raise SystemExit("--workload pubmed is a single-GPU profiling aid")
@@ -1254,15 +1276,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    clk0 = clock_mhz(lib, dev)
+    clk0 = clock_mhz(lib, dev) if args.full else None
     m = measure(sr, lib, ctx, names, args.steps, args.warmup, barrier, repeats=4 if world == 1 else 0,
-                dump=args.dump_outputs is not None)
+                dump=args.dump_outputs is not None, breakdown=args.full)
     outputs = m.pop("outputs")
     if outputs is not None and rank == 0:
         dump_outputs(outputs, args.dump_outputs)
-    clk1 = clock_mhz(lib, dev)
+    clk1 = clock_mhz(lib, dev) if args.full else None
     elapsed, dominant, dom_ms = m["elapsed"], m["dominant"], m["dom_ms"]
     collectives = None
+    S_total = S
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -1271,6 +1294,7 @@ def main():
         s_tot = torch.tensor([S], dtype=torch.int64, device=red_dev)
         dist.all_reduce(s_tot)
         S_total = int(s_tot.item())
+    if world > 1 and args.full:
         # untimed: a few steps with every collective bracketed by device synchronisation, per rank
         sr.comm.timing = True
         k = min(10, args.steps)
@@ -1309,8 +1333,6 @@ def main():
                                "stream needing the result to the collective's end, 0 when hidden (PN_BENCH_OVERLAP=0 disables)",
                        "bytes_per_step": {"all_gather_Xh": n * H * 4, "reduce_scatter_dXh": n * H * 4,
                                           "all_reduce_grads": sum(q.numel() for q in sr.model.parameters()) * 4}}
-    else:
-        S_total = S
     ms_per_step = elapsed / args.steps * 1e3
     value = S_total * W / (elapsed / args.steps)
 
@@ -1322,14 +1344,15 @@ def main():
     if tr_src:
         roofline["traffic_source"] = tr_src
     multi = {}
-    if world > 1 and not args.no_extras and args.workload == "cora" and os.environ.get("PN_BENCH_MULTI_EXTRAS", "1") != "0":
+    if (args.full and world > 1 and not args.no_extras and args.workload == "cora"
+            and os.environ.get("PN_BENCH_MULTI_EXTRAS", "1") != "0"):
         try:
             multi = multi_gpu_blocks(lib, ctx, names, dev, rank, world, red_dev, barrier, args)
         except Exception as e:      # noqa: BLE001  (annotations of the N > 1 line: never fatal to it)
             multi = {"multi_gpu_blocks_error": repr(e)[:300]}
 
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extras = extras_single_gpu(lib, ctx, names, dev, sr, args)
 
     result = {
@@ -1350,20 +1373,23 @@ def main():
                                (n, F, C, H, W, L, S_total, S_total * W, wl.get("cls", "PathNet_homo")),
                    "nodes": n, "paths_per_step": S_total * W, "parallelism": "node-shard x%d" % world},
         "roofline": roofline,
-        "stages_ms": m["stages_ms"],
-        "dispersion": m["dispersion"],
-        "device": {"name": info.name.decode(errors="replace"), "arch": info.arch.decode(errors="replace"),
-                   "compute_units": info.compute_units, "max_clock_mhz": info.clock_khz / 1e3,
-                   "shader_clock_mhz_probe": {"before": clk0, "after": clk1},
-                   "note": "probe = shader cycles per 100 MHz wall tick of a one-wave kernel right before / after the "
-                           "timed region (light load: the clock under the MFMA kernels is lower)"},
         "library_source_hash": source_hash(),
     }
+    if args.full:
+        info = _lib.DeviceInfo()
+        _lib.check(lib.pn_device_query(ctypes.byref(info)))
+        result["stages_ms"] = m["stages_ms"]
+        result["dispersion"] = m["dispersion"]
+        result["device"] = {"name": info.name.decode(errors="replace"), "arch": info.arch.decode(errors="replace"),
+                            "compute_units": info.compute_units, "max_clock_mhz": info.clock_khz / 1e3,
+                            "shader_clock_mhz_probe": {"before": clk0, "after": clk1},
+                            "note": "probe = shader cycles per 100 MHz wall tick of a one-wave kernel right before / after "
+                                    "the timed region (light load: the clock under the MFMA kernels is lower)"}
     if collectives:
         result["collectives"] = collectives
         result["collectives"]["model_prediction"] = _model_prediction("cora_weak_overlap", world)
     result.update(multi)
-    if world == 1 and not sharded and not args.no_graph and args.workload == "cora":
+    if args.full and world == 1 and not sharded and not args.no_graph and args.workload == "cora":
         # the same K steps as one captured hipGraph replayed K times (`value` / `ms_per_step` above stay the eager run)
         try:
             result["graph_replay"] = measure_graph(wl, dev, args.steps, args.warmup, barrier)
@@ -1371,7 +1397,7 @@ def main():
         except Exception as e:      # noqa: BLE001  (an extra must not take the headline line down with it)
             result["graph_replay"] = {"error": repr(e)[:300]}
     result.update(extras)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the stated baseline: the reference's op sequence on stock torch modules, best thread
         # count; the oracle's port (explicit index plan, cell loop) stays beside it as a second line
         from oracle import merw as _merw
@@ -1387,10 +1413,10 @@ def main():
         if sb:
             result["cpu_baseline_sampler"] = sb
     if rank == 0:
-        emit(result)
+        emit(result, extras=args.full)
     if world > 1:
         import torch.distributed as dist
-        dist.barrier()              # rank 0's untimed extras run a little longer: leave together
+        dist.barrier()              # (with --full) rank 0's untimed extras run a little longer: leave together
         dist.destroy_process_group()
 
 

@@ -146,3 +146,29 @@ def test_dump_outputs_writes_float_arrays_under_the_size_cap(tmp_path):
     assert (np.load(tmp_path / "b" / "x.npy") == big["x"]).all()
     with pytest.raises(AssertionError):
         bench.dump_outputs({"codes": np.zeros(4, np.uint8)}, str(tmp_path / "d"))
+
+
+PLAIN_RECORD_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                     "untimed_steps_before_timed_region", "scaling", "vs_baseline", "dtype", "data", "dtype_note", "seq_math",
+                     "step_api", "config", "roofline", "library_source_hash")
+
+
+def test_plain_emit_prints_the_line_alone(tmp_path, capsys, monkeypatch):
+    """A run without --full: the record holds the headline keys only, and emit prints its line to stdout -- no extras
+    file, nothing on stderr, no pointer to an extras file in the line"""
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    full = json.load(open(os.path.join(root, "profiles", "r05_bench_fresh_box.json")))
+    plain = {k: full[k] for k in PLAIN_RECORD_KEYS if k in full}
+    monkeypatch.setenv("PN_BENCH_EXTRAS", str(tmp_path / "extras.json"))
+    bench.emit(plain, extras=False)
+    cap = capsys.readouterr()
+    assert cap.err == "" and not (tmp_path / "extras.json").exists()
+    lines = cap.out.strip().split("\n")
+    assert len(lines) == 1
+    got = json.loads(lines[0], parse_constant=_fail_constant)
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert got[k] == full[k], k
+    assert got["value"] == float("%.6g" % full["value"]) and got["ms_per_step"] == float("%.6g" % full["ms_per_step"])
+    assert got["roofline"]["kernel"] == full["roofline"]["kernel"]
+    assert not any(k in got for k in ("extras", "dispersion", "cpu_baseline", "stages_ms", "gather"))

@@ -255,7 +255,7 @@ def test_bench_with_two_ranks_on_one_gpu(workload, launcher):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PN_BENCH_MULTI_SMALL="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PN_DIST_BACKEND"):
         env.pop(k, None)
-    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload]
+    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", workload, "--full"]
     if launcher == "self":
         cmd = [sys.executable] + tail
     else:

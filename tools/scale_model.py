@@ -3,7 +3,7 @@ measurements -- there is no multi-GPU box to measure on, so the arithmetic is wr
 
     python tools/scale_model.py [bench.json] [--link-GBs 50] [--latency-us 25] [--md]
 
-Inputs: a bench.py JSON line (stages_ms of the headline configs[1] step and of the configs[3] / configs[4] extras).
+Inputs: a `bench.py --full` JSON line (stages_ms of the headline configs[1] step and of the configs[3] / configs[4] extras).
 Model, per rank and step, R ranks:
 
   sharded work   every stage that runs over the rank's masked nodes (sampler, plan, recurrence forward / BPTT, weight
