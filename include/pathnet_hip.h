@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PN_ABI_VERSION 10 /* 2: pn_sampler_tables gained draws_per_step; pn_pairs_*, pn_uniform_*, pn_merw_*, pn_cross_entropy, pn_adam_step
+#define PN_ABI_VERSION 11 /* 2: pn_sampler_tables gained draws_per_step; pn_pairs_*, pn_uniform_*, pn_merw_*, pn_cross_entropy, pn_adam_step
                           * 4: pn_context (no process-global state); pn_pagg_shape gained S_total / group_begin / batch_groups
                           *    (micro-batches, exact sharding of the hetero class); pn_pagg_args gained reuse_tables; 64-bit
                           *    offsets throughout; pn_clock_probe
@@ -50,7 +50,9 @@ extern "C" {
                           * 8: pn_seq_range / pn_pagg_range_offset (the fp16 recurrence's operand range and the spread of the gathered
                           *    rows' magnitudes, for callers that want to fall back to bf16x3 on pathological inputs)
                           * 9: pn_adam_step_advance (the optimizer's last launch moves the step state on)
-                          * 10: pn_pagg_paths_stream (where a call reads its path arrays: a sampler enqueued there needs no event) */
+                          * 10: pn_pagg_paths_stream (where a call reads its path arrays: a sampler enqueued there needs no event)
+                          * 11: pn_tables_workspace_bytes, pn_alias_build_device, pn_csr_build_device, pn_hops_dense_device (the
+                          *     sampler's tables built on the device, bit-identical to the host builders) */
 
 #define PN_OK 0
 #define PN_ERR_ARG (-1)          /* bad argument / unsupported shape */
@@ -190,6 +192,35 @@ int pn_node_ref_pack(int32_t n, const int64_t *off, uint32_t *ref);
 /* Pack host A/B/thr arrays into the 16-byte device layout (host helper, dst is a host buffer of
  * total*4 int32 that the caller then copies to the device). */
 int pn_alias_pack(int64_t total, const int32_t *A, const int32_t *B, const uint32_t *thr, int32_t *dst);
+
+/* ---- the same tables built on the device (pn_tables.hip), bit-identical to the host builders above ------------------
+ * Every pointer is a device pointer; every call enqueues on `stream` and takes a caller-owned workspace of at least
+ * pn_tables_workspace_bytes(n, m) bytes (a bound that needs no device; one workspace serves the alias and CSR calls).
+ * The edge rows are checked first: the first row whose source or target lies outside [0, n) fails with PN_ERR_ARG
+ * naming it, as the host builders do.  That check reads one word back, so these two calls synchronise with the stream.
+ * m >= 2^31 (the radix sort's range) fails with PN_ERR_ARG. */
+int pn_tables_workspace_bytes(int32_t n, int64_t m, int64_t *bytes);
+
+/* pn_alias_build + pn_alias_pack + pn_node_ref_pack on the device: off[n+1], triples[total*4] in the walker's packed
+ * {A, B, thr, 0} layout (16-byte aligned), node_ref[n][2] (may be NULL) and the fp64 splits S[total] (may be NULL).
+ * A node with k rows has exactly k triples (every triple retires one of its pending items), so *total = m and off[]
+ * is the per-source prefix of the rows; total < 2^31 always fits node_ref.  cap = 0 only sizes (*total, off[]); then
+ * call with cap >= *total, which redoes the bucketing. */
+int pn_alias_build_device(int32_t n, int64_t m, const int32_t *u, const int32_t *v, const double *p, int64_t *off,
+                          int32_t *triples, uint32_t *node_ref, double *S, int64_t cap, int64_t *total, void *workspace,
+                          int64_t workspace_bytes, void *stream);
+
+/* pn_csr_build on the device: sorted, duplicate-free out-lists (reverse = 0) or in-lists (reverse = 1), off[n+1] and
+ * adj[*count].  Returning *count synchronises with the stream.  cap = 0 only sizes (*count, off[]); a call with
+ * cap >= *count (any upper bound, m included) also writes adj. */
+int pn_csr_build_device(int32_t n, int64_t m, const int32_t *u, const int32_t *v, int32_t reverse, int64_t *off,
+                        int32_t *adj, int64_t cap, int64_t *count, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* pn_hops_dense on the device, from the out-lists of pn_csr_build_device (off[n+1], adj with entries in [0, n); NULL
+ * when the lists are empty):
+ * dis[n*n] uint8 with the same values.  seq_len outside 1..254 fails with PN_ERR_ARG.  Needs no workspace and does
+ * not synchronise. */
+int pn_hops_dense_device(int32_t n, const int64_t *off, const int32_t *adj, int32_t seq_len, uint8_t *dis, void *stream);
 
 /* Bytes of device scratch pn_sample_paths needs for this window (0 for PN_DRAW_PHILOX). */
 int pn_sample_workspace_bytes(int32_t W, int32_t L, int32_t draw_source, int64_t epoch_count, int32_t node_count,

@@ -13,7 +13,7 @@ PN_OK = 0
 PN_ERR_ARG, PN_ERR_IO, PN_ERR_FORMAT, PN_ERR_HIP, PN_ERR_EMPTY_TABLE, PN_ERR_NOMEM, PN_ERR_CAPACITY = (
     -1, -2, -3, -4, -5, -6, -7)
 DRAW_GLIBC_REPLAY, DRAW_PHILOX = 0, 1
-ABI_VERSION = 10              # PN_ABI_VERSION of include/pathnet_hip.h this binding was written against
+ABI_VERSION = 11            # PN_ABI_VERSION of include/pathnet_hip.h this binding was written against
 VARIANT_HETERO, VARIANT_HOMO, VARIANT_PAGG = 0, 1, 2
 CELL_DEFAULT, CELL_LSTM, CELL_RNN, CELL_GRU, CELL_MEAN, CELL_SUM = 0, 1, 2, 3, 4, 5
 SEQ_MATH_DEFAULT, SEQ_MATH_BF16X3, SEQ_MATH_F16X2 = 0, 1, 2     # pn_pagg_shape.seq_math
@@ -99,6 +99,12 @@ SIGNATURES = {
     "pn_csr_build": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_i32p, c_i32p, ctypes.c_int32, c_i64p, c_i32p,
                                     ctypes.c_int64, c_i64p]),
     "pn_glibc_draws": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int64, c_i32p]),
+    "pn_tables_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_i64p]),
+    "pn_alias_build_device": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64,
+                                             c_i64p, vp, ctypes.c_int64, vp]),
+    "pn_csr_build_device": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, vp, vp, ctypes.c_int32, vp, vp,
+                                           ctypes.c_int64, c_i64p, vp, ctypes.c_int64, vp]),
+    "pn_hops_dense_device": (ctypes.c_int, [ctypes.c_int32, vp, vp, ctypes.c_int32, vp, vp]),
     "pn_sample_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                                  ctypes.c_int32, c_i64p]),
     "pn_sample_paths": (ctypes.c_int, [vp, ctypes.POINTER(SamplerTables), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

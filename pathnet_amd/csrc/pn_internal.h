@@ -95,7 +95,7 @@ struct StageTimer {
 int launch_cross_entropy(const float *logits, const int64_t *target, int rows, int classes, float scale, float *loss,
                          float *g_logits, void *stream, bool overwrite = false);
 
-// ---- stable radix sort of (int32 key, int32 value) pairs (pn_sort.hip; the deterministic backward) ----------------
+// ---- stable radix sort of (int32 key, int32 value) pairs (pn_sort.hip; the deterministic backward, pn_tables.hip) -
 size_t sort_temp_reserve(int64_t n);        // bytes of temporary storage to reserve for n pairs (no device needed)
 int sort_pairs_i32(void *tmp, size_t tmp_bytes, const int32_t *keys_in, int32_t *keys_out, const int32_t *vals_in,
                    int32_t *vals_out, int64_t n, int key_bits, void *stream);

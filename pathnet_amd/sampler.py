@@ -114,6 +114,79 @@ def csr_build(n, u, v, reverse=False):
     return off, adj[:cnt.value]
 
 
+def _cuda_device(device):
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def _on_device(x, dtype, device):
+    """x (NumPy array or tensor) as a contiguous `dtype` tensor on `device`; a dtype conversion runs there."""
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    return t.to(device=device).to(dtype).contiguous()
+
+
+def tables_workspace(n, m, device="cuda"):
+    """A workspace for the device table builders (pn_tables_workspace_bytes(n, m) bytes, uint8 on `device`)."""
+    need = ctypes.c_int64(0)
+    _lib.check(_lib.load().pn_tables_workspace_bytes(int(n), int(m), ctypes.byref(need)))
+    return torch.empty(need.value, dtype=torch.uint8, device=device)
+
+
+def build_alias_device(n, u, v, p, device="cuda", split=False, workspace=None):
+    """build_alias + pn_alias_pack + pn_node_ref_pack on the GPU (pn_alias_build_device), bit-identical.
+    u / v / p: NumPy arrays or tensors (int32 / int32 / float64 on `device`; anything else is uploaded and converted).
+    -> device tensors off int64 [n+1], packed int32 [max(total, 1) * 4] {A, B, thr, 0}, node_ref int32 [max(n, 1) * 2]
+    (uint32 bits) and, with split=True, S float64 [total] (else None).  total = the number of rows."""
+    dev = _cuda_device(device)
+    with torch.cuda.device(dev):
+        u, v, p = _on_device(u, torch.int32, dev), _on_device(v, torch.int32, dev), _on_device(p, torch.float64, dev)
+        m = int(u.numel())
+        if int(v.numel()) != m or int(p.numel()) != m:
+            raise ValueError("build_alias_device: u, v and p must have the same length")
+        ws = workspace if workspace is not None else tables_workspace(n, m, dev)
+        off = torch.empty(int(n) + 1, dtype=torch.int64, device=dev)
+        packed = torch.empty(max(m, 1) * 4, dtype=torch.int32, device=dev)
+        node_ref = torch.empty(2 * max(int(n), 1), dtype=torch.int32, device=dev)
+        S = torch.empty(max(m, 1), dtype=torch.float64, device=dev) if split else None
+        total = ctypes.c_int64(0)
+        _lib.check(_lib.load().pn_alias_build_device(int(n), m, _lib.ptr(u), _lib.ptr(v), _lib.ptr(p), _lib.ptr(off),
+                                                     _lib.ptr(packed), _lib.ptr(node_ref), _lib.ptr(S), max(m, 1),
+                                                     ctypes.byref(total), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    return off, packed, node_ref, (S[:total.value] if split else None)
+
+
+def csr_build_device(n, u, v, reverse=False, device="cuda", workspace=None):
+    """csr_build on the GPU (pn_csr_build_device), bit-identical: device tensors off int64 [n+1], adj int32 [count].
+    u / v as for build_alias_device."""
+    dev = _cuda_device(device)
+    with torch.cuda.device(dev):
+        u, v = _on_device(u, torch.int32, dev), _on_device(v, torch.int32, dev)
+        m = int(u.numel())
+        if int(v.numel()) != m:
+            raise ValueError("csr_build_device: u and v must have the same length")
+        ws = workspace if workspace is not None else tables_workspace(n, m, dev)
+        off = torch.empty(int(n) + 1, dtype=torch.int64, device=dev)
+        adj = torch.empty(max(m, 1), dtype=torch.int32, device=dev)     # m bounds the count: one call, no sizing pass
+        cnt = ctypes.c_int64(0)
+        _lib.check(_lib.load().pn_csr_build_device(int(n), m, _lib.ptr(u), _lib.ptr(v), 1 if reverse else 0,
+                                                   _lib.ptr(off), _lib.ptr(adj), max(m, 1), ctypes.byref(cnt),
+                                                   _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    return off, adj[:cnt.value]
+
+
+def hops_dense_device(n, off, adj, seq_len):
+    """hops_dense on the GPU (pn_hops_dense_device) from the out-lists of csr_build_device: dis [n, n] uint8 on their
+    device, the same values."""
+    dev = off.device
+    dis = torch.empty((int(n), int(n)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().pn_hops_dense_device(int(n), _lib.ptr(off), _lib.ptr(adj), int(seq_len), _lib.ptr(dis),
+                                                    _lib.stream_ptr(dev)))
+    return dis
+
+
 def glibc_draws(seed, first, count):
     out = np.empty(count, np.int32)
     _lib.check(_lib.load().pn_glibc_draws(seed & 0xFFFFFFFF, first, count, _lib.np_ptr(out, ctypes.c_int32)))
@@ -127,9 +200,19 @@ class MerwSampler:
 
     draws_per_step = 2              # the alias roll: slot draw + probability draw (gen_merw.cpp:81-91)
 
-    def __init__(self, n, u, v, p, seq_len, device="cuda", hops="auto"):
+    def __init__(self, n, u, v, p, seq_len, device="cuda", hops="auto", build="host"):
         """hops: "dense" = the reference's dis[n][n] byte table in HBM; "otf" = exact hop codes derived on the
-        fly from CSR lists (any n); "auto" picks dense while n*n <= DENSE_LIMIT_BYTES."""
+        fly from CSR lists (any n); "auto" picks dense while n*n <= DENSE_LIMIT_BYTES.
+        build: "host" = the host builders, then one upload (self.host keeps their arrays); "device" = the same tables,
+        bit-identical, built on `device` (pn_tables.hip) from the rows -- NumPy arrays (uploaded once) or device
+        tensors -- and self.host is None."""
+        if build not in ("host", "device"):
+            raise ValueError("build must be 'host' or 'device'")
+        if hops not in ("dense", "otf", "auto"):
+            raise ValueError("hops must be 'dense', 'otf' or 'auto'")
+        if build == "device":
+            self._build_on_device(n, u, v, p, seq_len, device, hops)
+            return
         off, A, B, S, thr = build_alias(n, u, v, p)
         self.host = dict(off=off, A=A, B=B, S=S, thr=thr)
         packed = np.empty(max(len(A), 1) * 4, np.int32)
@@ -137,18 +220,41 @@ class MerwSampler:
                                              _lib.np_ptr(thr, ctypes.c_uint32), _lib.np_ptr(packed, ctypes.c_int32)))
         self._upload(n, seq_len, device, hops, off, packed, len(A), u, v)
 
-    def _upload(self, n, seq_len, device, hops, off, packed, total, eu, ev):
-        """Device copies of the walker table (off, packed) and of the hop-code source built from the directed edge
-        list (eu -> ev): the dense table or the two CSR lists."""
+    def _place(self, n, seq_len, device, hops):
         self.n, self.L = int(n), int(seq_len)
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _cuda_device(device)
         if hops == "auto":
             hops = "dense" if self.n * self.n <= self.DENSE_LIMIT_BYTES else "otf"
         if hops not in ("dense", "otf"):
             raise ValueError("hops must be 'dense', 'otf' or 'auto'")
         self.hops = hops
+
+    def _build_on_device(self, n, u, v, p, seq_len, device, hops):
+        """build="device": the walker table, node_ref and the hop-code source, all built on self.device."""
+        self._place(n, seq_len, device, hops)
+        if self.hops == "otf" and seq_len > 8:
+            raise ValueError("on-the-fly hop codes support path lengths up to 8")
+        dev = self.device
+        with torch.cuda.device(dev):
+            u, v, p = _on_device(u, torch.int32, dev), _on_device(v, torch.int32, dev), _on_device(p, torch.float64, dev)
+            ws = tables_workspace(n, u.numel(), dev)
+            self.d_off, self.d_triples, self.d_node_ref, _ = build_alias_device(n, u, v, p, dev, workspace=ws)
+            self.d_dis = self.d_adj_off = self.d_adj = self.d_radj_off = self.d_radj = None
+            if self.hops == "dense":
+                self.d_dis = hops_dense_device(n, *csr_build_device(n, u, v, False, dev, workspace=ws), seq_len)
+            else:
+                self.d_adj_off, self.d_adj = csr_build_device(n, u, v, False, dev, workspace=ws)
+                self.d_radj_off, self.d_radj = csr_build_device(n, u, v, True, dev, workspace=ws)
+            self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.host = None
+        self.total = int(u.numel())
+        self._ws = None
+
+    def _upload(self, n, seq_len, device, hops, off, packed, total, eu, ev):
+        """Device copies of the walker table (off, packed) and of the hop-code source built from the directed edge
+        list (eu -> ev): the dense table or the two CSR lists."""
+        self._place(n, seq_len, device, hops)
+        hops = self.hops
         self.d_off = torch.from_numpy(off).to(self.device)
         self.d_triples = torch.from_numpy(packed).to(self.device)
         self.d_node_ref = None
@@ -172,9 +278,9 @@ class MerwSampler:
         self._ws = None
 
     @classmethod
-    def from_edge_file(cls, path, seq_len, device="cuda", hops="auto"):
+    def from_edge_file(cls, path, seq_len, device="cuda", hops="auto", build="host"):
         n, u, v, p = read_edge_file(path)
-        return cls(n, u, v, p, seq_len, device=device, hops=hops)
+        return cls(n, u, v, p, seq_len, device=device, hops=hops, build=build)
 
     def sample(self, W, seed, epoch_begin=0, epoch_count=1, node_begin=0, node_count=None,
                draw_source=DRAW_PHILOX, check=True, out=None, step_state=None, nodes=None):

@@ -1,9 +1,15 @@
 #!/usr/bin/env python
-"""Host-side set-up of the sampler (gen_merw.cpp:162-179: edge file -> per-node lists -> alias tables -> bfs/dis),
-timed stage by stage on the CPU (no GPU needed).
+"""Set-up of the sampler (gen_merw.cpp:162-179: edge file -> per-node lists -> alias tables -> bfs/dis).
 
     python tools/bench_sampler_setup.py [n_nodes=19717] [L=4] [dense|otf]
+        the host builders timed stage by stage on the CPU (no GPU needed)
+    python tools/bench_sampler_setup.py [n_nodes] [L] [dense|otf] --build host|device|both [--repeats 3]
+        MerwSampler(..., build=...) on the GPU from the Erdos-Renyi rows in memory: wall clock of the whole set-up
+        (tables + upload, or upload + device build) ending in torch.cuda.synchronize(), after one warm-up build of each
+        kind on a small graph (code-object load excluded); prints one JSON line with host_sampler_tables_s and / or
+        device_sampler_tables_s (median) and their spread
 """
+import json
 import os
 import sys
 import tempfile
@@ -15,10 +21,7 @@ from pathnet_amd import sampler  # noqa: E402
 from tools.bench_sampler_large import er_graph  # noqa: E402
 
 
-def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 19717
-    L = int(sys.argv[2]) if len(sys.argv) > 2 else 4
-    mode = sys.argv[3] if len(sys.argv) > 3 else ("dense" if n <= 50000 else "otf")
+def host_stages(n, L, mode):
     g = er_graph(n, 16, 0)
     d = tempfile.mkdtemp(prefix="pn_setup_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     f = os.path.join(d, "g.in")
@@ -44,6 +47,49 @@ def main():
         if os.path.exists(f):
             os.remove(f)
         os.rmdir(d)
+
+
+def timed_builds(n, L, mode, builds, repeats):
+    import torch
+    small = er_graph(1000, 16, 1)
+    for b in builds:                                # warm-up: code objects, allocator, host thread pool
+        sampler.MerwSampler(*small, L, hops=mode, build=b)
+    torch.cuda.synchronize()
+    g = er_graph(n, 16, 0)
+    rec = {"n": n, "rows": len(g[1]), "L": L, "hops": mode, "repeats": repeats}
+    for b in builds:
+        ts = []
+        for _ in range(repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            smp = sampler.MerwSampler(*g, L, hops=mode, build=b)
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+            del smp
+        ts.sort()
+        rec["%s_sampler_tables_s" % b] = round(ts[len(ts) // 2], 4)
+        rec["%s_sampler_tables_s_all" % b] = [round(t, 4) for t in ts]
+    return rec
+
+
+def main():
+    argv = list(sys.argv[1:])
+    builds, repeats = None, 3
+    if "--build" in argv:
+        i = argv.index("--build")
+        builds = ["host", "device"] if argv[i + 1] == "both" else [argv[i + 1]]
+        del argv[i:i + 2]
+    if "--repeats" in argv:
+        i = argv.index("--repeats")
+        repeats = int(argv[i + 1])
+        del argv[i:i + 2]
+    n = int(argv[0]) if len(argv) > 0 else 19717
+    L = int(argv[1]) if len(argv) > 1 else 4
+    mode = argv[2] if len(argv) > 2 else ("dense" if n <= 50000 else "otf")
+    if builds is None:
+        host_stages(n, L, mode)
+    else:
+        print(json.dumps(timed_builds(n, L, mode, builds, repeats)))
 
 
 if __name__ == "__main__":
