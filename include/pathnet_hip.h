@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PN_ABI_VERSION 11 /* 2: pn_sampler_tables gained draws_per_step; pn_pairs_*, pn_uniform_*, pn_merw_*, pn_cross_entropy, pn_adam_step
+#define PN_ABI_VERSION 12 /* 2: pn_sampler_tables gained draws_per_step; pn_pairs_*, pn_uniform_*, pn_merw_*, pn_cross_entropy, pn_adam_step
                           * 4: pn_context (no process-global state); pn_pagg_shape gained S_total / group_begin / batch_groups
                           *    (micro-batches, exact sharding of the hetero class); pn_pagg_args gained reuse_tables; 64-bit
                           *    offsets throughout; pn_clock_probe
@@ -52,7 +52,9 @@ extern "C" {
                           * 9: pn_adam_step_advance (the optimizer's last launch moves the step state on)
                           * 10: pn_pagg_paths_stream (where a call reads its path arrays: a sampler enqueued there needs no event)
                           * 11: pn_tables_workspace_bytes, pn_alias_build_device, pn_csr_build_device, pn_hops_dense_device (the
-                          *     sampler's tables built on the device, bit-identical to the host builders) */
+                          *     sampler's tables built on the device, bit-identical to the host builders)
+                          * 12: pn_pagg_args gained out_embed / out_path_weight / out_path_state / g_embed (the classifier input
+                          *     and the pooling coefficients and final hidden states of the paths, and a gradient on the first) */
 
 #define PN_OK 0
 #define PN_ERR_ARG (-1)          /* bad argument / unsupported shape */
@@ -395,6 +397,25 @@ typedef struct pn_pagg_args {
     int32_t index_rows_local;
     /* dev or NULL: the dropout seed is step_state->seed, read when the kernels run (hipGraph replay), instead of `seed` */
     const pn_step_state *step_state;
+    /* Optional outputs of pn_pagg_forward (dev or NULL; NULL: not written, the forward is what it is without them), rows of
+     * the slice's S masked nodes like `out`:
+     *   out_embed [S, 2H]: the classifier input BEFORE the classifier's dropout, [Xh[sel[s]] | pooled paths of s] (layer1 =
+     *       torch.cat((ego, h_n), dim=1) at PathNet_run.py:207 / :275, copy.py:355, ahead of F.dropout); in training it
+     *       holds the sequence dropout of the same call.
+     *   out_path_weight [S, W]: the coefficient that multiplies member j's final hidden state in row s's mean -- the softmax
+     *       weight (HETERO), 1 + att (HOMO), 1 (PAGG).
+     *   out_path_state [S, W, H]: member j's final hidden state.
+     * Members are in the reference's order: for HOMO / PAGG member j of row s is path j of masked node s; for HETERO it is
+     * slot q = j * S_total + (group_begin + s) of the reference's scrambled LSTM batch (the [W, S] re-view of
+     * PathNet_run.py:196-197), whose steps come from other masked nodes' paths (oracle/pagg_oracle.py: plan).
+     * pn_pagg_backward's re-runs of micro-batches write none of them.
+     * g_embed [S, 2H] (pn_pagg_backward, dev or NULL): upstream gradient on out_embed.  The backward computes the gradients
+     * of sum(out * g_out) + sum(out_embed * g_embed); one of g_out / g_embed may be NULL (g_out NULL: g_fc2_* are zero).
+     * pn_pagg_train_step refuses all four (PN_ERR_ARG). */
+    float *out_embed;
+    float *out_path_weight;
+    float *out_path_state;
+    const float *g_embed;
 } pn_pagg_args;
 
 int pn_pagg_workspace_bytes(const pn_pagg_shape *shape, int64_t *bytes);
@@ -424,9 +445,10 @@ int pn_pagg_range_offset(const pn_pagg_shape *shape, int64_t *offset);
  * event on `stream`, and runs under whatever that stream still holds of the previous step (the recurrent weight gradient):
  * the walk leaves the step's critical path.  Ask before every call (the answer follows pn_profile_configure). */
 int pn_pagg_paths_stream(pn_context *ctx, const pn_pagg_shape *shape, void *stream, void **out);
-/* out = forward(...).  Leaves what backward needs in the workspace. */
+/* out = forward(...) (and the optional out_embed / out_path_weight / out_path_state).  Leaves what backward needs in the
+ * workspace. */
 int pn_pagg_forward(pn_context *ctx, const pn_pagg_args *args, void *stream);
-/* Gradients of sum(out * g_out) w.r.t. every parameter (overwritten, not accumulated) and X.
+/* Gradients of sum(out * g_out) [+ sum(out_embed * g_embed)] w.r.t. every parameter (overwritten, not accumulated) and X.
  * Must follow a pn_pagg_forward (no_save = 0) on the same args/workspace with the same weights: the saved tensors, the index
  * plan and -- fp16 mode -- the weights' operand ranges and their packed planes for the BPTT (written by the forward's packing
  * stream, off the backward's critical path) live there. */

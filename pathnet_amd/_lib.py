@@ -13,7 +13,7 @@ PN_OK = 0
 PN_ERR_ARG, PN_ERR_IO, PN_ERR_FORMAT, PN_ERR_HIP, PN_ERR_EMPTY_TABLE, PN_ERR_NOMEM, PN_ERR_CAPACITY = (
     -1, -2, -3, -4, -5, -6, -7)
 DRAW_GLIBC_REPLAY, DRAW_PHILOX = 0, 1
-ABI_VERSION = 11            # PN_ABI_VERSION of include/pathnet_hip.h this binding was written against
+ABI_VERSION = 12            # PN_ABI_VERSION of include/pathnet_hip.h this binding was written against
 VARIANT_HETERO, VARIANT_HOMO, VARIANT_PAGG = 0, 1, 2
 CELL_DEFAULT, CELL_LSTM, CELL_RNN, CELL_GRU, CELL_MEAN, CELL_SUM = 0, 1, 2, 3, 4, 5
 SEQ_MATH_DEFAULT, SEQ_MATH_BF16X3, SEQ_MATH_F16X2 = 0, 1, 2     # pn_pagg_shape.seq_math
@@ -67,7 +67,9 @@ class PaggArgs(ctypes.Structure):
                                           "att_b", "fc2_w", "fc2_b")] +
                 [("Xh_in", vp), ("g_Xh", vp), ("Xh_ready", vp), ("g_Xh_ready", vp), ("no_save", ctypes.c_int32),
                  ("reuse_tables", ctypes.c_int32),
-                 ("index_rows_local", ctypes.c_int32), ("step_state", vp)])
+                 ("index_rows_local", ctypes.c_int32), ("step_state", vp),
+                 # optional outputs of the forward / gradient on the first of them in the backward (ABI 12)
+                 ("out_embed", vp), ("out_path_weight", vp), ("out_path_state", vp), ("g_embed", vp)])
 
 
 # name -> (restype, argtypes): every symbol include/pathnet_hip.h declares

@@ -465,6 +465,11 @@ struct PoolParams {
     float *rawsc;           // [P] raw attention score (pre LeakyReLU) per slot'
     float *layer1;          // [S, 2H] classifier input after dropout
     float *out;             // [S, C]
+    // optional outputs (pn_pagg_args.out_*), rows of this launch's groups; null: not written (kernel arguments: the tests
+    // below are uniform over the grid -- the pooling steps, which never set them, run the same code as before)
+    float *embed;           // [S, 2H] classifier input before the dropout
+    float *path_weight;     // [S, W]  coef in member order
+    float *path_state;      // [S, W, H] hn in member order
 };
 
 __device__ __forceinline__ void pool_fwd_body(const PoolParams &p, float *lds) {
@@ -538,6 +543,13 @@ __device__ __forceinline__ void pool_fwd_body(const PoolParams &p, float *lds) {
     }
     __syncthreads();
     for (int mem = tid; mem < W; mem += 256) p.coef[(int64_t)g * W + mem] = sc[mem];
+    if (p.path_weight)
+        for (int mem = tid; mem < W; mem += 256) p.path_weight[(int64_t)g * W + mem] = sc[mem];
+    if (p.path_state) {     // the group's W rows of hn are already in member order: one contiguous copy (H % 32 == 0)
+        const float4 *src = reinterpret_cast<const float4 *>(p.hn + (int64_t)g * W * H);
+        float4 *dst = reinterpret_cast<float4 *>(p.path_state + (int64_t)g * W * H);
+        for (int i = tid; i < W * H / 4; i += 256) dst[i] = src[i];
+    }
 
     // pooled = mean_w coef_w * h_w: each wave sums its quarter of the members, the quarters meet in LDS (fixed order)
     {
@@ -555,6 +567,10 @@ __device__ __forceinline__ void pool_fwd_body(const PoolParams &p, float *lds) {
     const float *ego = p.Xh + (int64_t)min(max(p.sel[g], 0), p.N - 1) * H;
     for (int j = tid; j < H; j += 256) {
         float a = ego[j], b = (part4[j] + part4[H + j] + part4[2 * H + j] + part4[3 * H + j]) * inv_w;
+        if (p.embed) {
+            p.embed[(int64_t)g * 2 * H + j] = a;
+            p.embed[(int64_t)g * 2 * H + H + j] = b;
+        }
         const uint64_t gg = (uint64_t)(p.goff + g);
         if (p.mask) {
             a *= p.mask[gg * 2 * H + j];
@@ -609,6 +625,9 @@ struct PoolBwdParams {
     float *det_sel;    // [S, H]
     float *det_ds;     // [P]
     float *det_att;    // [workgroups][2H + 4]
+    // pn_pagg_args.g_embed: d loss / d (classifier input before the dropout) [S, 2H] of this launch's groups, or null.  g_out
+    // may be null when it is set (the classifier's term is then absent)
+    const float *g_embed;
 };
 
 // A workgroup per group: the W members of a group split over the four waves.  (A wavefront per group ran its ~50 dependent
@@ -636,11 +655,12 @@ __device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *
     }
     for (int j = tid; j < H; j += 256) {
         float a = 0.0f, b = 0.0f;
-        for (int c = 0; c < p.C; c++) {
-            const float go = p.g_out[(int64_t)g * p.C + c];
-            a += go * p.fc2_w[(int64_t)c * 2 * H + j];
-            b += go * p.fc2_w[(int64_t)c * 2 * H + H + j];
-        }
+        if (p.g_out)
+            for (int c = 0; c < p.C; c++) {
+                const float go = p.g_out[(int64_t)g * p.C + c];
+                a += go * p.fc2_w[(int64_t)c * 2 * H + j];
+                b += go * p.fc2_w[(int64_t)c * 2 * H + H + j];
+            }
         const uint64_t gg = (uint64_t)(p.goff + g);
         if (p.mask) {
             a *= p.mask[gg * 2 * H + j];
@@ -649,6 +669,10 @@ __device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *
             const uint64_t seed = p.dyn ? p.dyn->seed : p.seed;
             a *= dropout1(seed, gg * 2 * H + j, 2u, p.p_drop);
             b *= dropout1(seed, gg * 2 * H + H + j, 2u, p.p_drop);
+        }
+        if (p.g_embed) {    // the embedding is read before the dropout: its gradient joins behind the mask
+            a += p.g_embed[(int64_t)g * 2 * H + j];
+            b += p.g_embed[(int64_t)g * 2 * H + H + j];
         }
         if (p.det_sel)
             p.det_sel[(int64_t)g * H + j] = a;
@@ -1891,8 +1915,17 @@ PoolParams pool_fwd_params(const Call &c, int b, float *out) {
     return pp;
 }
 inline size_t pool_fwd_lds_bytes(const Dims &d) { return (size_t)(2 * d.W + 6 * d.H) * sizeof(float); }
-int run_pool_fwd(const Call &c, int b, float *out) {
-    const PoolParams pp = pool_fwd_params(c, b, out);
+// outputs: pn_pagg_forward's own pass writes the caller's optional outputs (out_*: rows of micro-batch b); the backward's
+// re-runs do not
+int run_pool_fwd(const Call &c, int b, float *out, bool outputs = false) {
+    PoolParams pp = pool_fwd_params(c, b, out);
+    if (outputs) {
+        const pn_pagg_args *a = c.a;
+        const int64_t r0 = (int64_t)b * c.d.Sb;       // first row of the slice's outputs (= c.group0(b) - group_begin)
+        if (a->out_embed) pp.embed = a->out_embed + r0 * 2 * c.d.H;
+        if (a->out_path_weight) pp.path_weight = a->out_path_weight + r0 * c.d.W;
+        if (a->out_path_state) pp.path_state = a->out_path_state + r0 * c.d.W * c.d.H;
+    }
     StageTimer tm(c.ctx, ST_POOL_FWD, c.stream);
     hipLaunchKernelGGL(pool_fwd_kernel, dim3(pp.S), dim3(256), pool_fwd_lds_bytes(c.d), c.stream, pp);
     PN_CHECK_HIP(hipGetLastError());
@@ -1907,6 +1940,8 @@ int check_forward_args(const Call &c, const char *who) {
     if (d.G > 0 && (!a->w_ih || !a->w_hh || !a->b_ih || !a->b_hh)) PN_FAIL(PN_ERR_ARG, "%s: recurrent weights missing", who);
     if (!a->Xh_in && !a->reuse_tables && (!a->X || !a->fc0_w || !a->fc0_b)) PN_FAIL(PN_ERR_ARG, "%s: X / fc0 missing", who);
     if (d.variant != PN_VARIANT_PAGG && (!a->att_w || !a->att_b)) PN_FAIL(PN_ERR_ARG, "%s: attention weights missing", who);
+    if (reinterpret_cast<uintptr_t>(a->out_path_state) % 16 != 0)
+        PN_FAIL(PN_ERR_ARG, "%s: out_path_state must be 16-byte aligned", who);
     return PN_OK;
 }
 
@@ -2140,7 +2175,7 @@ int run_fc2_grad(const Call &c, int b, JoinGuard &joiner, hipStream_t s, const f
                            d.nb == 1 ? 1 : 0);
         PN_CHECK_HIP(hipGetLastError());
     }
-    {
+    if (g_out) {        // (no g_out: only the embedding is differentiated, g_fc2_* keep the backward's zero fill)
         StageTimer tm(c.ctx, ST_FC2_GRAD, s);
         if (a->g_fc2_w && d.det) {
             if (int rc = launch_gemm_det(s, g_out, 1, d.C, nullptr, c.at<float>(c.w.layer1), 1, 2 * H, a->g_fc2_w, 2 * H, d.C,
@@ -2646,7 +2681,7 @@ int pn_pagg_forward(pn_context *ctx, const pn_pagg_args *a, void *stream_) {
             if (int rc = run_plan(c, stream, b)) return rc;
         }
         if (int rc = run_seq_fwd(c, b, save)) return rc;
-        if (int rc = run_pool_fwd(c, b, a->out + (size_t)b * d.Sb * d.C)) return rc;
+        if (int rc = run_pool_fwd(c, b, a->out + (size_t)b * d.Sb * d.C, true)) return rc;
     }
     return PN_OK;
 }
@@ -2668,7 +2703,7 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
     }
     // (S == 0 -- a rank of a sharded batch without masked nodes: its index arrays and g_out are empty tensors, i.e. NULL;
     //  the call still zero-fills every gradient it was given)
-    if (!a->bank_w || !a->fc2_w || (d.S > 0 && (!a->ids || !a->codes || !a->sel || (!fused && !a->g_out))))
+    if (!a->bank_w || !a->fc2_w || (d.S > 0 && (!a->ids || !a->codes || !a->sel || (!fused && !a->g_out && !a->g_embed))))
         PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: null tensor");
     if (d.G > 0 && (!a->w_ih || !a->w_hh)) PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: recurrent weights missing");
     if (!a->Xh_in && (!a->X || !a->fc0_w)) PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: X / fc0 missing");
@@ -2737,7 +2772,7 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
     const bool small_behind_pool = side_ok && wgrad_wanted && ctx != nullptr;
     const bool rerun = fused || d.nb > 1;
     for (int b = 0; b < d.nb; b++) {
-        const float *g_out = fused ? c.at<const float>(c.w.gout) : a->g_out + (size_t)b * d.Sb * d.C;
+        const float *g_out = fused ? c.at<const float>(c.w.gout) : a->g_out ? a->g_out + (size_t)b * d.Sb * d.C : nullptr;
         float *loss_sum = pool_step ? loss : nullptr;
         if (rerun) {
             // pn_pagg_backward with micro-batches: this micro-batch's recurrence again (same seed and positions in the
@@ -2759,7 +2794,8 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
                         return rc;
             }
         }
-        const PoolBwdParams pp = pool_bwd_params(c, b, g_out);
+        PoolBwdParams pp = pool_bwd_params(c, b, g_out);
+        if (a->g_embed) pp.g_embed = a->g_embed + (size_t)b * d.Sb * 2 * H;     // (never with the pooling step: train_step refuses it)
         if (pool_step)
             if (int rc = run_pool_step(c, b, pp, target, grad_scale)) return rc;
         if (!small_behind_pool)
@@ -2794,6 +2830,9 @@ int pn_pagg_backward(pn_context *ctx, const pn_pagg_args *a, void *stream) {
 int pn_pagg_train_step(pn_context *ctx, const pn_pagg_args *a, const int64_t *target, float grad_scale, float *loss,
                        void *stream) {
     if (!a) PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step: null args");
+    if (a->out_embed || a->out_path_weight || a->out_path_state || a->g_embed)
+        PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step: out_embed / out_path_weight / out_path_state / g_embed are for pn_pagg_forward / "
+                            "pn_pagg_backward");
     if (!loss || (a->shape.S > 0 && !target)) PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step: null target / loss");
     if (a->shape.S == 0) {          // nothing to aggregate: zero loss, zero gradients
         PN_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float), (hipStream_t)stream));

@@ -10,6 +10,7 @@ meaning (PathNet_run.py:172): X fp32 [N, F] on the GPU, neis [S, W*L] node ids, 
 All arithmetic runs in hand-written HIP kernels through libpathnet_hip.so; there is no PyTorch
 fallback -- if the library is missing, construction fails.
 """
+import collections
 import ctypes
 import os
 
@@ -198,6 +199,10 @@ class _PaggFunction(torch.autograd.Function):
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
             a.no_save = 0 if cfg.get("grad", True) else 1       # torch.no_grad() forwards skip the saved tensors
             a.reuse_tables = int(cfg.get("reuse_tables") or 0)     # 1: Xh and the dense bank are valid, 2: Xh only
+            enc = cfg.get("encode_out")         # (_PaggEncodeFunction: embedding, path weights, path states or None)
+            if enc is not None:
+                a.out_embed, a.out_path_weight = enc[0].data_ptr(), enc[1].data_ptr()
+                a.out_path_state = enc[2].data_ptr() if enc[2] is not None else None
             if cfg["S"] > 0:
                 _lib.check(lib.pn_pagg_forward(_lib.context(dev), ctypes.byref(a), _lib.stream_ptr(dev)))
         ctx.cfg, ctx.ws = cfg, ws
@@ -208,6 +213,11 @@ class _PaggFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
+        return _PaggFunction._backward(ctx, g_out, None)
+
+    @staticmethod
+    def _backward(ctx, g_out, g_embed):
+        """one pn_pagg_backward for d loss / d logits (g_out) and / or d loss / d embedding (g_embed); either may be None"""
         lib = _lib.load()
         cfg = ctx.cfg
         saved = list(ctx.saved_tensors)
@@ -218,7 +228,8 @@ class _PaggFunction(torch.autograd.Function):
         p = _split_params(params, L)
         dev = X.device
         with torch.cuda.device(dev):
-            g_out = g_out.contiguous().float()
+            g_out = g_out.contiguous().float() if g_out is not None else None
+            g_embed = g_embed.contiguous().float() if g_embed is not None else None
             a = _PaggFunction._args(cfg, X, ids, codes, sel, p)
             grads = {}
             for k in ("fc0_w", "fc0_b", "w_ih", "w_hh", "b_ih", "b_hh", "att_w", "att_b", "fc2_w", "fc2_b"):
@@ -230,7 +241,8 @@ class _PaggFunction(torch.autograd.Function):
             gX = torch.empty_like(X) if ctx.needs_input_grad[1] else None
             a.g_X = gX.data_ptr() if gX is not None else None
             a.workspace, a.workspace_bytes = ctx.ws.data_ptr(), ctx.ws.numel()
-            a.g_out = g_out.data_ptr()
+            a.g_out = g_out.data_ptr() if g_out is not None else None
+            a.g_embed = g_embed.data_ptr() if g_embed is not None else None
             if cfg["S"] > 0:
                 _lib.check(lib.pn_pagg_backward(_lib.context(dev), ctypes.byref(a), _lib.stream_ptr(dev)))
             else:
@@ -242,6 +254,35 @@ class _PaggFunction(torch.autograd.Function):
                                             "fc2_w", "fc2_b"))
         return (None, gX, None, None, None) + head + tuple(g_bank_w[d] for d in range(L)) + tuple(
             g_bank_b[d] for d in range(L))
+
+
+class _PaggEncodeFunction(torch.autograd.Function):
+    """logits, embedding [S, 2H], path weights [S, W] (and final hidden states [S, W, H]) of ONE pn_pagg_forward; the
+    library's optional outputs (pn_pagg_args.out_*).  Logits and embedding are differentiable: one pn_pagg_backward takes
+    the upstream gradients of both (g_out / g_embed, an unused output's being NULL)."""
+
+    @staticmethod
+    def forward(ctx, cfg, X, ids, codes, sel, *params):
+        S, W, H, dev = cfg["S"], cfg["W"], cfg["H"], X.device
+        with torch.cuda.device(dev):
+            emb = torch.empty((S, 2 * H), dtype=torch.float32, device=dev)
+            pw = torch.empty((S, W), dtype=torch.float32, device=dev)
+            ps = torch.empty((S, W, H), dtype=torch.float32, device=dev) if cfg["path_state"] else None
+        cfg["encode_out"] = (emb, pw, ps)
+        try:
+            out = _PaggFunction.forward(ctx, cfg, X, ids, codes, sel, *params)
+        finally:
+            del cfg["encode_out"]       # (ctx keeps cfg: it must not hold the outputs)
+        ctx.mark_non_differentiable(*[t for t in (pw, ps) if t is not None])
+        # (an output the loss does not use gets no zero-filled gradient: pn_pagg_backward is given NULL for it)
+        ctx.set_materialize_grads(False)
+        return (out, emb, pw) if ps is None else (out, emb, pw, ps)
+
+    @staticmethod
+    def backward(ctx, g_out, g_embed, *_unused):
+        if g_out is None and g_embed is None:
+            return (None,) * (5 + len(ctx.present))
+        return _PaggFunction._backward(ctx, g_out, g_embed)
 
 
 class _PaggLossFunction(torch.autograd.Function):
@@ -358,6 +399,9 @@ def _as_index_tensors(neis, layer_type, indices, num_w, walk_len, device, n_node
     ids = ids.reshape(S, num_w, walk_len).to(device, non_blocking=True).contiguous()
     codes = codes.reshape(S, num_w, walk_len).to(device, non_blocking=True).contiguous()
     return ids, codes, sel.to(device, non_blocking=True).contiguous(), S
+
+
+Encoded = collections.namedtuple("Encoded", ("logits", "embedding", "path_weight", "path_state"))
 
 
 class _Aggregator(nn.Module):
@@ -504,6 +548,41 @@ class _Aggregator(nn.Module):
     def forward(self, X, neis, num_w, walk_len, indices, layer_type, indxx=None, reuse_tables=False, group_slice=None):
         return self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=reuse_tables, group_slice=group_slice)
 
+    def encode(self, X, neis, num_w, walk_len, indices, layer_type, indxx=None, *, path_state=False, group_slice=None,
+               reuse_tables=False, seed=None):
+        """The model's internals next to its logits, from the same single forward: ``Encoded(logits, embedding, path_weight,
+        path_state)``, every tensor fp32 on X's device, one row per masked node (of the group_slice, when given).
+
+          logits      [S, C]     bit-identical to forward() on the same inputs, weights and dropout seed.
+          embedding   [S, 2H]    cat(Xh[sel[s]], pooled[s]): the classifier input BEFORE the classifier's dropout
+                                 (layer1 = torch.cat((ego, h_n), dim=1), PathNet_run.py:207 / :275, copy.py:355); in training
+                                 it holds the sequence dropout of the same call.  Differentiable w.r.t. every parameter and X.
+          path_weight [S, W]     the coefficient that multiplies member j's final hidden state in row s's mean: the softmax
+                                 weight (PathNet), 1 + att (PathNet_homo), 1 (PAGG).  Not differentiable.
+          path_state  [S, W, H]  member j's final hidden state h_n; only with path_state=True (it is large), else None.
+                                 Not differentiable.
+
+        Member order is the reference's: for PathNet_homo / PAGG member j of row s is path j of masked node s.  For PathNet
+        it is sequence slot q = j * S + s of the reference's scrambled LSTM batch (S: masked nodes of the whole batch; the
+        [W, S] re-view of PathNet_run.py:196-197): its steps come from other masked nodes' paths, and that is what the
+        reference pools for node s (oracle/pagg_oracle.py, plan()).
+
+        A loss over any mix of logits and embedding runs ONE backward of the library.  group_slice, reuse_tables and the
+        dropout handling are forward()'s; seed (training only) fixes the dropout seed instead of drawing it from torch's
+        generator.  Not covered: gradients through path_weight / path_state, the node-sharded and replicated aggregators
+        of pathnet_amd.dist, and the fused training step (forward_loss(fused=True))."""
+        res = self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=reuse_tables, group_slice=group_slice,
+                        seed=seed, _encode=bool(path_state))
+        logits, emb, pw = res[:3]
+        ps = res[3] if path_state else None
+        H = self.hidden_size
+        Hk = emb.shape[1] // 2
+        if Hk != H:         # the kernels ran at a hidden size padded to a multiple of 32: the padded units are zeros
+            S = emb.shape[0]
+            emb = emb.view(S, 2, Hk)[:, :, :H].reshape(S, 2 * H)      # (its backward zero-pads the gradient going in)
+            ps = ps[:, :, :H].contiguous() if ps is not None else None
+        return Encoded(logits, emb, pw, ps)
+
     def paths_stream(self):
         """The torch stream on which this module's NEXT call will read its path arrays (neis / layer_type), judged by the
         shape of its last call on the current stream (pn_pagg_paths_stream): the library's second stream when the call forks
@@ -566,7 +645,7 @@ class _Aggregator(nn.Module):
             self._range_pending = (rec, ev)
 
     def _run(self, X, neis, num_w, walk_len, indices, layer_type, reuse_tables=False, group_slice=None, target=None,
-             grad_scale=None, fused=None, batch_position=None, seed=None, _math=None):
+             grad_scale=None, fused=None, batch_position=None, seed=None, _math=None, _encode=None):
         """reuse_tables (extension, inference only): X and the weights are those of the previous no-grad forward of this
         module -- the validation and the test forward of an epoch (PathNet_run.py:362, :378) -- so the projected
         feature matrix and the distance bank still sitting in the module's workspace are used again.
@@ -678,6 +757,9 @@ class _Aggregator(nn.Module):
                 if grad_scale is not None:
                     loss = loss * (float(grad_scale) * max(S, 1))
                 res = (loss, out)
+        elif _encode is not None:       # (encode(): _encode = whether the paths' final hidden states are wanted)
+            cfg["path_state"] = bool(_encode)
+            res = _PaggEncodeFunction.apply(cfg, X, ids, codes, sel, *params)
         else:
             res = _PaggFunction.apply(cfg, X, ids, codes, sel, *params)
         if guard and S > 0:
@@ -689,7 +771,7 @@ class _Aggregator(nn.Module):
                     return self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=False, group_slice=group_slice,
                                      target=target, grad_scale=grad_scale, fused=fused, batch_position=batch_position,
                                      seed=cfg["seed"] if (p > 0 and self.step_state is None) else seed,
-                                     _math=_lib.SEQ_MATH_BF16X3)
+                                     _math=_lib.SEQ_MATH_BF16X3, _encode=_encode)
         return res
 
 
