@@ -443,7 +443,11 @@ int pn_pagg_range_offset(const pn_pagg_shape *shape, int64_t *offset);
  * by one), else `stream` itself.  A producer of the paths enqueued THERE -- the sampler of a training loop: pn_sample_paths with
  * *out as its stream, right before the call -- is ordered before its readers and behind those of the previous call without an
  * event on `stream`, and runs under whatever that stream still holds of the previous step (the recurrent weight gradient):
- * the walk leaves the step's critical path.  Ask before every call (the answer follows pn_profile_configure). */
+ * the walk leaves the step's critical path.  Ask before every call (the answer follows pn_profile_configure).  A call that
+ * reads the paths on `stream` before it forks (the touched-row marks of a compact shape) first waits for the work already on
+ * the second stream, so a producer placed there by the answer for another shape is still ordered before it.  A sampler driven
+ * by a pn_step_state reads epoch and seed from device memory: it stays on the stream that advances the state
+ * (pn_step_state_advance, pn_adam_step_advance), not on *out. */
 int pn_pagg_paths_stream(pn_context *ctx, const pn_pagg_shape *shape, void *stream, void **out);
 /* out = forward(...) (and the optional out_embed / out_path_weight / out_path_state).  Leaves what backward needs in the
  * workspace. */

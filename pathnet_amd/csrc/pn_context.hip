@@ -149,6 +149,16 @@ int context_join(pn_context *ctx, void *stream) {
     PN_CHECK_HIP(hipStreamWaitEvent((hipStream_t)stream, ctx->join, 0));
     return PN_OK;
 }
+int context_wait_side(pn_context *ctx, void *stream) {
+    if (!ctx || !ctx->side || (hipStream_t)stream == ctx->side) return PN_OK;
+    // (a captured stream cannot wait for work outside its graph: a walk captured on the second stream has joined the capture)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone, ss = hipStreamCaptureStatusNone;
+    PN_CHECK_HIP(hipStreamIsCapturing((hipStream_t)stream, &cs));
+    PN_CHECK_HIP(hipStreamIsCapturing(ctx->side, &ss));
+    if ((cs == hipStreamCaptureStatusActive) != (ss == hipStreamCaptureStatusActive)) return PN_OK;
+    if (int rc = context_record_join(ctx)) return rc;
+    return context_join(ctx, stream);
+}
 
 StageTimer::StageTimer(pn_context *ctx_, int stage, void *stream_) : ctx(ctx_), slot(-1), stream(stream_) {
     if (!ctx || ctx->prof_mode == 0 || (ctx->prof_mode == 2 && stage != ctx->prof_stage)) return;

@@ -75,6 +75,9 @@ void *context_side_stream(pn_context *ctx);      // the second stream itself (or
 // records the join event on the second stream; context_join makes `stream` wait for it
 int context_record_join(pn_context *ctx);
 int context_join(pn_context *ctx, void *stream);
+// `stream` waits for everything enqueued so far on the second stream (a producer the caller placed there by
+// pn_pagg_paths_stream) -- skipped when only one of the two streams is being captured into a graph
+int context_wait_side(pn_context *ctx, void *stream);
 // hipFuncSetAttribute(kernel, MaxDynamicSharedMemorySize, bytes), remembered per context (= per device) so that the
 // steady state issues no runtime call besides the launches (a captured step must not)
 int ensure_dynamic_lds(pn_context *ctx, const void *kernel, int bytes);

@@ -1959,6 +1959,9 @@ int run_tables(const Call &c, JoinGuard &joiner, ZeroFill *zero_fill = nullptr) 
     // the index plan (of the first micro-batch) and the weight packing do not depend on fc0 / bank: second stream,
     // joined before the recurrence
     if (d.compact) {        // the compact rows first: the index plan and the bank both read them
+        // (they read ids / codes on `stream`, ahead of the fork: a walk enqueued on the second stream -- where
+        //  pn_pagg_paths_stream places it -- is waited for first; the dense call reads them behind the fork only)
+        if (int rc = context_wait_side(ctx, stream)) return rc;
         StageTimer tm(ctx, ST_PLAN_PACK, stream);
         if (int rc = run_compact_rows(c, stream)) return rc;
     }

@@ -589,10 +589,14 @@ class _Aggregator(nn.Module):
         the index plan off, else the current stream.  A training loop that enqueues its sampler there
         (``with torch.cuda.stream(model.paths_stream()): sampler.sample(..., out=bufs)``) takes the walk off the step's
         critical path -- it runs under the tail of the previous step -- without an event on the main stream.  The path
-        buffers must then be written by that stream only."""
+        buffers must then be written by that stream only.  With ``step_state`` set the walk stays on the current stream:
+        a sampler driven by the step state reads its epoch and seed from device memory, advanced on this stream."""
         cur = torch.cuda.current_stream()
         last = getattr(self, "_last_shape", None)
-        if last is None:
+        if last is None or self.step_state is not None:
+            prev = getattr(self, "_paths_stream_prev", None)
+            if prev is not None and prev.cuda_stream != cur.cuda_stream:
+                cur.wait_stream(prev)           # (behind the walk handed out last time)
             self._paths_stream_prev = cur
             return cur
         shape, dev = last
