@@ -245,6 +245,41 @@ int pn_sample_paths(pn_context *ctx, const pn_sampler_tables *tables, int32_t W,
                     const pn_step_state *step_state /* dev or NULL: PN_DRAW_PHILOX only; replaces seed / epoch_begin */,
                     const int32_t *node_list /* dev [node_count] or NULL */, void *stream);
 
+/* ---- distance codes and walk checks for paths that did not come from pn_sample_paths (pn_codes.hip) ----------------
+ * Paths of another sampler, of an ids-only file, or sampled before edges were hidden or added carry node ids only;
+ * this annotates them from the walker's hop source and counts what is wrong with them.  Added without an ABI bump:
+ * symbols only, no existing struct changed.
+ *
+ * Only the hop source of `tables` is read: dis, or (dis == NULL) the four CSR arrays; off / triples / node_ref may be
+ * NULL.  The source of row s is sources[s] when given, else ids[s, 0, 0].
+ *   codes[s, w, t] = min(hops(source -> ids[s, w, t]), L-1) over the directed edges the tables were built from.  A node
+ *     that is further away or unreachable gets L-1 and counts in `far`; an id outside [0, n) gets L-1, counts in
+ *     `out_of_range` and never indexes a table.  A source outside [0, n) (possible only through `sources`; it is not
+ *     an element of ids and is not counted as one) leaves every node of its row `far`.
+ *   non_edges counts the steps t -> t+1 whose two nodes are in range and more than one hop apart; staying in place is
+ *     accepted, because the dense table cannot tell a self loop from identity.
+ * Both modes give the same numbers, and for paths pn_sample_paths produced from the same tables the codes are the
+ * walker's, bit for bit.  A dense table must have been built with seq_len >= L (this cannot be seen from the struct:
+ * a table built for shorter paths reports nodes beyond its own radius as far); on-the-fly keeps the walker's limits
+ * (n < 2^28, L <= 8, and fewer than 2^32 entries in each CSR list: positions in them are kept as 32-bit words, which
+ * the call cannot check) and is exact for every source, hubs whose out-ball does not fit the LDS table included.  Its cost
+ * per node grows with the number of in-neighbour chains of length L-1-(ball radius): see pn_codes.hip.
+ * Asynchronous: nothing is read back.  `report` (may be NULL) is zeroed by the call, first_bad set to -1.  The workspace
+ * (its size from the function below, which needs no device) receives the counters of a call without a report; a missing
+ * or short one fails with PN_ERR_ARG. */
+typedef struct pn_path_report {   /* device memory, caller-owned, zeroed by the call */
+    int64_t out_of_range;         /* ids < 0 or >= n */
+    int64_t non_edges;            /* consecutive (ids[t], ids[t+1]) with hops > 1 */
+    int64_t far;                  /* nodes more than L-1 hops from the row's source */
+    int64_t first_bad;            /* flat index of the first out_of_range id, or -1 */
+} pn_path_report;
+
+int pn_path_codes_workspace_bytes(const pn_sampler_tables *tables, int32_t W, int32_t L, int32_t rows, int64_t *bytes);
+int pn_path_codes(pn_context *ctx, const pn_sampler_tables *tables, int32_t W, int32_t L, int32_t rows,
+                  const int32_t *ids /* dev [rows, W, L] */, const int32_t *sources /* dev [rows] or NULL */,
+                  uint8_t *codes /* dev [rows, W, L] */, pn_path_report *report /* dev or NULL */,
+                  void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ================================================================================================
  * Path file.  The on-disk interface between sampler and trainer: one line per path,
  * "[v0, v1, ..., v_{L-1}, d0, ..., d_{L-1}]\n"  (writer gen_merw.cpp:189-206; reader

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "pn_internal.h"
+#include "pn_otf.h"
 
 namespace {
 
@@ -297,22 +298,7 @@ __global__ __launch_bounds__(kWalkThreads) void merw_walk_kernel(WalkParams p) {
 #ifndef PN_OTF_ABL
 #define PN_OTF_ABL 0     // tuning builds only: 1 = no Bloom filter (round 3's search), 2 = no backward search at all (wrong codes)
 #endif
-constexpr int kOtfWaves = 2;                  // source nodes per workgroup (16 KB of LDS each: five workgroups per CU)
-constexpr int kOtfCap = 2048;                 // hash slots per wave (8 KB)
-constexpr uint32_t kOtfEmpty = 0xFFFFFFFFu;
-constexpr int kOtfMaxDepth = 8;
-constexpr int kOtfBloomWords = 1024;          // 32 Kbit per wave
-__device__ __forceinline__ void otf_bloom_bits(int32_t node, uint32_t &b0, uint32_t &b1, uint32_t &b2) {
-    b0 = ((uint32_t)node * 0x9E3779B1u) >> 17;         // 15 bits each
-    b1 = ((uint32_t)node * 0x85EBCA6Bu + 0x27D4EB2Fu) >> 17;
-    b2 = ((uint32_t)node * 0xC2B2AE35u + 0x165667B1u) >> 17;
-}
-__device__ __forceinline__ bool otf_bloom_maybe(const uint32_t *bloom, int32_t node) {
-    uint32_t b0, b1, b2;
-    otf_bloom_bits(node, b0, b1, b2);
-    return ((bloom[b0 >> 5] >> (b0 & 31)) & (bloom[b1 >> 5] >> (b1 & 31)) & (bloom[b2 >> 5] >> (b2 & 31)) & 1u) != 0;
-}
-
+// (table, Bloom filter and ball build: pn_otf.h, shared with the path annotator of pn_codes.hip)
 struct OtfParams {
     WalkParams w;
     const int64_t *adj_off;
@@ -320,33 +306,6 @@ struct OtfParams {
     const int64_t *radj_off;
     const int32_t *radj;
 };
-
-__device__ __forceinline__ uint32_t otf_hash(uint32_t x) {
-    x *= 0x9E3779B1u;
-    return (x ^ (x >> 15)) & (kOtfCap - 1);
-}
-// returns true if (node, d) was newly inserted
-__device__ __forceinline__ bool otf_insert(uint32_t *tab, int32_t node, int d) {
-    uint32_t h = otf_hash((uint32_t)node);
-    const uint32_t packed = ((uint32_t)node << 3) | (uint32_t)d;
-    for (int probe = 0; probe < kOtfCap; probe++) {
-        const uint32_t old = atomicCAS(&tab[h], kOtfEmpty, packed);
-        if (old == kOtfEmpty) return true;
-        if ((old >> 3) == (uint32_t)node) return false;     // already there with a level <= d
-        h = (h + 1) & (kOtfCap - 1);
-    }
-    return false;
-}
-__device__ __forceinline__ int otf_lookup(const uint32_t *tab, int32_t node) {
-    uint32_t h = otf_hash((uint32_t)node);
-    for (int probe = 0; probe < kOtfCap; probe++) {
-        const uint32_t v = tab[h];
-        if (v == kOtfEmpty) return -1;
-        if ((v >> 3) == (uint32_t)node) return (int)(v & 7u);
-        h = (h + 1) & (kOtfCap - 1);
-    }
-    return -1;
-}
 
 template <int DRAW>
 __global__ __launch_bounds__(kOtfWaves * 64) void merw_walk_otf_kernel(OtfParams op) {
@@ -365,79 +324,14 @@ __global__ __launch_bounds__(kOtfWaves * 64) void merw_walk_otf_kernel(OtfParams
     uint32_t *tab = s_tab[wave];
 
     // ---- out-ball of st, radius rf (largest of 2, 1, 0 that keeps the table at most half full) ----------
-    int rf = 2;
-    for (;; rf--) {
-        for (int i = lane; i < kOtfCap; i += 64) tab[i] = kOtfEmpty;
-        if (lane == 0) s_cnt[wave] = 0;
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
-            otf_insert(tab, st, 0);
-            s_cnt[wave] = 1;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int64_t b0 = op.adj_off[st], e0 = op.adj_off[st + 1];
-        bool overflow = false;
-        if (rf >= 1) {
-            if (e0 - b0 > kOtfCap / 2) overflow = true;
-            if (!overflow) {
-                for (int64_t j = b0 + lane; j < e0; j += 64)
-                    if (otf_insert(tab, op.adj[j], 1)) atomicAdd(&s_cnt[wave], 1);
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-        if (rf >= 2 && !overflow) {
-            for (int64_t j = b0; j < e0 && !overflow; j++) {
-                const int32_t a = op.adj[j];
-                const int64_t b1 = op.adj_off[a], e1 = op.adj_off[a + 1];
-                if (s_cnt[wave] + (e1 - b1) > kOtfCap / 2) {    // could exceed half load: give up this radius
-                    overflow = true;
-                    break;
-                }
-                for (int64_t k = b1 + lane; k < e1; k += 64)
-                    if (otf_insert(tab, op.adj[k], 2)) atomicAdd(&s_cnt[wave], 1);
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-        if (!overflow || rf == 0) break;
-    }
-    __builtin_amdgcn_wave_barrier();
+    const int rf = otf_build_ball(tab, &s_cnt[wave], lane, st, op.adj_off, op.adj);
 
     // ---- out-neighbours of the ball's level-2 nodes -> Bloom filter (only when a search can happen: L >= rf + 3) ----------
     uint32_t *bloom = s_bloom[wave];
     bool bloom_ok = false;
     if (rf == 2 && p.L >= 5 && PN_OTF_ABL != 1) {
-        uint32_t *list = &s_stack[wave][0][0][0];             // 2 * kOtfMaxDepth * 64 = 1024 entries: the table is at most half full
-        for (int i = lane; i < kOtfBloomWords; i += 64) bloom[i] = 0u;
-        if (lane == 0) s_cnt[wave] = 0;
-        __builtin_amdgcn_wave_barrier();
-        for (int i = lane; i < kOtfCap; i += 64) {
-            const uint32_t v = tab[i];
-            if (v != kOtfEmpty && (v & 7u) == 2u) list[atomicAdd(&s_cnt[wave], 1)] = v >> 3;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int n2 = s_cnt[wave];
-        // a lane per level-2 node: its out-neighbours, three bits each; the list bounds of a lane's NEXT node are fetched
-        // while it walks the current one
-        int64_t kb_n = 0, ke_n = 0;
-        if (lane < n2) kb_n = op.adj_off[(int32_t)list[lane]], ke_n = op.adj_off[(int32_t)list[lane] + 1];
-        for (int i = lane; i < n2; i += 64) {
-            const int64_t kb = kb_n, ke = ke_n;
-            if (i + 64 < n2) kb_n = op.adj_off[(int32_t)list[i + 64]], ke_n = op.adj_off[(int32_t)list[i + 64] + 1];
-            for (int64_t k = kb; k < ke; k += 4) {       // four loads in flight (the tail repeats the last entry)
-                int32_t nb[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) nb[u] = op.adj[min(k + u, ke - 1)];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    uint32_t b0, b1, b2;
-                    otf_bloom_bits(nb[u], b0, b1, b2);
-                    atomicOr(&bloom[b0 >> 5], 1u << (b0 & 31));
-                    atomicOr(&bloom[b1 >> 5], 1u << (b1 & 31));
-                    atomicOr(&bloom[b2 >> 5], 1u << (b2 & 31));
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
+        // (the list of level-2 nodes: 2 * kOtfMaxDepth * 64 = 1024 entries of the stack, the table is at most half full)
+        otf_build_bloom(bloom, tab, &s_cnt[wave], &s_stack[wave][0][0][0], lane, 2u, op.adj_off, op.adj);
         bloom_ok = true;
     }
 

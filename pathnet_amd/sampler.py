@@ -7,6 +7,7 @@ Mirrors /root/reference/preprocess/gen_merw.cpp: ``main`` (:125-213) becomes
 ``../edge_input/<name>.in`` and writes ``./<name>_<W>_<L>_merw.txt`` (or one file per epoch with
 ``--per-epoch``, gen_epoch_merw.cpp:166-178), 1000 epochs.
 """
+import collections
 import ctypes
 import sys
 import time
@@ -193,10 +194,124 @@ def glibc_draws(seed, first, count):
     return out
 
 
-class MerwSampler:
-    """Device-resident sampler tables for one graph and one path length."""
+PathReport = collections.namedtuple("PathReport", ("out_of_range", "non_edges", "far", "first_bad"))
+
+
+class _HopSource:
+    """What the walker reads hop counts from -- the dense dis[n][n] table or the two CSR lists, on self.device -- and
+    annotate(), which reads nothing else.  Needs self.n, self.L, self.device and the five d_* tensors (None when unused)."""
 
     DENSE_LIMIT_BYTES = 8 << 30     # hops="auto": dense n*n table up to 8 GB (n <= 92681), else on the fly
+    # pn_path_codes' workspace.  A call without a report writes its counters there and nobody reads them, so calls on
+    # several streams may share it; whoever starts reading counters from it needs one per stream.
+    _codes_ws = None
+
+    def annotate(self, ids, sources=None, *, report=False, check=False, out=None):
+        """Distance codes for paths that did not come from sample() (pn_path_codes): another sampler's, an ids-only
+        file's, or paths sampled before edges were hidden or added.
+        ids: [S, W, L] or [E, S, W, L]; an int32 tensor on the device is read in place, anything else torch.as_tensor
+        takes is narrowed to int32 and uploaded.  L <= the seq_len the tables were built for.
+        sources: the node every row's hops are counted from, one per [W, L] block (shape ids.shape[:-2]); default: the
+        row's first node ids[..., 0, 0].
+        -> codes, a uint8 device tensor shaped like ids: min(hops(source -> node), L-1) over the directed edges of the
+        graph; nodes further away, unreachable or outside [0, n) get L-1.
+        report=True: -> (codes, PathReport(out_of_range, non_edges, far, first_bad)) -- ids outside the graph, steps that
+        are no edge (staying in place is accepted), nodes beyond L-1 hops, flat index of the first id outside the graph
+        or -1; costs one read-back.  check=True: IndexError naming first_bad when an id lies outside the graph.
+        Without either flag nothing is read back: the call is enqueued on the current stream like sample().
+        On the fly (hops="otf") a node that is not within two hops of its source is searched for over chains of
+        in-neighbours up to L-1 long, without a visited set: many far or random targets in a graph with in-degrees of 16
+        and more, at L near 8, make one launch long.  The dense table has no such case."""
+        dev = self.device
+        t = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(ids)
+        if t.dim() not in (3, 4):
+            raise ValueError("annotate: ids of shape [S, W, L] or [E, S, W, L] expected, got %s" % (tuple(t.shape),))
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise TypeError("annotate: integer node ids expected, got %s" % t.dtype)
+        if t.dtype != torch.int32:       # (a wider id cannot be a node: it stays out of range after the narrowing)
+            t = t.clamp(-1, 2 ** 31 - 1).to(torch.int32)
+        t = t.to(dev).contiguous()
+        W, L = int(t.shape[-2]), int(t.shape[-1])
+        rows = t.numel() // max(W * L, 1)
+        if L < 1 or W < 1 or L > self.L:
+            raise ValueError("annotate: paths of %d x %d nodes; the hop source was built for path lengths up to %d"
+                             % (W, L, self.L))
+        src = None
+        if sources is not None:
+            src = sources if isinstance(sources, torch.Tensor) else torch.as_tensor(sources)
+            if src.numel() != rows:
+                raise ValueError("annotate: %d sources for %d rows" % (src.numel(), rows))
+            if src.dtype != torch.int32:
+                src = src.clamp(-1, 2 ** 31 - 1).to(torch.int32)
+            src = src.to(dev).contiguous()
+        if out is None:
+            codes = torch.empty(t.shape, dtype=torch.uint8, device=t.device)
+        else:
+            codes = out
+            if (tuple(codes.shape) != tuple(t.shape) or codes.dtype != torch.uint8 or not codes.is_contiguous() or
+                    codes.device != t.device):
+                raise ValueError("annotate(out=...): contiguous uint8 tensor of shape %s on %s expected, got %s %s on %s"
+                                 % (tuple(t.shape), t.device, codes.dtype, tuple(codes.shape), codes.device))
+        lib = _lib.load()
+        dp = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
+        tb = _lib.SamplerTables(self.n, 0, None, None, dp(self.d_dis), dp(self.d_adj_off), dp(self.d_adj),
+                                dp(self.d_radj_off), dp(self.d_radj), 0, None)
+        need = ctypes.c_int64(0)
+        _lib.check(lib.pn_path_codes_workspace_bytes(ctypes.byref(tb), W, L, rows, ctypes.byref(need)))
+        with torch.cuda.device(t.device):
+            if self._codes_ws is None or self._codes_ws.numel() < need.value:
+                self._codes_ws = torch.empty(max(need.value, 1), dtype=torch.uint8, device=t.device)
+            rep = torch.empty(4, dtype=torch.int64, device=t.device) if (report or check) else None
+            _lib.check(lib.pn_path_codes(_lib.context(t.device), ctypes.byref(tb), W, L, rows, _lib.ptr(t), _lib.ptr(src),
+                                         _lib.ptr(codes), _lib.ptr(rep), _lib.ptr(self._codes_ws),
+                                         self._codes_ws.numel(), _lib.stream_ptr(t.device)))
+        if rep is None:
+            return codes
+        rep = PathReport(*rep.tolist())
+        if check and rep.out_of_range > 0:
+            raise IndexError("annotate: %d ids lie outside [0, %d); the first is element %d of the flattened ids"
+                             % (rep.out_of_range, self.n, rep.first_bad))
+        return (codes, rep) if report else codes
+
+
+class PathAnnotator(_HopSource):
+    """The hop source of a graph without a sampler around it: annotate() for callers that bring their own paths and
+    have no transition probabilities.  (u[i] -> v[i]) are the directed edges; hops / build as for MerwSampler."""
+
+    def __init__(self, n, u, v, seq_len, device="cuda", hops="auto", build="host"):
+        if build not in ("host", "device"):
+            raise ValueError("build must be 'host' or 'device'")
+        if hops not in ("dense", "otf", "auto"):
+            raise ValueError("hops must be 'dense', 'otf' or 'auto'")
+        self.n, self.L = int(n), int(seq_len)
+        self.device = dev = _cuda_device(device)
+        if hops == "auto":
+            hops = "dense" if self.n * self.n <= self.DENSE_LIMIT_BYTES else "otf"
+        self.hops = hops
+        if hops == "otf" and seq_len > 8:
+            raise ValueError("on-the-fly hop codes support path lengths up to 8")
+        self.d_dis = self.d_adj_off = self.d_adj = self.d_radj_off = self.d_radj = None
+        if build == "device":
+            with torch.cuda.device(dev):
+                u, v = _on_device(u, torch.int32, dev), _on_device(v, torch.int32, dev)
+                ws = tables_workspace(n, u.numel(), dev)
+                self.d_adj_off, self.d_adj = csr_build_device(n, u, v, False, dev, workspace=ws)
+                if hops == "dense":
+                    self.d_dis = hops_dense_device(n, self.d_adj_off, self.d_adj, seq_len)
+                    self.d_adj_off = self.d_adj = None
+                else:
+                    self.d_radj_off, self.d_radj = csr_build_device(n, u, v, True, dev, workspace=ws)
+        elif hops == "dense":
+            self.d_dis = torch.from_numpy(hops_dense(n, u, v, seq_len)).to(dev)
+        else:
+            ao, aa = csr_build(n, u, v, reverse=False)
+            ro, ra = csr_build(n, u, v, reverse=True)
+            self.d_adj_off, self.d_adj = torch.from_numpy(ao).to(dev), torch.from_numpy(aa).to(dev)
+            self.d_radj_off, self.d_radj = torch.from_numpy(ro).to(dev), torch.from_numpy(ra).to(dev)
+
+
+class MerwSampler(_HopSource):
+    """Device-resident sampler tables for one graph and one path length."""
 
     draws_per_step = 2              # the alias roll: slot draw + probability draw (gen_merw.cpp:81-91)
 
