@@ -214,59 +214,34 @@ class HipOps:
                                              ws.data_ptr(), ws.numel() * 4, _lib.stream_ptr(dev)))
         return out
 
-    def _args(self, cfg, Xh, ids, codes, sel, p):
-        a = _lib.PaggArgs()
-        a.shape = M._cfg_shape(cfg)
-        a.Xh_in = Xh.data_ptr()
-        a.ids, a.codes, a.sel = ids.data_ptr(), codes.data_ptr(), sel.data_ptr()
-        a.index_rows_local = 1 if cfg.get("index_rows_local") else 0
-        for k in M._HEAD_PARAMS[2:]:
-            setattr(a, k, p[k].data_ptr() if p.get(k) is not None else None)
-        a.bank_w, a.bank_b = cfg["bank_w"].data_ptr(), cfg["bank_b"].data_ptr()
-        a.p_seq, a.p_cls, a.seed = cfg["p_seq"], cfg["p_cls"], cfg["seed"]
-        ms, mc = cfg.get("mask_seq"), cfg.get("mask_cls")
-        a.mask_seq = ms.data_ptr() if ms is not None else None
-        a.mask_cls = mc.data_ptr() if mc is not None else None
-        return a
-
-    def forward(self, cfg, Xh, ids, codes, sel, p, ready=None):
-        """ready: torch.cuda.Event recorded after the all-gather of Xh on the communication stream, or None (Xh is complete
-        in stream order)"""
+    def forward(self, call, Xh, ids, codes, sel, p, ready=None):
+        """call: modules.PaggCall.  ready: torch.cuda.Event recorded after the all-gather of Xh on the communication stream,
+        or None (Xh is complete in stream order)"""
         lib = _lib.load()
         dev = Xh.device
         with torch.cuda.device(dev):
-            out = torch.empty((cfg["S"], cfg["C"]), dtype=torch.float32, device=dev)
-            ws = torch.empty(max(M._cfg_workspace_bytes(cfg), 1), dtype=torch.uint8, device=dev)
-            a = self._args(cfg, Xh, ids, codes, sel, p)
+            a, out, ws = M._begin(call, ids, codes, sel, p, Xh=Xh)
             a.Xh_ready = ready.cuda_event if ready is not None else None
-            a.out = out.data_ptr()
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-            if cfg["S"] > 0:
+            if call.S > 0:
                 _lib.check(lib.pn_pagg_forward(_lib.context(dev), ctypes.byref(a), _lib.stream_ptr(dev)))
-        return out, (cfg, Xh, ids, codes, sel, p, ws)
+        return out, (call, Xh, ids, codes, sel, p, ws)
 
     def backward(self, state, g_out, ready=None):
         """-> (g_Xh [N,H], grads): grads maps the head parameter names (without fc0) to tensors and
         "bank_w"/"bank_b" to the stacked [L,H,H] / [L,H] gradients.  ready: a torch.cuda.Event the library records as soon
         as g_Xh is complete (the weight gradients follow it), or None."""
         lib = _lib.load()
-        cfg, Xh, ids, codes, sel, p, ws = state
+        call, Xh, ids, codes, sel, p, ws = state
         dev = Xh.device
         with torch.cuda.device(dev):
-            a = self._args(cfg, Xh, ids, codes, sel, p)
+            a = call.args(ids, codes, sel, p, Xh=Xh)
             a.g_Xh_ready = ready.cuda_event if ready is not None else None
             a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
             g_out = g_out.contiguous().float()
             a.g_out = g_out.data_ptr()
             g_Xh = torch.empty_like(Xh)
             a.g_Xh = g_Xh.data_ptr()
-            grads = {"bank_w": torch.empty_like(cfg["bank_w"]), "bank_b": torch.empty_like(cfg["bank_b"])}
-            a.g_bank_w, a.g_bank_b = grads["bank_w"].data_ptr(), grads["bank_b"].data_ptr()
-            for k in M._HEAD_PARAMS[2:]:
-                if p.get(k) is None:
-                    continue
-                grads[k] = torch.empty_like(p[k])
-                setattr(a, "g_" + k, grads[k].data_ptr())
+            grads = call.grad_buffers(a, p)[0]
             # (S == 0: the library zero-fills every gradient it was given)
             _lib.check(lib.pn_pagg_backward(_lib.context(dev), ctypes.byref(a), _lib.stream_ptr(dev)))
         return g_Xh, grads
@@ -312,17 +287,17 @@ class _SparsePlan:
 
 class _ShardedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, runner, cfg, X_loc, ids, codes, sel, *params):
-        p = M._split_params(params, cfg["L"])
+    def forward(ctx, runner, call, X_loc, ids, codes, sel, *params):
+        p = M._split_params(params, call.L)
         ops, comm = runner.ops, runner.comm
-        plan = cfg.get("sparse_plan")
+        plan = call.sparse_plan
         pre = runner._take_prefetched(X_loc, p["fc0_w"], p["fc0_b"]) if plan is None else None
         if pre is not None:             # begin_step projected and gathered already, on the communication stream
             Xh_loc, Xh, ready = pre
         elif plan is not None:
-            Xh_loc, Xh, ready = runner._project_and_fetch(cfg["variant"], X_loc, p["fc0_w"], p["fc0_b"], plan)
+            Xh_loc, Xh, ready = runner._project_and_fetch(call.variant, X_loc, p["fc0_w"], p["fc0_b"], plan)
         else:
-            Xh_loc, Xh, ready = runner._project_and_gather(cfg["variant"], X_loc, p["fc0_w"], p["fc0_b"])
+            Xh_loc, Xh, ready = runner._project_and_gather(call.variant, X_loc, p["fc0_w"], p["fc0_b"])
         if ready is not None and comm.measure_exposed:
             need = torch.cuda.Event(enable_timing=True)
             need.record()
@@ -330,19 +305,18 @@ class _ShardedFn(torch.autograd.Function):
         if ready is not None and not isinstance(ops, HipOps):      # a checker backend: plain stream order
             torch.cuda.current_stream(X_loc.device).wait_event(ready)
             ready = None
-        out, state = ops.forward(cfg, Xh, ids, codes, sel, p, ready) if isinstance(ops, HipOps) else ops.forward(cfg, Xh, ids, codes, sel, p)
-        ctx.runner, ctx.state, ctx.cfg = runner, state, cfg
+        out, state = ops.forward(call, Xh, ids, codes, sel, p, ready) if isinstance(ops, HipOps) else ops.forward(call, Xh, ids, codes, sel, p)
+        ctx.runner, ctx.state, ctx.call = runner, state, call
         ctx.save_for_backward(X_loc, Xh_loc, p["fc0_w"])
-        ctx.present = [t is not None for t in params]
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        runner, cfg = ctx.runner, ctx.cfg
+        runner, call = ctx.runner, ctx.call
         ops, comm = runner.ops, runner.comm
         X_loc, Xh_loc, fc0_w = ctx.saved_tensors
         dev = X_loc.device
-        plan = cfg.get("sparse_plan")
+        plan = call.sparse_plan
         rows = Xh_loc.shape[0]
 
         def to_owner(g_Xh):
@@ -357,8 +331,8 @@ class _ShardedFn(torch.autograd.Function):
         if not overlap:
             g_Xh, grads = ops.backward(ctx.state, g_out)
             g_loc = to_owner(g_Xh)
-            grads["fc0_w"], grads["fc0_b"] = ops.linear_backward(cfg["variant"], g_loc, Xh_loc, X_loc, fc0_w,
-                                                                 deterministic=cfg.get("deterministic", False))
+            grads["fc0_w"], grads["fc0_b"] = ops.linear_backward(call.variant, g_loc, Xh_loc, X_loc, fc0_w,
+                                                                 deterministic=call.deterministic)
         else:
             # the library records `ready` as soon as d Xh is complete; its weight-gradient GEMMs then run under the
             # reduce-scatter (or the sparse return) and fc0's backward, which follow on the communication stream
@@ -369,8 +343,8 @@ class _ShardedFn(torch.autograd.Function):
             with torch.cuda.stream(cst):
                 cst.wait_event(ready)
                 g_loc = to_owner(g_Xh)
-                grads["fc0_w"], grads["fc0_b"] = ops.linear_backward(cfg["variant"], g_loc, Xh_loc, X_loc, fc0_w,
-                                                                     deterministic=cfg.get("deterministic", False))
+                grads["fc0_w"], grads["fc0_b"] = ops.linear_backward(call.variant, g_loc, Xh_loc, X_loc, fc0_w,
+                                                                     deterministic=call.deterministic)
                 done = torch.cuda.Event(enable_timing=comm.measure_exposed)
                 done.record(cst)
             if comm.measure_exposed:        # the compute stream needs fc0's gradients when the library's own work is over
@@ -380,10 +354,7 @@ class _ShardedFn(torch.autograd.Function):
             cur.wait_event(done)
             for t in (g_loc, grads["fc0_w"], grads["fc0_b"]):
                 t.record_stream(cur)
-        L = cfg["L"]
-        head = tuple(grads.get(k) if pres else None for k, pres in zip(M._HEAD_PARAMS, ctx.present[:10]))
-        return (None, None, None, None, None, None) + head + tuple(grads["bank_w"][d] for d in range(L)) + tuple(
-            grads["bank_b"][d] for d in range(L))
+        return (None, None, None, None, None, None) + M._grad_tuple(grads, call.L)
 
 
 class ShardedAggregator:
@@ -395,7 +366,7 @@ class ShardedAggregator:
     """
 
     def __init__(self, module, n_total, row_begin, row_count, group=None, ops=None, comm=None, dropout_seed=0,
-                 exchange="auto"):
+                 exchange="auto", check_block=True):
         self.module, self.n_total, self.row_begin, self.row_count = module, int(n_total), int(row_begin), int(row_count)
         self.comm = comm if comm is not None else Comm(group)
         self.group = self.comm.group
@@ -403,7 +374,7 @@ class ShardedAggregator:
         self.distributed = self.comm.active()
         world = self.comm.world()
         want = node_block(self.n_total, world, self.comm.rank())
-        if (self.row_begin, self.row_count) != want:
+        if check_block and (self.row_begin, self.row_count) != want:
             raise ValueError("rank %d of %d owns the node block (begin %d, %d rows) of a %d-node graph -- node_block(); got "
                              "(%d, %d)" % (self.comm.rank(), world, want[0], want[1], self.n_total, self.row_begin, self.row_count))
         self.block_rows = -(-self.n_total // world)     # rows of a full block: what the dense collectives move per rank
@@ -582,7 +553,38 @@ class ShardedAggregator:
         p = m.dropout_p() if m.training else 0.0
         comm = self.comm
         multi = comm.active()           # several ranks (or a one-rank group forced through the multi-rank path)
-        if not multi:
+        hip = isinstance(self.ops, HipOps)
+        S_total, begin = self._batch_counts(S, dev)
+        local_rows = True
+        if multi and m.variant == "hetero":
+            # the [W, S] re-view reads other ranks' paths: every rank gets the whole batch's index arrays
+            ids, codes, sel = (comm.all_gather_ragged(t, self.batch_counts) for t in (ids, codes, sel))
+            local_rows = False
+        Xn = self._prefetched_input(X_loc)
+        plan = None
+        if Xn is None:
+            Xn = X_loc.contiguous().float()
+            plan, ids, sel = self._plan_sparse(ids, sel)
+        self.last_exchange = None if not multi else "sparse" if plan is not None else "dense"
+        seed = self._draw_seed(p)
+        n_table = plan.T if plan is not None else (self.n_pad if multi else self.n_total)
+        det, compact, math = m._call_modes()
+        ms, mc = M._explicit_masks(self.mask_seq, self.mask_cls, H, Hk, math, check_range=hip) if m.training else (None, None)
+        if ms is not None or mc is not None:
+            p = 0.0
+        call = M.PaggCall(m.variant, max(n_table, 1), X_loc.shape[1], Hk, m.out_size, S, int(num_w), int(walk_len),
+                          S_total if multi else 0, begin if multi else 0, 0, m._cell_kind, det, compact, math,
+                          p_seq=p, p_cls=p, seed=seed, mask_seq=ms, mask_cls=mc, index_rows_local=local_rows and multi,
+                          bank_w=fw, bank_b=fb, sparse_plan=plan)
+        if hip:
+            call.pick_batch_groups(m.workspace_budget)
+        return _ShardedFn.apply(self, call, Xn, ids, codes, sel, *params)
+
+    def _batch_counts(self, S, dev):
+        """Sets batch_counts, the masked nodes per rank of this call (S: this rank's).  -> (masked nodes of the whole batch,
+        of the ranks before this one)"""
+        comm = self.comm
+        if not comm.active():
             counts = [S]
         elif self._fixed_counts is not None:
             counts = self._fixed_counts
@@ -592,48 +594,11 @@ class ShardedAggregator:
         else:
             counts = comm.counts(S, dev)        # (a host round trip: see set_batch_counts)
         self.batch_counts = counts
-        S_total, begin = sum(counts), sum(counts[:comm.rank()])
-        local_rows = True
-        if multi and m.variant == "hetero":
-            # the [W, S] re-view reads other ranks' paths: every rank gets the whole batch's index arrays
-            ids, codes, sel = (comm.all_gather_ragged(t, counts) for t in (ids, codes, sel))
-            local_rows = False
-        Xn = self._prefetched_input(X_loc)
-        plan = None
-        if Xn is None:
-            Xn = X_loc.contiguous().float()
-            plan, ids, sel = self._plan_sparse(ids, sel)
-        self.last_exchange = None if not multi else "sparse" if plan is not None else "dense"
-        # one seed per step for all ranks (positions in the batch separate their masks)
-        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, generator=self._seed_gen).item()) if p > 0 else 0
-        n_table = plan.T if plan is not None else (self.n_pad if multi else self.n_total)
-        cfg = dict(variant=m.variant, N=max(n_table, 1), F=X_loc.shape[1], H=Hk, C=m.out_size, S=S,
-                   W=int(num_w), L=int(walk_len), p_seq=p, p_cls=p, bank_w=fw, bank_b=fb, seed=seed,
-                   S_total=S_total, group_begin=begin, index_rows_local=local_rows and multi, cell=m._cell_kind,
-                   mask_seq=None, mask_cls=None, sparse_plan=plan,
-                   deterministic=M.deterministic_default() if m.deterministic is None else bool(m.deterministic),
-                   compact=M.compact_default(),
-                   seq_math=M.seq_math_default() if m.seq_math is None else M._SEQ_MATH[m.seq_math])
-        if not multi:
-            cfg["S_total"], cfg["group_begin"] = 0, 0
-        if m.training and (self.mask_seq is not None or self.mask_cls is not None):
-            ms, mc = self.mask_seq, self.mask_cls
-            if Hk != H:         # explicit masks are given for the module's own hidden size
-                P = torch.nn.functional.pad
-                ms = P(ms, (0, Hk - H)).contiguous() if ms is not None else None
-                mc = P(mc.view(mc.shape[0], 2, H), (0, Hk - H)).reshape(mc.shape[0], 2 * Hk).contiguous() if mc is not None else None
-            if (ms is not None and isinstance(self.ops, HipOps) and cfg["seq_math"] != _lib.SEQ_MATH_BF16X3
-                    and float(ms.abs().max()) > 16.0):
-                raise ValueError("explicit sequence masks must satisfy |m| <= 16 with seq_math f16x2 (include/pathnet_hip.h); "
-                                 "use seq_math='bf16x3' for others")
-            cfg["mask_seq"], cfg["mask_cls"] = ms, mc
-            cfg["p_seq"] = cfg["p_cls"] = 0.0
-        cfg["batch_groups"] = M.pick_batch_groups(m.variant, cfg["N"], cfg["F"], cfg["H"], cfg["C"], S, cfg["W"],
-                                                  cfg["L"], m.workspace_budget, cell=m._cell_kind,
-                                                  deterministic=cfg["deterministic"], S_total=cfg["S_total"],
-                                                  group_begin=cfg["group_begin"], compact=cfg["compact"],
-                                                  seq_math=cfg["seq_math"]) if isinstance(self.ops, HipOps) else 0
-        return _ShardedFn.apply(self, cfg, Xn, ids, codes, sel, *params)
+        return sum(counts), sum(counts[:comm.rank()])
+
+    def _draw_seed(self, p):
+        """one dropout seed per step for all ranks (positions in the batch separate their masks); 0 without dropout"""
+        return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, generator=self._seed_gen).item()) if p > 0 else 0
 
     def set_batch_counts(self, counts):
         """Masked nodes per rank, when they are the same every step (a fixed train mask): spares the per-step
@@ -702,18 +667,8 @@ class ReplicatedAggregator(ShardedAggregator):
     step from identically seeded generators)."""
 
     def __init__(self, module, n_total, group=None, comm=None, dropout_seed=0):
-        self.module, self.n_total, self.row_begin, self.row_count = module, int(n_total), 0, int(n_total)
-        self.comm = comm if comm is not None else Comm(group)
-        self.group = self.comm.group
-        self.ops = None
-        self.distributed = self.comm.active()
-        self._flat = None
-        self._flat_ids = None
-        self.batch_counts = None
-        self._fixed_counts = None
-        self._seed_gen = torch.Generator()
-        self._seed_gen.manual_seed(int(dropout_seed))
-        self.mask_seq = self.mask_cls = None
+        # (every rank holds the whole graph: there is no node block to check)
+        super().__init__(module, n_total, 0, n_total, group=group, comm=comm, dropout_seed=dropout_seed, check_block=False)
         self.compact_nodes = None       # True / False: run on the rows of X the call's paths can touch; None: when they are few
 
     def _touched_rows(self, X, ids, sel):
@@ -756,26 +711,17 @@ class ReplicatedAggregator(ShardedAggregator):
         dev = X.device
         comm = self.comm
         ids, codes, sel, S = M._as_index_tensors(neis, layer_type, sel_global, num_w, walk_len, dev, n_nodes=self.n_total)
+        S_total, begin = self._batch_counts(S, dev)
         if not comm.active():
-            self.batch_counts = [S]
             X, ids, sel = self._touched_rows(X, ids, sel)
             return m._run(X, ids, num_w, walk_len, sel, codes)
-        if self._fixed_counts is not None:
-            counts = self._fixed_counts
-            if counts[comm.rank()] != S:
-                raise ValueError("set_batch_counts said %d masked nodes for this rank, the call has %d" % (counts[comm.rank()], S))
-        else:
-            counts = comm.counts(S, dev)
-        self.batch_counts = counts
-        S_total, begin = sum(counts), sum(counts[:comm.rank()])
-        p = m.dropout_p() if m.training else 0.0
-        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, generator=self._seed_gen).item()) if p > 0 else None
+        seed = self._draw_seed(m.dropout_p() if m.training else 0.0)
         old = m._mask_seq, m._mask_cls
         if self.mask_seq is not None or self.mask_cls is not None:
             m._mask_seq, m._mask_cls = self.mask_seq, self.mask_cls
         try:
             if m.variant == "hetero":
-                ids, codes, sel = (comm.all_gather_ragged(t, counts) for t in (ids, codes, sel))
+                ids, codes, sel = (comm.all_gather_ragged(t, self.batch_counts) for t in (ids, codes, sel))
                 X, ids, sel = self._touched_rows(X, ids, sel)
                 return m._run(X, ids, num_w, walk_len, sel, codes, group_slice=(begin, S), seed=seed)
             X, ids, sel = self._touched_rows(X, ids, sel)

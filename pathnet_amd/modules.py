@@ -75,11 +75,125 @@ def seq_math_default():
     return _SEQ_MATH[e]
 
 
+class PaggCall:
+    """One aggregator call as the library is to see it, described once: the fields of pn_pagg_shape by name (SHAPE_FIELDS: the
+    struct's order and defaults; variant and cell by their Python names) and what the call carries besides.  Everything
+    that fills a pn_pagg_shape / pn_pagg_args -- the modules here, dist.HipOps -- goes through shape() / args().  What is
+    decided after construction (batch_groups, workspace, reuse_tables) is assigned to attributes that exist from the start;
+    a name that is not listed below raises."""
+    SHAPE_FIELDS = ("variant", "N", "F", "H", "C", "S", "W", "L", "S_total", "group_begin", "batch_groups", "cell",
+                    "deterministic", "compact", "seq_math")
+    __slots__ = SHAPE_FIELDS + ("p_seq", "p_cls", "seed", "mask_seq", "mask_cls", "step_state", "index_rows_local", "bank_w",
+                                "bank_b", "grad", "reuse_tables", "grad_scale", "path_state", "sparse_plan", "workspace",
+                                "_shape", "_ws_bytes")
+
+    def __init__(self, variant, N, F, H, C, S, W, L, S_total=0, group_begin=0, batch_groups=0, cell=None, deterministic=False,
+                 compact=None, seq_math=None, *, p_seq=0.0, p_cls=0.0, seed=0, mask_seq=None, mask_cls=None, step_state=None,
+                 index_rows_local=False, bank_w=None, bank_b=None, grad=True, reuse_tables=0, grad_scale=1.0,
+                 path_state=False, sparse_plan=None, workspace=None):
+        self.variant, self.N, self.F, self.H, self.C, self.S, self.W, self.L = variant, N, F, H, C, S, W, L
+        self.S_total, self.group_begin, self.batch_groups, self.cell = S_total, group_begin, batch_groups, cell
+        # decisions that shape the workspace are taken once per call and travel with its shape
+        self.deterministic = bool(deterministic)
+        self.compact = compact_default() if compact is None else int(compact)
+        self.seq_math = seq_math_default() if seq_math is None else int(seq_math)
+        self.p_seq, self.p_cls, self.seed, self.mask_seq, self.mask_cls = p_seq, p_cls, seed, mask_seq, mask_cls
+        self.step_state, self.index_rows_local, self.bank_w, self.bank_b = step_state, index_rows_local, bank_w, bank_b
+        # grad False: a torch.no_grad() forward, which skips the saved tensors.  reuse_tables 1: Xh and the dense bank in the
+        # workspace are valid, 2: Xh only
+        self.grad, self.reuse_tables, self.grad_scale, self.path_state = grad, reuse_tables, grad_scale, path_state
+        self.sparse_plan, self.workspace = sparse_plan, workspace
+        self._shape = self._ws_bytes = None
+
+    def get(self, name, default=None):
+        """call.get("S_total") / call["W"]: read access by name for ShardedAggregator(ops=...) backends written against the
+        earlier dict description.  Every name exists, so no default applies: an unknown one raises here too."""
+        return getattr(self, name)
+    __getitem__ = get
+
+    def shape(self):
+        """the call's _lib.PaggShape, built at the first use"""
+        if self._shape is None:
+            self._shape = _lib.PaggShape(_VARIANT[self.variant], self.N, self.F, self.H, self.C, self.S, self.W, self.L,
+                                         self.S_total, self.group_begin, self.batch_groups, _CELL[self.cell],
+                                         1 if self.deterministic else 0, self.compact, self.seq_math)
+        return self._shape
+
+    def set_batch_groups(self, bg):
+        """the one shape field that is decided after the others: what was derived from the shape is derived again"""
+        self.batch_groups = bg
+        self._shape = self._ws_bytes = None
+        return self
+
+    def pick_batch_groups(self, budget, device=None):
+        # (the module's function, looked up at the call: tools/ab_chunks.py replaces it)
+        return self.set_batch_groups(pick_batch_groups(
+            self.variant, self.N, self.F, self.H, self.C, self.S, self.W, self.L, budget, cell=self.cell, device=device,
+            deterministic=self.deterministic, S_total=self.S_total, group_begin=self.group_begin, compact=self.compact,
+            seq_math=self.seq_math))
+
+    def workspace_bytes(self):
+        if self._ws_bytes is None:
+            n = ctypes.c_int64(0)
+            _lib.check(_lib.load().pn_pagg_workspace_bytes(ctypes.byref(self.shape()), ctypes.byref(n)))
+            self._ws_bytes = n.value
+        return self._ws_bytes
+
+    def take_workspace(self, dev, have=None):
+        """`have` when it sits on `dev` and is large enough for this call, else a new tensor"""
+        need = self.workspace_bytes()
+        if have is not None and have.numel() >= need and have.device == dev:
+            return have
+        return torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+
+    def args(self, ids, codes, sel, p, X=None, Xh=None):
+        """A _lib.PaggArgs with the call's inputs: shape, index arrays, parameters (p: _split_params), dropout, flags.
+        X: the feature matrix, which the library projects itself (the modules here).  Xh: the caller has projected already --
+        the node-sharded runner applies fc0 to its own rows before the exchange -- so the library gets the projected table
+        and no fc0; that runner has no captured steps either, its calls carry no step_state.
+        Outputs, workspace and gradient pointers are the caller's to add (grad_buffers)."""
+        a = _lib.PaggArgs()
+        a.shape = self.shape()
+        if Xh is None:
+            a.X, names = X.data_ptr(), _HEAD_PARAMS
+        else:
+            a.Xh_in, names = Xh.data_ptr(), _HEAD_PARAMS[2:]
+        a.ids, a.codes, a.sel = ids.data_ptr(), codes.data_ptr(), sel.data_ptr()
+        for k in names:
+            if p[k] is not None:
+                setattr(a, k, p[k].data_ptr())
+        a.bank_w, a.bank_b = self.bank_w.data_ptr(), self.bank_b.data_ptr()
+        a.p_seq, a.p_cls, a.seed = self.p_seq, self.p_cls, self.seed
+        a.mask_seq = self.mask_seq.data_ptr() if self.mask_seq is not None else None
+        a.mask_cls = self.mask_cls.data_ptr() if self.mask_cls is not None else None
+        a.step_state = self.step_state.ptr() if self.step_state is not None else None
+        a.index_rows_local = 1 if self.index_rows_local else 0
+        return a
+
+    def grad_buffers(self, a, p, X=None, flat=False):
+        """Gradient tensors for every parameter `a` names (and for X, when given), their addresses set in a.g_*.
+        -> ({head parameter name / "bank_w" / "bank_b": tensor}, g_X or None, flat buffer or None).  flat: the parameter
+        gradients are views of ONE buffer, in 16-byte aligned pieces, that a single launch can scale."""
+        keys = [k for k in _HEAD_PARAMS if getattr(a, k)]
+        like = [p[k] for k in keys] + [self.bank_w, self.bank_b]
+        buf = None
+        if flat:
+            sizes = [-(-t.numel() // 4) * 4 for t in like]
+            buf = torch.empty(sum(sizes), dtype=torch.float32, device=self.bank_w.device)
+            pieces = [v[:t.numel()].view(t.shape) for v, t in zip(buf.split(sizes), like)]
+        else:
+            pieces = [torch.empty_like(t) for t in like]
+        grads = dict(zip(keys + ["bank_w", "bank_b"], pieces))
+        for k, g in grads.items():
+            setattr(a, "g_" + k, g.data_ptr())
+        gX = torch.empty_like(X) if X is not None else None
+        a.g_X = gX.data_ptr() if gX is not None else None
+        return grads, gX, buf
+
+
 def _shape(variant, N, F, H, C, S, W, L, S_total=0, group_begin=0, batch_groups=0, cell=None, deterministic=False,
            compact=None, seq_math=None):
-    return _lib.PaggShape(_VARIANT[variant], N, F, H, C, S, W, L, S_total, group_begin, batch_groups, _CELL[cell],
-                          1 if deterministic else 0, compact_default() if compact is None else int(compact),
-                          seq_math_default() if seq_math is None else int(seq_math))
+    return PaggCall(variant, N, F, H, C, S, W, L, S_total, group_begin, batch_groups, cell, deterministic, compact, seq_math).shape()
 
 
 def shape_info(sh):
@@ -95,18 +209,9 @@ def deterministic_default():
     return torch.are_deterministic_algorithms_enabled() or os.environ.get("PN_DETERMINISTIC", "0") not in ("", "0")
 
 
-def _cfg_shape(cfg):
-    return _shape(cfg["variant"], cfg["N"], cfg["F"], cfg["H"], cfg["C"], cfg["S"], cfg["W"], cfg["L"],
-                  cfg.get("S_total", 0), cfg.get("group_begin", 0), cfg.get("batch_groups", 0), cfg.get("cell"),
-                  cfg.get("deterministic", False), cfg.get("compact"), cfg.get("seq_math"))
-
-
 def workspace_bytes(variant, N, F, H, C, S, W, L, S_total=0, group_begin=0, batch_groups=0, cell=None, deterministic=False,
                     compact=None, seq_math=None):
-    n = ctypes.c_int64(0)
-    sh = _shape(variant, N, F, H, C, S, W, L, S_total, group_begin, batch_groups, cell, deterministic, compact, seq_math)
-    _lib.check(_lib.load().pn_pagg_workspace_bytes(ctypes.byref(sh), ctypes.byref(n)))
-    return n.value
+    return PaggCall(variant, N, F, H, C, S, W, L, S_total, group_begin, batch_groups, cell, deterministic, compact, seq_math).workspace_bytes()
 
 
 def pick_batch_groups(variant, N, F, H, C, S, W, L, budget=None, cell=None, device=None, deterministic=False,
@@ -118,10 +223,10 @@ def pick_batch_groups(variant, N, F, H, C, S, W, L, budget=None, cell=None, devi
     depend on the WHOLE call's S (and S_total for a slice of a hetero batch) when the bank runs over compact rows -- plus
     the per-path tensors of one micro-batch.  Both terms are measured on this call's own shape (batch_groups = 1 and
     1 + step), and the pick is checked against the budget afterwards."""
-    kw = dict(cell=cell, deterministic=deterministic, S_total=S_total, group_begin=group_begin, compact=compact, seq_math=seq_math)
+    call = PaggCall(variant, N, F, H, C, S, W, L, S_total, group_begin, 0, cell, deterministic, compact, seq_math)
 
     def ws(bg):
-        return workspace_bytes(variant, N, F, H, C, S, W, L, batch_groups=bg, **kw)
+        return call.set_batch_groups(bg).workspace_bytes()
     need = ws(0) if S > 1 else 0
     floor = MIN_BATCH_BYTES if budget is None else 0       # an explicit budget is kept to the byte
     if budget is None:
@@ -147,69 +252,57 @@ def pick_batch_groups(variant, N, F, H, C, S, W, L, budget=None, cell=None, devi
     return bg
 
 
-def _cfg_workspace_bytes(cfg):
-    return workspace_bytes(cfg["variant"], cfg["N"], cfg["F"], cfg["H"], cfg["C"], cfg["S"], cfg["W"], cfg["L"],
-                           cfg.get("S_total", 0), cfg.get("group_begin", 0), cfg.get("batch_groups", 0), cfg.get("cell"),
-                           cfg.get("deterministic", False), cfg.get("compact"), cfg.get("seq_math"))
-
-
 def _split_params(params, L):
     """Function inputs -> dict of the tensors the C ABI wants.  `params` is
-    (fc0_w, fc0_b, w_ih, w_hh, b_ih, b_hh, att_w, att_b, fc2_w, fc2_b, bank_w_0..L-1, bank_b_0..L-1);
+    (the ten _HEAD_PARAMS, bank_w_0..L-1, bank_b_0..L-1);
     the bank entries are views of one contiguous [L,H,H] / [L,H] buffer (see _Aggregator._bank)."""
-    names = ("fc0_w", "fc0_b", "w_ih", "w_hh", "b_ih", "b_hh", "att_w", "att_b", "fc2_w", "fc2_b")
-    p = dict(zip(names, params[:10]))
+    p = dict(zip(_HEAD_PARAMS, params[:10]))
     p["bank_ws"], p["bank_bs"] = params[10:10 + L], params[10 + L:10 + 2 * L]
     return p
+
+
+def _grad_tuple(grads, L):
+    """PaggCall.grad_buffers' dict -> the gradients in the order of the Function inputs `params` (None: no such parameter)"""
+    return tuple(grads.get(k) for k in _HEAD_PARAMS) + tuple(grads["bank_w"][d] for d in range(L)) + tuple(
+        grads["bank_b"][d] for d in range(L))
+
+
+def _begin(call, ids, codes, sel, p, X=None, Xh=None):
+    """what every forward starts with (X / Xh: PaggCall.args): -> (args with inputs, logits and workspace set; logits; workspace)"""
+    dev = ids.device
+    out = torch.empty((call.S, call.C), dtype=torch.float32, device=dev)
+    ws = call.take_workspace(dev, call.workspace)
+    a = call.args(ids, codes, sel, p, X=X, Xh=Xh)
+    a.out = out.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    return a, out, ws
 
 
 class _PaggFunction(torch.autograd.Function):
     """forward/backward through pn_pagg_forward / pn_pagg_backward."""
 
     @staticmethod
-    def _args(cfg, X, ids, codes, sel, p):
-        a = _lib.PaggArgs()
-        a.shape = _cfg_shape(cfg)
-        a.X, a.ids, a.codes, a.sel = X.data_ptr(), ids.data_ptr(), codes.data_ptr(), sel.data_ptr()
-        for k in ("fc0_w", "fc0_b", "w_ih", "w_hh", "b_ih", "b_hh", "att_w", "att_b", "fc2_w", "fc2_b"):
-            setattr(a, k, p[k].data_ptr() if p[k] is not None else None)
-        a.bank_w, a.bank_b = cfg["bank_w"].data_ptr(), cfg["bank_b"].data_ptr()
-        a.p_seq, a.p_cls, a.seed = cfg["p_seq"], cfg["p_cls"], cfg["seed"]
-        ms, mc = cfg.get("mask_seq"), cfg.get("mask_cls")
-        a.mask_seq = ms.data_ptr() if ms is not None else None
-        a.mask_cls = mc.data_ptr() if mc is not None else None
-        st = cfg.get("step_state")
-        a.step_state = st.ptr() if st is not None else None
-        a.index_rows_local = 1 if cfg.get("index_rows_local") else 0
-        return a
-
-    @staticmethod
-    def forward(ctx, cfg, X, ids, codes, sel, *params):
-        lib = _lib.load()
-        p = _split_params(params, cfg["L"])
+    def _forward(ctx, call, X, ids, codes, sel, params, encode_out=None):
+        """encode_out (_PaggEncodeFunction): (embedding, path weights, path states or None) for the library to fill"""
+        p = _split_params(params, call.L)
         dev = X.device
-        nbytes = _cfg_workspace_bytes(cfg)
-        ws = cfg.get("workspace")
         with torch.cuda.device(dev):        # the library launches on the current device
-            out = torch.empty((cfg["S"], cfg["C"]), dtype=torch.float32, device=dev)
-            if ws is None or ws.numel() < nbytes or ws.device != dev:
-                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-            a = _PaggFunction._args(cfg, X, ids, codes, sel, p)
-            a.out = out.data_ptr()
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-            a.no_save = 0 if cfg.get("grad", True) else 1       # torch.no_grad() forwards skip the saved tensors
-            a.reuse_tables = int(cfg.get("reuse_tables") or 0)     # 1: Xh and the dense bank are valid, 2: Xh only
-            enc = cfg.get("encode_out")         # (_PaggEncodeFunction: embedding, path weights, path states or None)
-            if enc is not None:
-                a.out_embed, a.out_path_weight = enc[0].data_ptr(), enc[1].data_ptr()
-                a.out_path_state = enc[2].data_ptr() if enc[2] is not None else None
-            if cfg["S"] > 0:
-                _lib.check(lib.pn_pagg_forward(_lib.context(dev), ctypes.byref(a), _lib.stream_ptr(dev)))
-        ctx.cfg, ctx.ws = cfg, ws
-        cfg["ws_used"] = ws         # (the module's range guard reads the call's pn_seq_range back from it)
+            a, out, ws = _begin(call, ids, codes, sel, p, X=X)
+            a.no_save = 0 if call.grad else 1
+            a.reuse_tables = int(call.reuse_tables or 0)
+            if encode_out is not None:
+                a.out_embed, a.out_path_weight = encode_out[0].data_ptr(), encode_out[1].data_ptr()
+                a.out_path_state = encode_out[2].data_ptr() if encode_out[2] is not None else None
+            if call.S > 0:
+                _lib.check(_lib.load().pn_pagg_forward(_lib.context(dev), ctypes.byref(a), _lib.stream_ptr(dev)))
+        ctx.call, ctx.ws = call, ws
         ctx.present = [t is not None for t in params]
         ctx.save_for_backward(X, ids, codes, sel, *[t for t in params if t is not None])
         return out
+
+    @staticmethod
+    def forward(ctx, call, X, ids, codes, sel, *params):
+        return _PaggFunction._forward(ctx, call, X, ids, codes, sel, params)
 
     @staticmethod
     def backward(ctx, g_out):
@@ -218,42 +311,27 @@ class _PaggFunction(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, g_out, g_embed):
         """one pn_pagg_backward for d loss / d logits (g_out) and / or d loss / d embedding (g_embed); either may be None"""
-        lib = _lib.load()
-        cfg = ctx.cfg
+        call = ctx.call
         saved = list(ctx.saved_tensors)
         X, ids, codes, sel = saved[:4]
         it = iter(saved[4:])
         params = [next(it) if pres else None for pres in ctx.present]
-        L = cfg["L"]
-        p = _split_params(params, L)
+        p = _split_params(params, call.L)
         dev = X.device
         with torch.cuda.device(dev):
             g_out = g_out.contiguous().float() if g_out is not None else None
             g_embed = g_embed.contiguous().float() if g_embed is not None else None
-            a = _PaggFunction._args(cfg, X, ids, codes, sel, p)
-            grads = {}
-            for k in ("fc0_w", "fc0_b", "w_ih", "w_hh", "b_ih", "b_hh", "att_w", "att_b", "fc2_w", "fc2_b"):
-                if p[k] is not None:
-                    grads[k] = torch.empty_like(p[k])
-                    setattr(a, "g_" + k, grads[k].data_ptr())
-            g_bank_w, g_bank_b = torch.empty_like(cfg["bank_w"]), torch.empty_like(cfg["bank_b"])
-            a.g_bank_w, a.g_bank_b = g_bank_w.data_ptr(), g_bank_b.data_ptr()
-            gX = torch.empty_like(X) if ctx.needs_input_grad[1] else None
-            a.g_X = gX.data_ptr() if gX is not None else None
+            a = call.args(ids, codes, sel, p, X=X)
+            grads, gX, _ = call.grad_buffers(a, p, X if ctx.needs_input_grad[1] else None)
             a.workspace, a.workspace_bytes = ctx.ws.data_ptr(), ctx.ws.numel()
             a.g_out = g_out.data_ptr() if g_out is not None else None
             a.g_embed = g_embed.data_ptr() if g_embed is not None else None
-            if cfg["S"] > 0:
-                _lib.check(lib.pn_pagg_backward(_lib.context(dev), ctypes.byref(a), _lib.stream_ptr(dev)))
+            if call.S > 0:
+                _lib.check(_lib.load().pn_pagg_backward(_lib.context(dev), ctypes.byref(a), _lib.stream_ptr(dev)))
             else:
-                for g in list(grads.values()) + [g_bank_w, g_bank_b]:
+                for g in list(grads.values()) + [gX] * (gX is not None):
                     g.zero_()
-                if gX is not None:
-                    gX.zero_()
-        head = tuple(grads.get(k) for k in ("fc0_w", "fc0_b", "w_ih", "w_hh", "b_ih", "b_hh", "att_w", "att_b",
-                                            "fc2_w", "fc2_b"))
-        return (None, gX, None, None, None) + head + tuple(g_bank_w[d] for d in range(L)) + tuple(
-            g_bank_b[d] for d in range(L))
+        return (None, gX, None, None, None) + _grad_tuple(grads, call.L)
 
 
 class _PaggEncodeFunction(torch.autograd.Function):
@@ -262,17 +340,14 @@ class _PaggEncodeFunction(torch.autograd.Function):
     the upstream gradients of both (g_out / g_embed, an unused output's being NULL)."""
 
     @staticmethod
-    def forward(ctx, cfg, X, ids, codes, sel, *params):
-        S, W, H, dev = cfg["S"], cfg["W"], cfg["H"], X.device
+    def forward(ctx, call, X, ids, codes, sel, *params):
+        S, W, H, dev = call.S, call.W, call.H, X.device
         with torch.cuda.device(dev):
             emb = torch.empty((S, 2 * H), dtype=torch.float32, device=dev)
             pw = torch.empty((S, W), dtype=torch.float32, device=dev)
-            ps = torch.empty((S, W, H), dtype=torch.float32, device=dev) if cfg["path_state"] else None
-        cfg["encode_out"] = (emb, pw, ps)
-        try:
-            out = _PaggFunction.forward(ctx, cfg, X, ids, codes, sel, *params)
-        finally:
-            del cfg["encode_out"]       # (ctx keeps cfg: it must not hold the outputs)
+            ps = torch.empty((S, W, H), dtype=torch.float32, device=dev) if call.path_state else None
+        # (the outputs travel as an argument: ctx keeps `call`, and it must not hold the outputs)
+        out = _PaggFunction._forward(ctx, call, X, ids, codes, sel, params, encode_out=(emb, pw, ps))
         ctx.mark_non_differentiable(*[t for t in (pw, ps) if t is not None])
         # (an output the loss does not use gets no zero-filled gradient: pn_pagg_backward is given NULL for it)
         ctx.set_materialize_grads(False)
@@ -291,49 +366,26 @@ class _PaggLossFunction(torch.autograd.Function):
     out by backward(), scaled by the upstream gradient of the loss."""
 
     @staticmethod
-    def forward(ctx, cfg, X, ids, codes, sel, target, *params):
-        lib = _lib.load()
-        L = cfg["L"]
-        p = _split_params(params, L)
+    def forward(ctx, call, X, ids, codes, sel, target, *params):
+        p = _split_params(params, call.L)
         dev = X.device
-        nbytes = _cfg_workspace_bytes(cfg)
-        ws = cfg.get("workspace")
         with torch.cuda.device(dev):
-            out = torch.empty((cfg["S"], cfg["C"]), dtype=torch.float32, device=dev)
+            a, out, _ = _begin(call, ids, codes, sel, p, X=X)
             # (pn_pagg_train_step stores the loss -- or clears it itself before accumulating over micro-batches: no fill here)
-            loss = (torch.empty if cfg["S"] > 0 else torch.zeros)((), dtype=torch.float32, device=dev)
-            if ws is None or ws.numel() < nbytes or ws.device != dev:
-                ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-            a = _PaggFunction._args(cfg, X, ids, codes, sel, p)
-            a.out = out.data_ptr()
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+            loss = (torch.empty if call.S > 0 else torch.zeros)((), dtype=torch.float32, device=dev)
             # every parameter gradient is a view of one flat buffer: backward() scales them by the upstream gradient of
             # the loss with one launch instead of one per tensor
-            keys = [k for k in ("fc0_w", "fc0_b", "w_ih", "w_hh", "b_ih", "b_hh", "att_w", "att_b", "fc2_w", "fc2_b")
-                    if p[k] is not None]
-            shapes = [p[k].shape for k in keys] + [cfg["bank_w"].shape, cfg["bank_b"].shape]
-            sizes = [-(-int(np.prod(sh)) // 4) * 4 for sh in shapes]         # 16-byte aligned pieces
-            flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-            pieces = [v[:int(np.prod(sh))].view(sh) for v, sh in zip(flat.split(sizes), shapes)]
-            grads = dict(zip(keys, pieces))
-            for k in keys:
-                setattr(a, "g_" + k, grads[k].data_ptr())
-            g_bank_w, g_bank_b = pieces[-2], pieces[-1]
-            a.g_bank_w, a.g_bank_b = g_bank_w.data_ptr(), g_bank_b.data_ptr()
-            gX = torch.empty_like(X) if ctx.needs_input_grad[1] else None
-            a.g_X = gX.data_ptr() if gX is not None else None
+            grads, gX, flat = call.grad_buffers(a, p, X if ctx.needs_input_grad[1] else None, flat=True)
             target = target.to(device=dev, dtype=torch.int64).contiguous()
-            if cfg["S"] > 0:
-                _lib.check(lib.pn_pagg_train_step(_lib.context(dev), ctypes.byref(a), target.data_ptr(),
-                                                  float(cfg["grad_scale"]), loss.data_ptr(), _lib.stream_ptr(dev)))
+            if call.S > 0:
+                _lib.check(_lib.load().pn_pagg_train_step(_lib.context(dev), ctypes.byref(a), target.data_ptr(),
+                                                          float(call.grad_scale), loss.data_ptr(), _lib.stream_ptr(dev)))
             else:
                 flat.zero_()
                 if gX is not None:
                     gX.zero_()
-        head = tuple(grads.get(k) for k in ("fc0_w", "fc0_b", "w_ih", "w_hh", "b_ih", "b_hh", "att_w", "att_b", "fc2_w", "fc2_b"))
-        ctx.grads = (gX,) + head + tuple(g_bank_w[d] for d in range(L)) + tuple(g_bank_b[d] for d in range(L))
+        ctx.grads = (gX,) + _grad_tuple(grads, call.L)
         ctx.flat = flat
-        cfg["ws_used"] = ws
         ctx.mark_non_differentiable(out)
         # (without this autograd materialises a zero gradient for `out` -- an [S, C] fill launch in front of the optimizer,
         #  on the step's critical path: profiles/r06_glue.txt)
@@ -402,6 +454,22 @@ def _as_index_tensors(neis, layer_type, indices, num_w, walk_len, device, n_node
 
 
 Encoded = collections.namedtuple("Encoded", ("logits", "embedding", "path_weight", "path_state"))
+
+
+def _explicit_masks(ms, mc, H, Hk, seq_math, check_range=True):
+    """Explicit dropout masks (test hook; given for the module's own hidden size H) as the kernels at hidden size Hk read
+    them.  The caller zeroes the call's dropout probabilities.  check_range: the library's kernels will read them."""
+    if ms is None and mc is None:
+        return None, None
+    if Hk != H:
+        P = torch.nn.functional.pad
+        ms = P(ms, (0, Hk - H)).contiguous() if ms is not None else None
+        mc = P(mc.view(mc.shape[0], 2, H), (0, Hk - H)).reshape(mc.shape[0], 2 * Hk).contiguous() if mc is not None else None
+    if ms is not None and check_range and seq_math != _lib.SEQ_MATH_BF16X3 and float(ms.abs().max()) > 16.0:
+        # (one device round trip) the fp16 kernels scale the gathered rows for masks up to 16 = 1 / (1 - 0.9375)
+        raise ValueError("explicit sequence masks must satisfy |m| <= 16 with seq_math f16x2 (include/pathnet_hip.h); "
+                         "use seq_math='bf16x3' for others")
+    return ms, mc
 
 
 class _Aggregator(nn.Module):
@@ -632,10 +700,10 @@ class _Aggregator(nn.Module):
             self._range_pending = None
             self._range_eval(rec)
 
-    def _range_read(self, cfg, sync):
-        ws = cfg.get("ws_used")
+    def _range_read(self, call, ws, sync):
+        """start (sync: finish) the read-back of the range record that `call` left in its workspace `ws`"""
         off = ctypes.c_int64(-1)
-        _lib.check(_lib.load().pn_pagg_range_offset(ctypes.byref(_cfg_shape(cfg)), ctypes.byref(off)))
+        _lib.check(_lib.load().pn_pagg_range_offset(ctypes.byref(call.shape()), ctypes.byref(off)))
         if ws is None or off.value < 0:
             return
         rec = torch.empty(6, dtype=torch.int32, pin_memory=True)
@@ -647,6 +715,11 @@ class _Aggregator(nn.Module):
             self._range_eval(rec)
         else:
             self._range_pending = (rec, ev)
+
+    def _call_modes(self):
+        """(deterministic, compact, seq_math) of a call of this module, as PaggCall takes them"""
+        return (deterministic_default() if self.deterministic is None else bool(self.deterministic), compact_default(),
+                seq_math_default() if self.seq_math is None else _SEQ_MATH[self.seq_math])
 
     def _run(self, X, neis, num_w, walk_len, indices, layer_type, reuse_tables=False, group_slice=None, target=None,
              grad_scale=None, fused=None, batch_position=None, seed=None, _math=None, _encode=None):
@@ -661,26 +734,23 @@ class _Aggregator(nn.Module):
             raise RuntimeError("pathnet_amd aggregators run on the GPU only (X is on %s); no CPU fallback" % dev)
         X = X.contiguous().float()
         ids, codes, sel, S = _as_index_tensors(neis, layer_type, indices, num_w, walk_len, dev, n_nodes=X.shape[0])
-        H = self.hidden_size
+        H, L = self.hidden_size, int(walk_len)
         Hk = -(-H // 32) * 32           # the kernels' hidden size: H, or H zero-padded to the next multiple of 32
         fw, fb, params = self._param_inputs() if Hk == H else self._padded_param_inputs(Hk)
         training = self.training
         p = self.dropout_p() if training else 0.0
-        math = _math if _math is not None else (seq_math_default() if self.seq_math is None else _SEQ_MATH[self.seq_math])
+        det, compact, math = self._call_modes()
+        if _math is not None:
+            math = _math
         guard = (_math is None and self.seq_math is None and self.range_guard and math != _lib.SEQ_MATH_BF16X3 and
                  self.step_state is None)
         if guard:
             self._range_poll()
             if self._range_wide:
                 math, guard = _lib.SEQ_MATH_BF16X3, False
-        cfg = dict(variant=self.variant, N=X.shape[0], F=X.shape[1], H=Hk, C=self.out_size, S=S,
-                   W=int(num_w), L=int(walk_len), p_seq=p, p_cls=p, mask_seq=None, mask_cls=None, bank_w=fw, bank_b=fb,
-                   step_state=self.step_state, cell=self._cell_kind,
-                   deterministic=deterministic_default() if self.deterministic is None else bool(self.deterministic),
-                   # decisions that shape the workspace are taken once per call and travel with its shape
-                   compact=compact_default(), seq_math=math,
-                   seed=(int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item()))
-                   if (p > 0 and self.step_state is None) else 0)
+        draws = p > 0 and self.step_state is None       # (else the seed is unused, or read from the step state)
+        seed = (int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())) if draws else 0
+        S_total = begin = 0
         if batch_position is not None:
             # (data-parallel ranks, dist.ReplicatedAggregator) the S masked nodes of this call are the rows [begin, begin + S)
             # of a batch of S_total whose other rows are computed elsewhere; neis / indices / layer_type hold this call's
@@ -691,91 +761,73 @@ class _Aggregator(nn.Module):
             S_total, begin = int(batch_position[0]), int(batch_position[1])
             if begin < 0 or begin + S > S_total:
                 raise ValueError("batch_position (%d, %d): %d rows do not fit" % (S_total, begin, S))
-            cfg["S_total"], cfg["group_begin"], cfg["index_rows_local"] = S_total, begin, True
         if group_slice is not None:
             begin, count = int(group_slice[0]), int(group_slice[1])
             if begin < 0 or count < 0 or begin + count > S:
                 raise ValueError("group_slice (%d, %d) outside the batch of %d masked nodes" % (begin, count, S))
-            cfg["S_total"], cfg["group_begin"], cfg["S"] = S, begin, count
-            S = count
-        if len(params) != 10 + 2 * cfg["L"]:
-            raise ValueError("walk_len=%d but the module has %d distance layers" % (cfg["L"], (len(params) - 10) // 2))
-        if training and (self._mask_seq is not None or self._mask_cls is not None):
-            ms, mc = self._mask_seq, self._mask_cls
-            if Hk != H:         # explicit masks are given for the module's own hidden size
-                P = torch.nn.functional.pad
-                ms = P(ms, (0, Hk - H)).contiguous() if ms is not None else None
-                mc = P(mc.view(mc.shape[0], 2, H), (0, Hk - H)).reshape(mc.shape[0], 2 * Hk).contiguous() if mc is not None else None
-            if ms is not None and cfg["seq_math"] != _lib.SEQ_MATH_BF16X3 and float(ms.abs().max()) > 16.0:
-                # (test hook only: one device round trip) the fp16 kernels scale the gathered rows for masks up to 16 = 1 / (1 - 0.9375)
-                raise ValueError("explicit sequence masks must satisfy |m| <= 16 with seq_math f16x2 (include/pathnet_hip.h); "
-                                 "use seq_math='bf16x3' for others")
-            cfg["mask_seq"], cfg["mask_cls"] = ms, mc
-            cfg["p_seq"] = cfg["p_cls"] = 0.0
-        cfg["grad"] = torch.is_grad_enabled()
-        cfg["batch_groups"] = pick_batch_groups(self.variant, cfg["N"], cfg["F"], cfg["H"], cfg["C"], S, cfg["W"],
-                                                cfg["L"], self.workspace_budget, cell=self._cell_kind, device=dev,
-                                                deterministic=cfg["deterministic"], S_total=cfg.get("S_total", 0),
-                                                group_begin=cfg.get("group_begin", 0), compact=cfg["compact"],
-                                                seq_math=cfg["seq_math"])
-        self._last_shape = (_cfg_shape(cfg), dev)       # (paths_stream: where the NEXT call of this shape reads its paths)
-        if not cfg["grad"]:
-            need = _cfg_workspace_bytes(cfg)
-            fits = self._ws_eval is not None and self._ws_eval.numel() >= need and self._ws_eval.device == dev
-            key = self._tables_key(X, cfg["L"])
-            compact_now = shape_info(_cfg_shape(cfg))[0]
+            S_total, S = S, count
+        if len(params) != 10 + 2 * L:
+            raise ValueError("walk_len=%d but the module has %d distance layers" % (L, (len(params) - 10) // 2))
+        ms, mc = _explicit_masks(self._mask_seq, self._mask_cls, H, Hk, math) if training else (None, None)
+        p_drop = p if ms is None and mc is None else 0.0       # explicit masks stand in for the drawn ones
+        grad = torch.is_grad_enabled()
+        call = PaggCall(self.variant, X.shape[0], X.shape[1], Hk, self.out_size, S, int(num_w), L, S_total, begin, 0,
+                        self._cell_kind, det, compact, math, p_seq=p_drop, p_cls=p_drop, seed=seed, mask_seq=ms, mask_cls=mc,
+                        step_state=self.step_state, index_rows_local=batch_position is not None, bank_w=fw, bank_b=fb,
+                        grad=grad, path_state=bool(_encode))
+        call.pick_batch_groups(self.workspace_budget, dev)
+        self._last_shape = (call.shape(), dev)       # (paths_stream: where the NEXT call of this shape reads its paths)
+        if not grad:
+            ws = call.take_workspace(dev, self._ws_eval)
+            fits = ws is self._ws_eval
+            key = self._tables_key(X, L)
+            compact_now = shape_info(call.shape())[0]
             # what the workspace holds: (key, dense) -- Xh for `key`, and with dense also the distance bank over all N * L
             # rows.  A compact call leaves only ITS batch's rows of the bank behind (a later dense call must not
             # read them as the full table), so it hands on Xh alone.
             have_key, have_dense = self._ws_tables if self._ws_tables is not None else (None, False)
-            mode = 0
             if reuse_tables and fits and have_key == key:
-                mode = 1 if (have_dense and not compact_now) else 2
-            if not fits:
-                with torch.cuda.device(dev):
-                    self._ws_eval = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-            cfg["workspace"] = self._ws_eval
-            cfg["reuse_tables"] = mode
+                call.reuse_tables = 1 if (have_dense and not compact_now) else 2
+            call.workspace = self._ws_eval = ws
             # the tables are in the workspace after this call only if it computes (or keeps) them: S = 0 returns early
             self._ws_tables = (key, not compact_now) if S > 0 else None
         elif reuse_tables:
             raise RuntimeError("reuse_tables is for no-grad (inference) forwards")
         else:
+            call.workspace = call.take_workspace(dev)
             self._ws_tables = None          # a training forward: the weights are about to change
         if target is not None:
-            if not cfg["grad"]:
+            if not grad:
                 raise RuntimeError("forward_loss computes gradients: call it with grad enabled")
             target = torch.as_tensor(target)
             if target.numel() != S:
                 raise ValueError("target holds %d classes, the batch has %d masked nodes" % (target.numel(), S))
-            cfg["grad_scale"] = (1.0 / max(S, 1)) if grad_scale is None else float(grad_scale)
+            call.grad_scale = (1.0 / max(S, 1)) if grad_scale is None else float(grad_scale)
             target = target.reshape(-1)
             if fused is None:
-                fused = cfg["batch_groups"] > 0
+                fused = call.batch_groups > 0
             if fused:
-                res = _PaggLossFunction.apply(cfg, X, ids, codes, sel, target, *params)
+                res = _PaggLossFunction.apply(call, X, ids, codes, sel, target, *params)
             else:
                 from . import optim
-                out = _PaggFunction.apply(cfg, X, ids, codes, sel, *params)
+                out = _PaggFunction.apply(call, X, ids, codes, sel, *params)
                 loss = optim.CrossEntropyLoss()(out, target.to(device=dev, dtype=torch.int64))        # the mean over the S rows
                 if grad_scale is not None:
                     loss = loss * (float(grad_scale) * max(S, 1))
                 res = (loss, out)
         elif _encode is not None:       # (encode(): _encode = whether the paths' final hidden states are wanted)
-            cfg["path_state"] = bool(_encode)
-            res = _PaggEncodeFunction.apply(cfg, X, ids, codes, sel, *params)
+            res = _PaggEncodeFunction.apply(call, X, ids, codes, sel, *params)
         else:
-            res = _PaggFunction.apply(cfg, X, ids, codes, sel, *params)
+            res = _PaggFunction.apply(call, X, ids, codes, sel, *params)
         if guard and S > 0:
             first = self._range_calls == 0
             self._range_calls += 1
             if first or (self._range_calls % RANGE_POLL_EVERY == 0 and self._range_pending is None):
-                self._range_read(cfg, sync=first)
+                self._range_read(call, call.workspace, sync=first)
                 if first and self._range_wide:      # the very first result is not handed out on a range it cannot carry
                     return self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=False, group_slice=group_slice,
                                      target=target, grad_scale=grad_scale, fused=fused, batch_position=batch_position,
-                                     seed=cfg["seed"] if (p > 0 and self.step_state is None) else seed,
-                                     _math=_lib.SEQ_MATH_BF16X3, _encode=_encode)
+                                     seed=seed, _math=_lib.SEQ_MATH_BF16X3, _encode=_encode)
         return res
 
 

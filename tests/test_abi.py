@@ -217,6 +217,51 @@ def test_workspace_query_and_shape_validation():
         modules.workspace_bytes("homo", 100, 16, 256, 3, 10, 833, 4)      # pooling kernels' LDS
 
 
+def test_call_description_names_every_shape_field():
+    """modules.PaggCall spells pn_pagg_shape's fields once, in the struct's order: a new field cannot be left out in Python."""
+    from pathnet_amd import modules
+    assert list(modules.PaggCall.SHAPE_FIELDS) == [f for f, _ in _lib.PaggShape._fields_]
+    call = modules.PaggCall("homo", 100, 16, 128, 3, 10, 40, 4)
+    assert [getattr(call, f) for f in modules.PaggCall.SHAPE_FIELDS[8:11]] == [0, 0, 0] and call.cell is None
+    sh = call.shape()
+    assert [getattr(sh, f) for f, _ in _lib.PaggShape._fields_] == [
+        _lib.VARIANT_HOMO, 100, 16, 128, 3, 10, 40, 4, 0, 0, 0, _lib.CELL_DEFAULT, 0, modules.compact_default(),
+        modules.seq_math_default()]
+    with pytest.raises(AttributeError):
+        call.determinstic = True            # a typo is an error, not a silent default
+    with pytest.raises(AttributeError):
+        call.ws_used = None
+    # read access by name, for backends written against the earlier dict: the same names, and no silent default either
+    assert call["W"] == call.get("W") == 40 and call.get("mask_seq") is None and call.get("S_total", 7) == 0
+    with pytest.raises(AttributeError):
+        call.get("determinstic", False)
+    with pytest.raises(TypeError):
+        modules.PaggCall("homo", 100, 16, 128, 3, 10, 40, 4, seqmath=1)
+
+
+@pytest.mark.parametrize("variant,cell,L", [("hetero", None, 5), ("homo", "gru", 4), ("pagg", None, 4)])
+def test_workspace_bytes_through_the_call_description(variant, cell, L):
+    """the legacy function and the class agree, also with every optional shape field set; the fields change the answer"""
+    from pathnet_amd import modules
+    dims = (variant, 5000, 64, 128, 7, 300, 40, L)
+    plain = modules.workspace_bytes(*dims)
+    assert plain == modules.PaggCall(*dims).workspace_bytes() > 0
+    for kw in (dict(S_total=900, group_begin=150), dict(batch_groups=64), dict(deterministic=True), dict(compact=_lib.COMPACT_ON),
+               dict(compact=_lib.COMPACT_OFF, seq_math=_lib.SEQ_MATH_BF16X3),
+               dict(S_total=900, group_begin=150, batch_groups=64, cell=cell, deterministic=True, compact=_lib.COMPACT_ON,
+                    seq_math=_lib.SEQ_MATH_F16X2)):
+        want = modules.workspace_bytes(*dims, **kw)
+        call = modules.PaggCall(*dims, **kw)
+        assert call.workspace_bytes() == want > 0, kw
+        assert [getattr(call.shape(), f) for f in kw] == [
+            modules._CELL[v] if f == "cell" else int(v) for f, v in kw.items()], kw
+    # batch_groups is decided after construction: what was derived from the shape follows it
+    call = modules.PaggCall(*dims)
+    assert call.workspace_bytes() == plain
+    assert call.set_batch_groups(64).workspace_bytes() == modules.workspace_bytes(*dims, batch_groups=64) != plain
+    assert call.shape().batch_groups == 64
+
+
 def test_context_knobs_defaults_and_retired_names():
     """pn_context_get_knob with a NULL context (no GPU needed) reports the defaults a NULL context runs with
     (include/pathnet_hip.h); the retired A/B knobs are no longer knobs."""

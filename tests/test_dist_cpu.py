@@ -44,8 +44,8 @@ class OracleOps:
         bank, cell = self._names()
         leaf = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()
                 if k not in ("bank_ws", "bank_bs") and v is not None}
-        leaf["bank_w"] = cfg["bank_w"].detach().clone().requires_grad_(True)
-        leaf["bank_b"] = cfg["bank_b"].detach().clone().requires_grad_(True)
+        leaf["bank_w"] = cfg.bank_w.detach().clone().requires_grad_(True)
+        leaf["bank_b"] = cfg.bank_b.detach().clone().requires_grad_(True)
         params = {"fc2.weight": leaf["fc2_w"], "fc2.bias": leaf["fc2_b"],
                   cell + ".weight_ih_l0": leaf["w_ih"], cell + ".weight_hh_l0": leaf["w_hh"],
                   cell + ".bias_ih_l0": leaf["b_ih"], cell + ".bias_hh_l0": leaf["b_hh"]}
@@ -59,20 +59,20 @@ class OracleOps:
         # a rank computes the pooling groups [group_begin, +S) of the step's batch (pn_pagg_shape.S_total / group_begin).
         # homo / PAGG ranks hold their own rows only (index_rows_local); a hetero rank holds the whole batch's index
         # arrays: by definition its rows are those rows of the whole-batch forward
-        drop_seq, drop_cls = cfg.get("mask_seq"), cfg.get("mask_cls")
-        W = cfg["W"]
-        S, S_total, begin = cfg["S"], cfg.get("S_total") or cfg["S"], cfg.get("group_begin", 0)
-        if cfg.get("index_rows_local") and S_total != S:
-            assert cfg["variant"] != "hetero" and len(sel) == S
+        drop_seq, drop_cls = cfg.mask_seq, cfg.mask_cls
+        W = cfg.W
+        S, S_total, begin = cfg.S, cfg.S_total or cfg.S, cfg.group_begin
+        if cfg.index_rows_local and S_total != S:
+            assert cfg.variant != "hetero" and len(sel) == S
             if drop_seq is not None:
                 drop_seq = drop_seq[:, begin * W:(begin + S) * W]
             if drop_cls is not None:
                 drop_cls = drop_cls[begin:begin + S]
-            out = po.forward(cfg["variant"], params, None, ids.numpy(), codes.numpy(), sel.numpy(), W, cfg["L"],
+            out = po.forward(cfg.variant, params, None, ids.numpy(), codes.numpy(), sel.numpy(), W, cfg.L,
                              Xh=Xh, drop_seq=drop_seq, drop_cls=drop_cls)
         else:
             assert len(sel) == S_total
-            out = po.forward(cfg["variant"], params, None, ids.numpy(), codes.numpy(), sel.numpy(), W, cfg["L"],
+            out = po.forward(cfg.variant, params, None, ids.numpy(), codes.numpy(), sel.numpy(), W, cfg.L,
                              Xh=Xh, drop_seq=drop_seq, drop_cls=drop_cls)[begin:begin + S]
         return out.detach(), (out, Xh, leaf)
 

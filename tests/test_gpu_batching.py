@@ -291,9 +291,8 @@ def test_two_contexts_two_host_threads_one_device():
             stream = torch.cuda.Stream()
             out = torch.empty(S, C, device="cuda")
             ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-            cfg = dict(variant="homo", N=N, F=F, H=H, C=C, S=S, W=W, L=L, p_seq=0.0, p_cls=0.0, seed=0, bank_w=fw,
-                       bank_b=fb)
-            a = modules._PaggFunction._args(cfg, X, d_ids, d_codes, d_sel, p)
+            call = modules.PaggCall("homo", N, F, H, C, S, W, L, p_seq=0.0, p_cls=0.0, seed=0, bank_w=fw, bank_b=fb)
+            a = call.args(d_ids, d_codes, d_sel, p, X=X)
             a.out, a.workspace, a.workspace_bytes, a.no_save = out.data_ptr(), ws.data_ptr(), ws.numel(), 1
             stream.wait_stream(torch.cuda.default_stream())
             for _ in range(20):
