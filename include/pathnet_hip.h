@@ -280,6 +280,38 @@ int pn_path_codes(pn_context *ctx, const pn_sampler_tables *tables, int32_t W, i
                   uint8_t *codes /* dev [rows, W, L] */, pn_path_report *report /* dev or NULL */,
                   void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- the synthetic-label generator (pn_census.hip): synthetic_data/gen_cora_syn.cpp, gen_citeseer_syn.cpp ------------
+ * For every node, the walks of walk_len steps binned by the symbols of the nodes they visit, and the most frequent bin.
+ * Added without an ABI bump: four new symbols, no existing struct or signature changed, so a caller built against
+ * version 12 runs unchanged and pn_abi_version keeps answering 12.
+ *
+ * pn_census_lists builds the graph the reference walks on from the m rows (u, v) of a pair file (device int32 arrays):
+ * every row puts v into u's list AND u into v's, duplicates are kept (a multigraph) and a row with u == v adds two
+ * entries to that node's list -- unlike pn_csr_build_device, which removes duplicates and is directed.  off[n+1] int64,
+ * adj[2m] int32, order inside a list unspecified.  The rows are checked as the table builders check theirs: the first
+ * row with a node outside [0, n) fails with PN_ERR_ARG naming it, and that check reads one word back, so this call
+ * synchronises with the stream.  m >= 2^30 (2m entries: the radix sort's range) fails with PN_ERR_ARG.  The workspace
+ * size needs no device. */
+int pn_census_lists_workspace_bytes(int32_t n, int64_t m, int64_t *bytes);
+int pn_census_lists(pn_context *ctx, int32_t n, int64_t m, const int32_t *u, const int32_t *v, int64_t *off, int32_t *adj,
+                    void *workspace, int64_t workspace_bytes, void *stream);
+
+/* counts[i][p] (dev int64 [n, B^k], may be NULL) = the number of walks i -> v1 -> ... -> vk along list entries, with
+ * multiplicity, whose pattern sum_j s[v_j] * B^(k-j) is p (the first step is the most significant digit; B =
+ * num_symbols, k = walk_len).  labels[i] (dev int64 [n], may be NULL) = the SMALLEST pattern among those with the
+ * largest count, so an isolated node gets 0; with counts == NULL the n * B^k table is never written.  At least one of
+ * the two must be given.  symbols: dev uint8 [n] with values in [0, B) (a larger value counts as B - 1), or NULL for
+ * the reference's s[v] = v & 1.  off / adj as pn_census_lists writes them (entries in [0, n) are the caller's promise).
+ * Limits, checked with PN_ERR_ARG: walk_len >= 1, 2 <= num_symbols <= 16, B^k <= 1024.  Counts are exact int64 sums
+ * (the reference counts in int): they stay below 2^63 when (longest list)^k does, which the caller checks.
+ * One launch per level, asynchronous, nothing read back; the workspace holds two level tables of n * B^(k-1) counts
+ * (size from the function below, which needs no device; none is needed for walk_len = 1). */
+int pn_pattern_census_workspace_bytes(int32_t n, int32_t num_symbols, int32_t walk_len, int64_t *bytes);
+int pn_pattern_census(pn_context *ctx, int32_t n, const int64_t *off, const int32_t *adj,
+                      const uint8_t *symbols /* dev [n] or NULL */, int32_t num_symbols, int32_t walk_len,
+                      int64_t *counts /* dev [n, B^k] or NULL */, int64_t *labels /* dev [n] or NULL */, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+
 /* ================================================================================================
  * Path file.  The on-disk interface between sampler and trainer: one line per path,
  * "[v0, v1, ..., v_{L-1}, d0, ..., d_{L-1}]\n"  (writer gen_merw.cpp:189-206; reader

@@ -6,6 +6,7 @@
   pathnet_amd.dist      node sharding across the GPUs of one box (RCCL)
   pathnet_amd.optim     CrossEntropyLoss / Adam of the reference's training step as single launches
   pathnet_amd.trainer   train_fixed_indices with everything resident on the GPU
+  pathnet_amd.synth     path-pattern census: the labels of the synthetic experiment (the gen_*_syn CLI)
 
 Everything computes through csrc/libpathnet_hip.so (C ABI: include/pathnet_hip.h).
 """
@@ -14,5 +15,6 @@ from .modules import PAGG, PathNet, PathNet_homo  # noqa: F401
 from .optim import Adam, CrossEntropyLoss, StepState, backward, cross_entropy  # noqa: F401
 from .sampler import (DRAW_GLIBC_REPLAY, DRAW_PHILOX, MerwSampler, PathAnnotator, PathReport,  # noqa: F401
                       UniformSampler)
+from .synth import PatternCensus  # noqa: F401
 
 __version__ = "0.1.0"

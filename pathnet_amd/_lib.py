@@ -116,6 +116,11 @@ SIGNATURES = {
                                                      ctypes.c_int32, c_i64p]),
     "pn_path_codes": (ctypes.c_int, [vp, ctypes.POINTER(SamplerTables), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp,
                                      vp, vp, vp, ctypes.c_int64, vp]),
+    "pn_census_lists_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_i64p]),
+    "pn_census_lists": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp, vp, ctypes.c_int64, vp]),
+    "pn_pattern_census_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_i64p]),
+    "pn_pattern_census": (ctypes.c_int, [vp, ctypes.c_int32, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp,
+                                         ctypes.c_int64, vp]),
     "pn_paths_write_text": (ctypes.c_int, [ctypes.c_char_p, c_i32p, c_u8p, ctypes.c_int64, ctypes.c_int32,
                                            ctypes.c_int32]),
     "pn_paths_read_text": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, c_i32p, c_u8p, ctypes.c_int64, c_i64p]),
