@@ -2,7 +2,8 @@
 // weight gradient; /root/reference/PathNet_run.py:175, :185-192 / :242-257, :210 / :277 and autograd's backward of them):
 //   gemm_kernel    fp32-input MFMA, 64 x 64 tiles, any operand layout, ReLU gate, row indirection (compact bank rows), K split
 //   gemm3_kernel   fp32 results from the bf16 matrix pipe (three planes, six MFMAs per product), 128 x 128 tiles: large graphs
-//   gemm_finish_kernel / colsum_kernel / transpose_kernel and the launchers (pn_gemm.h).  gfx950 only.
+//   gemm_finish_kernel / colsum_kernel / transpose_kernel and the launchers (pn_gemm.h: a launch is one GemmParams /
+//   Gemm3Params description), and the entry points over them: pn_gemm_f32, pn_linear_forward, pn_linear_backward.  gfx950 only.
 // Split out of pn_pagg.hip in round 6; the kernels are unchanged.
 #include <hip/hip_runtime.h>
 
@@ -24,32 +25,6 @@ namespace pn {
 // ================================================================================================
 constexpr int GEMM_PITCH = 65;
 
-struct GemmParams {
-    const float *A;
-    int64_t sAm, sAk;
-    const float *gateA;
-    const float *B;
-    int64_t sBn, sBk;
-    float *C;
-    int64_t ldc;
-    const float *bias;
-    int M, N, K;
-    int relu, mode;
-    int kchunk;  // K range per blockIdx.z
-    float *rowsum;  // optional [M]: += sum_k A(m,k) (after gating) -- the bias gradient that goes with a dW GEMM
-                    // (PARTIAL: [nz][M], chunk z stores its own sums)
-    // Compact rows (the distance bank over the (node, code) rows a batch touches, GEMM_IND_*): `list` holds the node of every
-    // compact row, the launch covers rows [seg[0], seg[1]) of it -- counts that exist in device memory only; M (or K) given
-    // on the host is their upper bound (it sizes the grid), workgroups past the real count leave at once.
-    const int32_t *seg, *list;
-    int ind;
-    // operand range of the fp16 recurrence taken where the values are produced (run_tables; SeqRange of pn_seq.h, whose first
-    // three words these point to): absmax[0] = atomicMax of the bit patterns of |C| over what this launch stores (after bias /
-    // ReLU); absmax[1] += the biased exponents, absmax[2] += the count of the non-zero 32 x 32 sub-tile maxima of every eighth
-    // workgroup (the spread statistic); clear_word[0..2] are set to 0 by one thread of the launch -- the GEMM in front of the
-    // one that takes the maximum, on the same stream
-    uint32_t *absmax, *clear_word;
-};
 // (IND is a template parameter: as run-time branches in front of the 24 loads of a K tile the row indirection halved the
 //  speed of every GEMM, indirect or not)
 template <bool A_KCONTIG, bool B_KCONTIG, bool GATE, int IND>
@@ -292,27 +267,25 @@ void launch_gemm_variant(hipStream_t stream, dim3 grid, bool ak, bool bk, const 
     }
 }
 
-int launch_gemm(hipStream_t stream, const float *A, int64_t sAm, int64_t sAk, const float *gateA, const float *B,
-                int64_t sBn, int64_t sBk, float *C, int64_t ldc, const float *bias, int M, int N, int K, int relu,
-                int mode, int ksplit, float *rowsum, int ind, const int32_t *seg, const int32_t *list, uint32_t *absmax,
-                uint32_t *clear_word) {
-    if (M <= 0 || N <= 0) return PN_OK;
-    GemmParams p{A, sAm, sAk, gateA, B, sBn, sBk, C, ldc, bias, M, N, K, relu, mode, 0, rowsum, seg, list, ind, absmax, clear_word};
-    if (absmax && (mode != GEMM_STORE || ksplit > 1)) PN_FAIL(PN_ERR_ARG, "internal: gemm absmax needs a storing launch");
+int launch_gemm(hipStream_t stream, const GemmParams &g, int ksplit) {
+    if (g.M <= 0 || g.N <= 0) return PN_OK;
+    GemmParams p = g;
+    const int M = p.M, N = p.N, K = p.K;
+    if (p.absmax && (p.mode != GEMM_STORE || ksplit > 1)) PN_FAIL(PN_ERR_ARG, "internal: gemm absmax needs a storing launch");
     if (ksplit < 1) ksplit = 1;
-    if (mode != GEMM_ATOMIC && mode != GEMM_PARTIAL) ksplit = 1;
+    if (p.mode != GEMM_ATOMIC && p.mode != GEMM_PARTIAL) ksplit = 1;
     int kchunk = (K + ksplit - 1) / ksplit;
     kchunk = ((kchunk + GEMM_KT - 1) / GEMM_KT) * GEMM_KT;
     if (kchunk < GEMM_KT) kchunk = GEMM_KT;
     p.kchunk = kchunk;
     const int nz = K > 0 ? (K + kchunk - 1) / kchunk : 1;
     if (K <= 0 || M <= 0 || N <= 0) PN_FAIL(PN_ERR_ARG, "gemm: empty problem M=%d N=%d K=%d", M, N, K);
-    const bool ak = (sAk == 1), bk = (sBk == 1);
+    const bool ak = (p.sAk == 1), bk = (p.sBk == 1);
     dim3 grid((N + GEMM_BN - 1) / GEMM_BN, (M + GEMM_BM - 1) / GEMM_BM, nz);
     // a short reduction over K-contiguous operands, stored in one piece: every K tile's loads in flight at once (gemm_k128_kernel)
-    if (ak && bk && !gateA && ind == GEMM_IND_NONE && mode == GEMM_STORE && nz == 1 && K <= 4 * GEMM_KT && !rowsum)
+    if (ak && bk && !p.gateA && p.ind == GEMM_IND_NONE && p.mode == GEMM_STORE && nz == 1 && K <= 4 * GEMM_KT && !p.rowsum)
         hipLaunchKernelGGL(gemm_k128_kernel, grid, dim3(256), 0, stream, p);
-    else if (gateA)
+    else if (p.gateA)
         launch_gemm_variant<true>(stream, grid, ak, bk, p);
     else
         launch_gemm_variant<false>(stream, grid, ak, bk, p);
@@ -330,22 +303,6 @@ int launch_gemm(hipStream_t stream, const float *A, int64_t sAm, int64_t sAk, co
 //   workgroups per CU.
 // ================================================================================================
 constexpr int G3_PITCH = 80, G3_PLANE = 128 * G3_PITCH;
-struct Gemm3Params {
-    const float *A;
-    int64_t lda;
-    const float *B;
-    int64_t ldb;
-    float *C;
-    int64_t ldc;
-    const float *bias;
-    int M, N, K;
-    // node-level GEMMs over row lists (the compact distance bank, GEMM_IND_A_ROWS / GEMM_IND_C_ROWS as in gemm_kernel: the
-    // row count lives in device memory, M bounds it), a ReLU gate on A (element kept where gate > 0, same indexing as A),
-    // ReLU on the result, C += instead of C =
-    const float *gate;
-    const int32_t *seg, *list;
-    int relu, add;
-};
 
 template <int IND, bool GATE>
 __global__ __launch_bounds__(256, 2) void gemm3_kernel(Gemm3Params p) {
@@ -467,13 +424,11 @@ __global__ __launch_bounds__(256, 2) void gemm3_kernel(Gemm3Params p) {
     }
 }
 
-int launch_gemm3(hipStream_t stream, const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc,
-                 const float *bias, int M, int N, int K, int relu, int add, const float *gate, int ind, const int32_t *seg,
-                 const int32_t *list) {
-    if (M <= 0 || N <= 0) return PN_OK;
-    if (K < G3_KT || K % G3_KT != 0) PN_FAIL(PN_ERR_ARG, "gemm3: K=%d is not a multiple of %d", K, G3_KT);
-    Gemm3Params p{A, lda, B, ldb, C, ldc, bias, M, N, K, gate, seg, list, relu, add};
-    const dim3 grid((N + G3_BN - 1) / G3_BN, (M + G3_BM - 1) / G3_BM);
+int launch_gemm3(hipStream_t stream, const Gemm3Params &p, int ind) {
+    if (p.M <= 0 || p.N <= 0) return PN_OK;
+    if (p.K < G3_KT || p.K % G3_KT != 0) PN_FAIL(PN_ERR_ARG, "gemm3: K=%d is not a multiple of %d", p.K, G3_KT);
+    const float *gate = p.gate;
+    const dim3 grid((p.N + G3_BN - 1) / G3_BN, (p.M + G3_BM - 1) / G3_BM);
     if (ind == GEMM_IND_A_ROWS && !gate)
         hipLaunchKernelGGL((gemm3_kernel<GEMM_IND_A_ROWS, false>), grid, dim3(256), 0, stream, p);
     else if (ind == GEMM_IND_C_ROWS && gate)
@@ -587,22 +542,20 @@ int gemm_split_count(int M, int N, int K) {
     return nz < 1 ? 1 : (int)nz;
 }
 
-int launch_gemm_split(hipStream_t stream, const float *A, int64_t sAm, int64_t sAk, const float *gateA, const float *B,
-                      int64_t sBn, int64_t sBk, float *C, int64_t ldc, const float *bias, int M, int N, int K, int relu,
-                      int mode, float *partial, uint32_t *clear_word) {
+int launch_gemm_split(hipStream_t stream, const GemmParams &g, float *partial) {
+    const int M = g.M, N = g.N, K = g.K;
     int nz = gemm_split_count(M, N, K);
-    if (nz <= 1 || !partial || M <= 0 || N <= 0)
-        return launch_gemm(stream, A, sAm, sAk, gateA, B, sBn, sBk, C, ldc, bias, M, N, K, relu, mode, 1, nullptr, GEMM_IND_NONE,
-                           nullptr, nullptr, nullptr, clear_word);
+    if (nz <= 1 || !partial || M <= 0 || N <= 0) return launch_gemm(stream, g);
     int kchunk = (K + nz - 1) / nz;
     kchunk = (kchunk + GEMM_KT - 1) / GEMM_KT * GEMM_KT;
     nz = (K + kchunk - 1) / kchunk;
-    if (int rc = launch_gemm(stream, A, sAm, sAk, gateA, B, sBn, sBk, partial, N, nullptr, M, N, K, 0, GEMM_PARTIAL, nz, nullptr,
-                             GEMM_IND_NONE, nullptr, nullptr, nullptr, clear_word))
-        return rc;
+    GemmParams p = g;           // the chunk sums: raw, to `partial`; bias / ReLU / accumulate are the finish launch's
+    p.C = partial, p.ldc = N;
+    p.bias = nullptr, p.relu = 0, p.mode = GEMM_PARTIAL;
+    if (int rc = launch_gemm(stream, p, nz)) return rc;
     const int64_t n = (int64_t)M * N;
     hipLaunchKernelGGL(gemm_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, partial, nz, M, N,
-                       bias, relu, mode, C, ldc);
+                       g.bias, g.relu, g.mode, g.C, g.ldc);
     PN_CHECK_HIP(hipGetLastError());
     return PN_OK;
 }
@@ -610,21 +563,22 @@ int launch_gemm_split(hipStream_t stream, const float *A, int64_t sAm, int64_t s
 // ---- deterministic weight-gradient GEMM (pn_pagg_shape.deterministic): C += A . B^T and rowsum += row sums of A with the
 // reduction cut into at most DET_MAX_SPLIT chunks whose sums are stored ([nz][M][N], [nz][M]) and added up in chunk order
 // -- where the default path lets the chunks race with atomics.  C and rowsum accumulate (micro-batches).
-int launch_gemm_det(hipStream_t stream, const float *A, int64_t sAm, int64_t sAk, const float *gateA, const float *B,
-                    int64_t sBn, int64_t sBk, float *C, int64_t ldc, int M, int N, int K, int ksplit, float *rowsum,
-                    float *partial, int ind, const int32_t *seg, const int32_t *list) {
+int launch_gemm_det(hipStream_t stream, const GemmParams &g, int ksplit, float *partial) {
+    const int M = g.M, N = g.N, K = g.K;
     if (M <= 0 || N <= 0 || K <= 0) return PN_OK;
     int nz = std::max(1, std::min(ksplit, DET_MAX_SPLIT));
     int kchunk = (K + nz - 1) / nz;
     kchunk = std::max(GEMM_KT, (kchunk + GEMM_KT - 1) / GEMM_KT * GEMM_KT);
     nz = (K + kchunk - 1) / kchunk;             // (= the grid's z extent launch_gemm derives from the same numbers)
-    float *rs_part = rowsum ? partial + (size_t)nz * M * N : nullptr;
-    if (int rc = launch_gemm(stream, A, sAm, sAk, gateA, B, sBn, sBk, partial, N, nullptr, M, N, K, 0, GEMM_PARTIAL, nz,
-                             rs_part, ind, seg, list))
-        return rc;
+    float *rs_part = g.rowsum ? partial + (size_t)nz * M * N : nullptr;
+    GemmParams p = g;           // the chunk sums of C and of the row sums, to `partial`
+    p.C = partial, p.ldc = N;
+    p.bias = nullptr, p.relu = 0, p.mode = GEMM_PARTIAL;
+    p.rowsum = rs_part;
+    if (int rc = launch_gemm(stream, p, nz)) return rc;
     const int64_t n = (int64_t)M * N;
     hipLaunchKernelGGL(gemm_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, partial, nz, M, N,
-                       (const float *)nullptr, 0, (int)GEMM_ADD, C, ldc, (const float *)rs_part, rowsum);
+                       (const float *)nullptr, 0, (int)GEMM_ADD, g.C, g.ldc, (const float *)rs_part, g.rowsum);
     PN_CHECK_HIP(hipGetLastError());
     return PN_OK;
 }
@@ -636,3 +590,75 @@ int launch_transpose(hipStream_t stream, const float *in, int R, int C, float *o
 }
 
 }  // namespace pn
+
+// ---- the node-level GEMMs as entry points of their own (include/pathnet_hip.h) -------------------------------------------
+using namespace pn;
+
+extern "C" {
+
+int pn_gemm_f32(const float *A, int64_t sAm, int64_t sAk, const float *B, int64_t sBn, int64_t sBk, float *C,
+                int64_t ldc, const float *bias, int32_t M, int32_t N, int32_t K, int32_t relu, void *stream_) {
+    if (!A || !B || !C || M < 0 || N < 0 || K < 0) PN_FAIL(PN_ERR_ARG, "pn_gemm_f32: bad argument");
+    if ((sAm != 1 && sAk != 1) || (sBn != 1 && sBk != 1)) PN_FAIL(PN_ERR_ARG, "pn_gemm_f32: one stride per operand must be 1");
+    GemmParams g{};         // (the caller's strides: none of the three layouts)
+    g.A = A, g.sAm = sAm, g.sAk = sAk;
+    g.B = B, g.sBn = sBn, g.sBk = sBk;
+    g.C = C, g.ldc = ldc;
+    g.bias = bias;
+    g.M = M, g.N = N, g.K = K;
+    g.relu = relu;
+    return launch_gemm((hipStream_t)stream_, g);
+}
+
+int pn_linear_forward(pn_context *ctx, const float *X, const float *W, const float *b, int32_t rows, int32_t in_f,
+                      int32_t out_f, int32_t relu, float *Y, void *workspace, int64_t workspace_bytes, void *stream_) {
+    static_assert(PN_LINEAR_SPLIT_MAX == GEMM_MAX_SPLIT, "header and kernel agree on the split bound");
+    if (!X || !W || !Y || rows < 0 || in_f < 1 || out_f < 1) PN_FAIL(PN_ERR_ARG, "pn_linear_forward: bad argument");
+    if (int rc = context_check_device(ctx)) return rc;
+    if (rows == 0) return PN_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool split = workspace && workspace_bytes >= (int64_t)GEMM_MAX_SPLIT * rows * out_f * (int64_t)sizeof(float);
+    StageTimer tm(ctx, ST_FC0, stream);
+    GemmParams g = gemm_linear_fwd(X, in_f, W, in_f, Y, out_f, rows, in_f, out_f);
+    g.bias = b;
+    g.relu = relu;
+    return launch_gemm_split(stream, g, split ? reinterpret_cast<float *>(workspace) : nullptr);
+}
+
+int pn_linear_backward(pn_context *ctx, const float *dY, const float *gate, const float *X, const float *W, int32_t rows,
+                       int32_t in_f, int32_t out_f, float *g_W, float *g_b, float *g_X, void *workspace,
+                       int64_t workspace_bytes, void *stream_) {
+    static_assert(PN_LINEAR_BWD_SPLIT_MAX == DET_MAX_SPLIT, "header and kernel agree on the split bound");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!dY || rows < 0 || in_f < 1 || out_f < 1) PN_FAIL(PN_ERR_ARG, "pn_linear_backward: bad argument");
+    if (int rc = context_check_device(ctx)) return rc;
+    StageTimer tm(ctx, ST_FC0_BWD, stream);
+    if (g_W && !X) PN_FAIL(PN_ERR_ARG, "pn_linear_backward: g_W needs X");
+    ZeroFill zf{ctx};       // both are accumulated with atomics: one zero-fill launch for the two, inside this stage's bracket
+    if (int rc = zf.add(g_W, (size_t)out_f * in_f)) return rc;
+    if (int rc = zf.add(g_b, (size_t)out_f)) return rc;
+    if (int rc = zf.flush(stream, false)) return rc;
+    if (rows == 0) return PN_OK;
+    // with a workspace: chunk sums added in a fixed order (bitwise reproducible); without: chunks race with atomics
+    const bool det = workspace && workspace_bytes >= (int64_t)(det_gemm_floats(out_f, in_f) * sizeof(float));
+    GemmParams g = gemm_weight_grad(dY, out_f, X, in_f, g_W, in_f, rows, in_f, out_f);
+    g.gateA = gate;
+    g.rowsum = g_b;         // g_b rides along as the row sums of the (gated) A operand dY^T
+    g.mode = GEMM_ATOMIC;
+    if (g_W && det) {
+        if (int rc = launch_gemm_det(stream, g, (rows + 255) / 256, reinterpret_cast<float *>(workspace))) return rc;
+    } else if (g_W) {
+        if (int rc = launch_gemm(stream, g, (rows + 255) / 256)) return rc;
+    } else if (g_b) {
+        if (int rc = launch_colsum(stream, dY, gate, out_f, rows, out_f, g_b, workspace != nullptr)) return rc;
+    }
+    if (g_X) {
+        if (!W) PN_FAIL(PN_ERR_ARG, "pn_linear_backward: g_X needs W");
+        GemmParams gx = gemm_input_grad(dY, out_f, W, in_f, g_X, in_f, rows, in_f, out_f);
+        gx.gateA = gate;
+        if (int rc = launch_gemm(stream, gx)) return rc;
+    }
+    return PN_OK;
+}
+
+}  // extern "C"

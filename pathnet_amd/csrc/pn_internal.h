@@ -92,6 +92,27 @@ struct StageTimer {
     void *stream;
 };
 
+// ---- every buffer a backward accumulates into (atomics / += / split-K), cleared by ONE launch (zero_kernel, pn_pagg.hip) ----
+struct ZeroList {
+    float *ptr[12];
+    unsigned long long count[12];
+    int n;
+};
+struct ZeroFill {
+    pn_context *ctx;
+    ZeroList zl{};
+    int add(float *ptr, size_t count) {
+        if (!ptr || !count) return PN_OK;
+        if (zl.n >= (int)(sizeof zl.ptr / sizeof zl.ptr[0])) PN_FAIL(PN_ERR_ARG, "internal: zero list overflow");
+        zl.ptr[zl.n] = ptr;
+        zl.count[zl.n] = count;
+        zl.n++;
+        return PN_OK;
+    }
+    // timed: under a stage bracket of its own (ST_ZERO_FILL); false where the caller's bracket covers the launch
+    int flush(void *stream, bool timed = true);
+};
+
 // softmax cross entropy of `rows` rows (pn_train.hip): loss[0] += scale * sum of the rows' losses, g_logits (or null) =
 // (softmax - onehot) * scale.  pn_cross_entropy = zero-fill + this with scale = 1 / rows.
 // overwrite: loss[0] = ... instead of += (the zero fill, when one is needed at all, is issued here)

@@ -1358,12 +1358,7 @@ __global__ __launch_bounds__(256) void pad_rows_kernel(const float *__restrict__
     reinterpret_cast<float4 *>(out)[i] = v;
 }
 
-// zero-fill of up to 12 buffers in one launch (the accumulated gradients of a backward)
-struct ZeroList {
-    float *ptr[12];
-    unsigned long long count[12];
-    int n;
-};
+// zero-fill of up to 12 buffers in one launch (the accumulated gradients of a backward; ZeroList / ZeroFill: pn_internal.h)
 __global__ __launch_bounds__(256) void zero_kernel(ZeroList z) {
     for (int b = 0; b < z.n; b++) {
         float *p = z.ptr[b];
@@ -1389,6 +1384,7 @@ enum { CELL_LSTM = 1, CELL_RNN = 2, CELL_GRU = 3, CELL_MEAN = 4, CELL_SUM = 5 };
 struct Dims {
     int variant, N, F, H, C, S, W, L, G, SV;    // G: gate slots of the recurrent kernels (4: LSTM and GRU, 1: RNN, 0: mean / sum)
     int cell, Gw;                               // cell kind; Gw: gates of the caller's weight tensors (4, 1, 3, 0)
+    int gru;                                    // 1: the cell is a GRU (its three gates are packed into the four slots)
     bool generic;                               // H > 256: the step-by-step recurrence (gen_*_kernel) instead of the fused kernels
     int S_total, group_begin;
     int Sb;             // pooling groups per micro-batch
@@ -1425,7 +1421,8 @@ int make_dims(const pn_pagg_shape &s, Dims &d) {
     d.N = s.N, d.F = s.F, d.H = s.H, d.C = s.C, d.S = s.S, d.W = s.W, d.L = s.L;
     d.cell = s.cell ? s.cell : (s.variant == PN_VARIANT_PAGG ? CELL_RNN : CELL_LSTM);
     d.G = d.cell == CELL_RNN ? 1 : (d.cell == CELL_LSTM || d.cell == CELL_GRU) ? 4 : 0;
-    d.Gw = d.cell == CELL_GRU ? 3 : d.G;
+    d.gru = d.cell == CELL_GRU ? 1 : 0;
+    d.Gw = d.gru ? 3 : d.G;
     d.SV = d.G == 4 ? 5 : 1;
     d.generic = s.H > 256 && d.G > 0;
     d.S_total = S_total;
@@ -1591,29 +1588,6 @@ struct JoinGuard {
     ~JoinGuard() { (void)join(); }
 };
 
-// every buffer a backward accumulates into (atomics / += / split-K), cleared by ONE launch
-struct ZeroFill {
-    pn_context *ctx;
-    ZeroList zl{};
-    int add(float *ptr, size_t count) {
-        if (!ptr || !count) return PN_OK;
-        if (zl.n >= (int)(sizeof zl.ptr / sizeof zl.ptr[0])) PN_FAIL(PN_ERR_ARG, "internal: zero list overflow");
-        zl.ptr[zl.n] = ptr;
-        zl.count[zl.n] = count;
-        zl.n++;
-        return PN_OK;
-    }
-    int flush(hipStream_t s) {
-        if (!zl.n) return PN_OK;
-        StageTimer tm(ctx, ST_ZERO_FILL, s);       // (d Z and d Xh are the bulk: rows of the graph, not paths)
-        hipLaunchKernelGGL(zero_kernel, dim3(512), dim3(256), 0, s, zl);
-        PN_CHECK_HIP(hipGetLastError());
-        zl.n = 0;
-        return PN_OK;
-    }
-};
-
-
 // ---- one aggregator call, resolved: shapes, workspace pointers, and the stages that run once per micro-batch ---------
 struct Call {
     pn_context *ctx;
@@ -1652,10 +1626,15 @@ int resolve_call(Call &c, pn_context *ctx, const pn_pagg_args *a, hipStream_t st
     return PN_OK;
 }
 
+inline PlanDims plan_dims(const Call &c) {
+    const Dims &d = c.d;
+    return PlanDims{d.S_total, d.W, d.L, d.N, d.P_total, c.a->index_rows_local ? (int64_t)d.group_begin * d.W : 0};
+}
+
 int run_plan(const Call &c, hipStream_t s, int b) {
     const Dims &d = c.d;
     const int64_t count = (int64_t)c.groups(b) * d.W, n = count * d.L;
-    const PlanDims pd{d.S_total, d.W, d.L, d.N, d.P_total, c.a->index_rows_local ? (int64_t)d.group_begin * d.W : 0};
+    const PlanDims pd = plan_dims(c);
     hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d.variant, c.a->ids, c.a->codes,
                        pd, c.group0(b) * d.W, count, d.compact ? c.at<const int32_t>(c.w.rank) : nullptr,
                        c.at<int32_t>(c.w.rowidx), c.at<int32_t>(c.w.egoidx), c.at<int32_t>(c.w.slotof));
@@ -1669,7 +1648,7 @@ int run_compact_rows(const Call &c, hipStream_t s) {
     const bool het = d.variant == PN_VARIANT_HETERO;
     const int64_t slot0 = het ? 0 : (int64_t)d.group_begin * d.W, count = (int64_t)(het ? d.S_total : d.S) * d.W, n = count * d.L;
     const int64_t rows = (int64_t)d.N * d.L;
-    const PlanDims pd{d.S_total, d.W, d.L, d.N, d.P_total, c.a->index_rows_local ? (int64_t)d.group_begin * d.W : 0};
+    const PlanDims pd = plan_dims(c);
     uint8_t *flags = c.at<uint8_t>(c.w.flags);
     PN_CHECK_HIP(hipMemsetAsync(flags, 0, (size_t)rows, s));
     hipLaunchKernelGGL(mark_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d.variant, c.a->ids, c.a->codes, pd,
@@ -1725,9 +1704,10 @@ int run_seq_fwd_generic(const Call &c, int b, bool save) {
         hipLaunchKernelGGL(gen_x_kernel, dim3(bx), dim3(256), 0, c.stream, gp);
         PN_CHECK_HIP(hipGetLastError());
         // pre[q, :] = [x_t | h_{t-1}] . Wcat^T + b      (step 0: h_{-1} = 0, the x half of K suffices)
-        if (int rc = launch_gemm3(c.stream, gp.xh + (size_t)t * 2 * H, (int64_t)d.L * 2 * H, Wcat, 2 * H,
-                                  gp.pre + (size_t)t * GH, (int64_t)d.L * GH, gp.biasc, P, GH, t == 0 ? H : 2 * H))
-            return rc;
+        GemmParams g = gemm_linear_fwd(gp.xh + (size_t)t * 2 * H, (int64_t)d.L * 2 * H, Wcat, 2 * H, gp.pre + (size_t)t * GH,
+                                       (int64_t)d.L * GH, P, t == 0 ? H : 2 * H, GH);
+        g.bias = gp.biasc;
+        if (int rc = launch_gemm3(c.stream, gemm3_of(g))) return rc;
         hipLaunchKernelGGL(gen_cell_fwd_kernel, dim3(be), dim3(256), 0, c.stream, gp);
         PN_CHECK_HIP(hipGetLastError());
     }
@@ -1753,9 +1733,10 @@ int run_seq_bwd_generic(const Call &c, int b) {
             hipLaunchKernelGGL(gen_cell_bwd_kernel, dim3(be), dim3(256), 0, c.stream, gp);
             PN_CHECK_HIP(hipGetLastError());
             // [dx_t | dh_{t-1}] = dG_t . [W_ih | W_hh]      (step 0: the dx half suffices)
-            if (int rc = launch_gemm3(c.stream, gp.pre + (size_t)t * GH, (int64_t)d.L * GH, WcatT, GH, gx, 2 * H, nullptr, P,
-                                      t == 0 ? H : 2 * H, GH))
-                return rc;
+            // (a forward through the transposed weights WcatT [2 H, G H])
+            const GemmParams g = gemm_linear_fwd(gp.pre + (size_t)t * GH, (int64_t)d.L * GH, WcatT, GH, gx, 2 * H, P, GH,
+                                                 t == 0 ? H : 2 * H);
+            if (int rc = launch_gemm3(c.stream, gemm3_of(g))) return rc;
             hipLaunchKernelGGL(gen_scatter_kernel, dim3(bx), dim3(256), 0, c.stream, gp);
             PN_CHECK_HIP(hipGetLastError());
         }
@@ -1780,7 +1761,7 @@ int run_pack_fwd(const Call &c, hipStream_t s) {
     if (d.generic) {
         const int64_t n = (int64_t)d.G * d.H * 2 * d.H;
         hipLaunchKernelGGL(gen_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c.a->w_ih, c.a->w_hh,
-                           c.a->b_ih, c.a->b_hh, d.H, d.G, d.cell == CELL_GRU ? 1 : 0, c.at<float>(c.w.Wp),
+                           c.a->b_ih, c.a->b_hh, d.H, d.G, d.gru, c.at<float>(c.w.Wp),
                            c.at<float>(c.w.WpT), c.at<float>(c.w.biasc));
         PN_CHECK_HIP(hipGetLastError());
         return PN_OK;
@@ -1790,11 +1771,11 @@ int run_pack_fwd(const Call &c, hipStream_t s) {
         // (it also clears the slots this call's atomicMax launches add to; a reused dense bank keeps its range.x.)  A training
         // forward packs the BPTT's planes in the same launch, on the side stream under fc0 / the bank: the backward that follows
         // on this workspace then starts on its first real kernel (an inference forward uses that slot for Wcat)
-        return launch_pack_fb(s, c.a->w_ih, c.a->w_hh, c.a->b_ih, c.a->b_hh, d.H, d.G, d.Gw, d.cell == CELL_GRU ? 1 : 0,
+        return launch_pack_fb(s, c.a->w_ih, c.a->w_hh, c.a->b_ih, c.a->b_hh, d.H, d.G, d.Gw, d.gru,
                               (d.compact || c.a->reuse_tables != 1) && !bank_epilogue_range(c), rg, c.at<void>(c.w.wmax),
                               c.at<void>(c.w.Wp), c.at<float>(c.w.biasc), c.a->no_save ? nullptr : c.at<void>(c.w.WpT));
     }
-    return launch_pack_fwd3(s, c.a->w_ih, c.a->w_hh, c.a->b_ih, c.a->b_hh, d.H, d.G, d.cell == CELL_GRU ? 1 : 0, c.at<void>(c.w.Wp),
+    return launch_pack_fwd3(s, c.a->w_ih, c.a->w_hh, c.a->b_ih, c.a->b_hh, d.H, d.G, d.gru, c.at<void>(c.w.Wp),
                             c.at<float>(c.w.biasc));
 }
 
@@ -1981,12 +1962,13 @@ int run_tables(const Call &c, JoinGuard &joiner, ZeroFill *zero_fill = nullptr) 
         // fc0 (+ReLU for HOMO): Xh = X . fc0_w^T + fc0_b
         if (!a->Xh_in) {
             StageTimer tm(ctx, ST_FC0, stream);
+            GemmParams g = gemm_linear_fwd(a->X, d.F, a->fc0_w, d.F, c.at<float>(c.w.Xh), H, d.N, d.F, H);
+            g.bias = a->fc0_b;
+            g.relu = homo;
+            g.clear_word = epi_range ? &c.at<SeqRange>(c.w.range)->x : nullptr;     // (epi_range: never with gemm3)
             if (gemm3_pays(c.ctx, d.N, H, d.F, G3_FC0)) {          // large graphs: fp32 results from the bf16 matrix pipe (six MFMAs per product)
-                if (int rc = launch_gemm3(stream, a->X, d.F, a->fc0_w, d.F, c.at<float>(c.w.Xh), H, a->fc0_b, d.N, H, d.F, homo))
-                    return rc;
-            } else if (int rc = launch_gemm_split(stream, a->X, d.F, 1, nullptr, a->fc0_w, d.F, 1, c.at<float>(c.w.Xh), H,
-                                                  a->fc0_b, d.N, H, d.F, homo, GEMM_STORE, c.at<float>(c.w.gpart),
-                                                  epi_range ? &c.at<SeqRange>(c.w.range)->x : nullptr))
+                if (int rc = launch_gemm3(stream, gemm3_of(g))) return rc;
+            } else if (int rc = launch_gemm_split(stream, g, c.at<float>(c.w.gpart)))
                 return rc;
         }
     }
@@ -1999,24 +1981,27 @@ int run_tables(const Call &c, JoinGuard &joiner, ZeroFill *zero_fill = nullptr) 
         StageTimer tm(ctx, ST_BANK, stream);
         const int mmax = (int)std::min<int64_t>(d.N, d.ZR);
         for (int code = 0; code < L; code++) {
+            GemmParams g = gemm_linear_fwd(c.Xh, H, a->bank_w + (size_t)code * H * H, H, c.Z, H, mmax, H, H);
+            g.bias = a->bank_b + (size_t)code * H;
+            g.relu = homo;
+            g.ind = GEMM_IND_A_ROWS;
+            g.seg = c.at<const int32_t>(c.w.seg) + code;
+            g.list = c.at<const int32_t>(c.w.list);
             if (gemm3_pays(c.ctx, mmax, H, H, G3_BANK)) {
-                if (int rc = launch_gemm3(stream, c.Xh, H, a->bank_w + (size_t)code * H * H, H, c.Z, H, a->bank_b + (size_t)code * H,
-                                          mmax, H, H, homo, 0, nullptr, GEMM_IND_A_ROWS, c.at<const int32_t>(c.w.seg) + code,
-                                          c.at<const int32_t>(c.w.list)))
-                    return rc;
-            } else if (int rc = launch_gemm(stream, c.Xh, H, 1, nullptr, a->bank_w + (size_t)code * H * H, H, 1, c.Z, H,
-                                            a->bank_b + (size_t)code * H, mmax, H, H, homo, GEMM_STORE, 1, nullptr,
-                                            GEMM_IND_A_ROWS, c.at<const int32_t>(c.w.seg) + code, c.at<const int32_t>(c.w.list)))
+                if (int rc = launch_gemm3(stream, gemm3_of(g), g.ind)) return rc;
+            } else if (int rc = launch_gemm(stream, g))
                 return rc;
         }
     } else if (a->reuse_tables != 1) {      // (1: the dense Z of the previous forward is still valid; 2: only Xh is)
         // distance bank over every node: Z[v, d, :] = act(Xh[v] . bank_w[d]^T + bank_b[d])
         StageTimer tm(ctx, ST_BANK, stream);
+        GemmParams g = gemm_linear_fwd(c.Xh, H, a->bank_w, H, c.Z, (int64_t)L * H, d.N, H, L * H);
+        g.bias = a->bank_b;
+        g.relu = homo;
+        g.absmax = epi_range ? &c.at<SeqRange>(c.w.range)->x : nullptr;         // (epi_range: never with gemm3)
         if (gemm3_pays(c.ctx, d.N, L * H, H, G3_BANK)) {
-            if (int rc = launch_gemm3(stream, c.Xh, H, a->bank_w, H, c.Z, (int64_t)L * H, a->bank_b, d.N, L * H, H, homo)) return rc;
-        } else if (int rc = launch_gemm(stream, c.Xh, H, 1, nullptr, a->bank_w, H, 1, c.Z, (int64_t)L * H, a->bank_b, d.N,
-                                        L * H, H, homo, GEMM_STORE, 1, nullptr, GEMM_IND_NONE, nullptr, nullptr,
-                                        epi_range ? &c.at<SeqRange>(c.w.range)->x : nullptr))
+            if (int rc = launch_gemm3(stream, gemm3_of(g))) return rc;
+        } else if (int rc = launch_gemm(stream, g))
             return rc;
     }
     // the fp16 recurrence scales the gathered rows by a power of two taken from the largest |Z| of the rows just computed
@@ -2037,14 +2022,15 @@ int run_tables(const Call &c, JoinGuard &joiner, ZeroFill *zero_fill = nullptr) 
         const int64_t n = (int64_t)GH * 2 * H;
         float *Wcat = c.at<float>(c.w.WpT);
         hipLaunchKernelGGL(gen_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a->w_ih, a->w_hh, a->b_ih,
-                           a->b_hh, H, d.G, d.cell == CELL_GRU ? 1 : 0, Wcat, (float *)nullptr, c.at<float>(c.w.biasc));
+                           a->b_hh, H, d.G, d.gru, Wcat, (float *)nullptr, c.at<float>(c.w.biasc));
         PN_CHECK_HIP(hipGetLastError());
         const int M = (int)d.ZR;
         const bool g3 = H % G3_KT == 0 && (int64_t)((M + G3_BM - 1) / G3_BM) * ((GH + G3_BN - 1) / G3_BN) >= 256;
+        GemmParams g = gemm_linear_fwd(c.Z, H, Wcat, 2 * H, c.at<float>(c.w.saved), GH, M, H, GH);
+        g.bias = c.at<float>(c.w.biasc);
         if (g3) {
-            if (int rc = launch_gemm3(stream, c.Z, H, Wcat, 2 * H, c.at<float>(c.w.saved), GH, c.at<float>(c.w.biasc), M, GH, H)) return rc;
-        } else if (int rc = launch_gemm(stream, c.Z, H, 1, nullptr, Wcat, 2 * H, 1, c.at<float>(c.w.saved), GH, c.at<float>(c.w.biasc), M,
-                                        GH, H, 0, GEMM_STORE, 1))
+            if (int rc = launch_gemm3(stream, gemm3_of(g))) return rc;
+        } else if (int rc = launch_gemm(stream, g))
             return rc;
     }
     return PN_OK;
@@ -2180,14 +2166,13 @@ int run_fc2_grad(const Call &c, int b, JoinGuard &joiner, hipStream_t s, const f
     }
     if (g_out) {        // (no g_out: only the embedding is differentiated, g_fc2_* keep the backward's zero fill)
         StageTimer tm(c.ctx, ST_FC2_GRAD, s);
+        GemmParams g = gemm_weight_grad(g_out, d.C, c.at<float>(c.w.layer1), 2 * H, a->g_fc2_w, 2 * H, Sb, 2 * H, d.C);
+        g.rowsum = a->g_fc2_b;          // g_fc2_b = row sums of the A operand (g_out^T)
+        g.mode = GEMM_ATOMIC;
         if (a->g_fc2_w && d.det) {
-            if (int rc = launch_gemm_det(s, g_out, 1, d.C, nullptr, c.at<float>(c.w.layer1), 1, 2 * H, a->g_fc2_w, 2 * H, d.C,
-                                         2 * H, Sb, (Sb + 127) / 128, a->g_fc2_b, c.at<float>(c.w.dgemm)))
-                return rc;
-        } else if (a->g_fc2_w) {        // g_fc2_b = row sums of the A operand (g_out^T)
-            if (int rc = launch_gemm(s, g_out, 1, d.C, nullptr, c.at<float>(c.w.layer1), 1, 2 * H, a->g_fc2_w, 2 * H, nullptr,
-                                     d.C, 2 * H, Sb, 0, GEMM_ATOMIC, (Sb + 127) / 128, a->g_fc2_b))
-                return rc;
+            if (int rc = launch_gemm_det(s, g, (Sb + 127) / 128, c.at<float>(c.w.dgemm))) return rc;
+        } else if (a->g_fc2_w) {
+            if (int rc = launch_gemm(s, g, (Sb + 127) / 128)) return rc;
         } else if (a->g_fc2_b) {
             if (int rc = launch_colsum(s, g_out, nullptr, d.C, Sb, d.C, a->g_fc2_b, d.det)) return rc;
         }
@@ -2393,7 +2378,7 @@ int run_wgrad(const Call &c, int b, JoinGuard &joiner) {
         } else {
             if (int rc = launch_wgrad3(c.ctx, ws, wp, nz_used)) return rc;
         }
-        if (int rc = launch_wgrad_reduce(ws, wp.part_w, wp.part_b, nz_red, GH, H, b > 0 ? 1 : 0, d.cell == CELL_GRU ? 1 : 0,
+        if (int rc = launch_wgrad_reduce(ws, wp.part_w, wp.part_b, nz_red, GH, H, b > 0 ? 1 : 0, d.gru,
                                          a->g_w_ih, a->g_w_hh, a->g_b_ih, a->g_b_hh))
             return rc;
     }
@@ -2424,54 +2409,64 @@ int run_bank_bwd(const Call &c, float *dXh, const float *dZ) {
         if (g3)             // bank_w[code] [out, in] -> [in, out]: the reduction index (out) contiguous
             for (int code = 0; code < L; code++)
                 launch_transpose(stream, a->bank_w + (size_t)code * H * H, H, H, bankT + (size_t)code * H * H);
-        for (int code = 0; code < L; code++) {
+        for (int code = 0; code < L; code++) {      // (gemm3: a forward through the transposed weights)
+            GemmParams g = g3 ? gemm_linear_fwd(dZ, H, bankT + (size_t)code * H * H, H, dXh, H, mmax, H, H)
+                              : gemm_input_grad(dZ, H, a->bank_w + (size_t)code * H * H, H, dXh, H, mmax, H, H);
+            g.gateA = zgate;
+            g.mode = GEMM_ADD;
+            g.ind = GEMM_IND_C_ROWS;
+            g.seg = seg + code;
+            g.list = list;
             if (g3) {
-                if (int rc = launch_gemm3(stream, dZ, H, bankT + (size_t)code * H * H, H, dXh, H, nullptr, mmax, H, H, 0, 1, zgate,
-                                          GEMM_IND_C_ROWS, seg + code, list))
-                    return rc;
-            } else if (int rc = launch_gemm(stream, dZ, H, 1, zgate, a->bank_w + (size_t)code * H * H, 1, H, dXh, H, nullptr, mmax,
-                                            H, H, 0, GEMM_ADD, 1, nullptr, GEMM_IND_C_ROWS, seg + code, list))
+                if (int rc = launch_gemm3(stream, gemm3_of(g), g.ind)) return rc;
+            } else if (int rc = launch_gemm(stream, g))
                 return rc;
         }
         if (a->Xh_in && a->g_Xh_ready) PN_CHECK_HIP(hipEventRecord((hipEvent_t)a->g_Xh_ready, stream));
         for (int code = 0; code < L; code++) {
+            GemmParams g = gemm_weight_grad(dZ, H, Xh, H, a->g_bank_w ? a->g_bank_w + (size_t)code * H * H : nullptr, H, mmax, H, H);
+            g.gateA = zgate;
+            g.rowsum = a->g_bank_b ? a->g_bank_b + (size_t)code * H : nullptr;
+            g.mode = GEMM_ATOMIC;
+            g.ind = GEMM_IND_K;
+            g.seg = seg + code;
+            g.list = list;
             if (a->g_bank_w && d.det) {
-                if (int rc = launch_gemm_det(stream, dZ, 1, H, zgate, Xh, 1, H, a->g_bank_w + (size_t)code * H * H, H, H, H, mmax,
-                                             (mmax + 255) / 256, a->g_bank_b ? a->g_bank_b + (size_t)code * H : nullptr, dgemm,
-                                             GEMM_IND_K, seg + code, list))
-                    return rc;
+                if (int rc = launch_gemm_det(stream, g, (mmax + 255) / 256, dgemm)) return rc;
             } else if (a->g_bank_w && rgrad_pays(ctx, mmax, H, H)) {         // large graphs: the bf16 x 3 row-reduction kernel
                 const RgradParams rp{dZ, zgate, Xh, H, H, mmax, H, H, a->g_bank_w + (size_t)code * H * H, H,
                                      a->g_bank_b ? a->g_bank_b + (size_t)code * H : nullptr, seg + code, list};
                 if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
             } else if (a->g_bank_w)
-                if (int rc = launch_gemm(stream, dZ, 1, H, zgate, Xh, 1, H, a->g_bank_w + (size_t)code * H * H, H, nullptr, H,
-                                         H, mmax, 0, GEMM_ATOMIC, (mmax + 255) / 256,
-                                         a->g_bank_b ? a->g_bank_b + (size_t)code * H : nullptr, GEMM_IND_K, seg + code, list))
-                    return rc;
+                if (int rc = launch_gemm(stream, g, (mmax + 255) / 256)) return rc;
         }
         return PN_OK;
     }
     if (gemm3_pays(ctx, d.N, H, L * H, G3_BANK_DX)) {        // bank_w [L*H, H] -> [H, L*H]
         float *bankT = c.at<float>(c.w.bankT);
         launch_transpose(stream, a->bank_w, L * H, H, bankT);
-        if (int rc = launch_gemm3(stream, dZ, (int64_t)L * H, bankT, (int64_t)L * H, dXh, H, nullptr, d.N, H, L * H, 0, 1, zgate))
-            return rc;
-    } else if (int rc = launch_gemm_split(stream, dZ, (int64_t)L * H, 1, zgate, a->bank_w, 1, H, dXh, H, nullptr, d.N, H, L * H,
-                                          0, GEMM_ADD, c.at<float>(c.w.gpart)))
-        return rc;
+        GemmParams g = gemm_linear_fwd(dZ, (int64_t)L * H, bankT, (int64_t)L * H, dXh, H, d.N, L * H, H);
+        g.gateA = zgate;
+        g.mode = GEMM_ADD;
+        if (int rc = launch_gemm3(stream, gemm3_of(g))) return rc;
+    } else {
+        GemmParams g = gemm_input_grad(dZ, (int64_t)L * H, a->bank_w, H, dXh, H, d.N, H, L * H);
+        g.gateA = zgate;
+        g.mode = GEMM_ADD;
+        if (int rc = launch_gemm_split(stream, g, c.at<float>(c.w.gpart))) return rc;
+    }
     if (a->Xh_in && a->g_Xh_ready) PN_CHECK_HIP(hipEventRecord((hipEvent_t)a->g_Xh_ready, stream));
+    GemmParams g = gemm_weight_grad(dZ, (int64_t)L * H, Xh, H, a->g_bank_w, H, d.N, H, L * H);
+    g.gateA = zgate;
+    g.rowsum = a->g_bank_b;         // g_bank_b rides along as the row sums of the same (gated) A operand
+    g.mode = GEMM_ATOMIC;
     if (a->g_bank_w && d.det) {
-        if (int rc = launch_gemm_det(stream, dZ, 1, (int64_t)L * H, zgate, Xh, 1, H, a->g_bank_w, H, L * H, H, d.N,
-                                     (d.N + 255) / 256, a->g_bank_b, dgemm))
-            return rc;
+        if (int rc = launch_gemm_det(stream, g, (d.N + 255) / 256, dgemm)) return rc;
     } else if (a->g_bank_w && rgrad_pays(ctx, d.N, L * H, H)) {
         const RgradParams rp{dZ, zgate, Xh, (int64_t)L * H, H, d.N, L * H, H, a->g_bank_w, H, a->g_bank_b, nullptr, nullptr};
         if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
-    } else if (a->g_bank_w) {       // g_bank_b rides along as the row sums of the same (gated) A operand
-        if (int rc = launch_gemm(stream, dZ, 1, (int64_t)L * H, zgate, Xh, 1, H, a->g_bank_w, H, nullptr, L * H, H, d.N,
-                                 0, GEMM_ATOMIC, (d.N + 255) / 256, a->g_bank_b))
-            return rc;
+    } else if (a->g_bank_w) {
+        if (int rc = launch_gemm(stream, g, (d.N + 255) / 256)) return rc;
     } else if (a->g_bank_b) {
         if (int rc = launch_colsum(stream, dZ, zgate, (int64_t)L * H, d.N, L * H, a->g_bank_b, d.det)) return rc;
     }
@@ -2487,10 +2482,12 @@ int run_fc0_bwd(const Call &c, const float *dXh) {
     const int H = d.H;
     const float *xgate = d.variant == PN_VARIANT_HOMO ? c.Xh : nullptr;
     StageTimer tm(ctx, ST_FC0_BWD, stream);
+    GemmParams g = gemm_weight_grad(dXh, H, a->X, d.F, a->g_fc0_w, d.F, d.N, d.F, H);
+    g.gateA = xgate;
+    g.rowsum = a->g_fc0_b;
+    g.mode = GEMM_ATOMIC;
     if (a->g_fc0_w && d.det) {
-        if (int rc = launch_gemm_det(stream, dXh, 1, H, xgate, a->X, 1, d.F, a->g_fc0_w, d.F, H, d.F, d.N, (d.N + 255) / 256,
-                                     a->g_fc0_b, c.at<float>(c.w.dgemm)))
-            return rc;
+        if (int rc = launch_gemm_det(stream, g, (d.N + 255) / 256, c.at<float>(c.w.dgemm))) return rc;
     } else if (a->g_fc0_w && d.F % 4 == 0 && rgrad_pays(ctx, d.N, H, d.F)) {
         const RgradParams rp{dXh, xgate, a->X, H, d.F, d.N, H, d.F, a->g_fc0_w, d.F, a->g_fc0_b, nullptr, nullptr};
         if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
@@ -2504,20 +2501,28 @@ int run_fc0_bwd(const Call &c, const float *dXh) {
         const RgradParams rp{dXh, xgate, Xp, H, F4, d.N, H, d.F, a->g_fc0_w, d.F, a->g_fc0_b, nullptr, nullptr};
         if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
     } else if (a->g_fc0_w) {
-        if (int rc = launch_gemm(stream, dXh, 1, H, xgate, a->X, 1, d.F, a->g_fc0_w, d.F, nullptr, H, d.F, d.N, 0,
-                                 GEMM_ATOMIC, (d.N + 255) / 256, a->g_fc0_b))
-            return rc;
+        if (int rc = launch_gemm(stream, g, (d.N + 255) / 256)) return rc;
     } else if (a->g_fc0_b) {
         if (int rc = launch_colsum(stream, dXh, xgate, H, d.N, H, a->g_fc0_b, d.det)) return rc;
     }
-    if (a->g_X)
-        if (int rc = launch_gemm(stream, dXh, H, 1, xgate, a->fc0_w, 1, d.F, a->g_X, d.F, nullptr, d.N, d.F, H, 0,
-                                 GEMM_STORE, 1))
-            return rc;
+    if (a->g_X) {
+        GemmParams gx = gemm_input_grad(dXh, H, a->fc0_w, d.F, a->g_X, d.F, d.N, d.F, H);
+        gx.gateA = xgate;
+        if (int rc = launch_gemm(stream, gx)) return rc;
+    }
     return PN_OK;
 }
 
 }  // namespace
+
+int pn::ZeroFill::flush(void *stream, bool timed) {
+    if (!zl.n) return PN_OK;
+    StageTimer tm(timed ? ctx : nullptr, ST_ZERO_FILL, stream);       // (d Z and d Xh are the bulk: rows of the graph, not paths)
+    hipLaunchKernelGGL(zero_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, zl);
+    PN_CHECK_HIP(hipGetLastError());
+    zl.n = 0;
+    return PN_OK;
+}
 
 extern "C" {
 
@@ -2539,73 +2544,6 @@ int pn_pagg_shape_info(const pn_pagg_shape *shape, int64_t out[4]) {
     out[3] = d.math;
     return PN_OK;
 }
-
-int pn_gemm_f32(const float *A, int64_t sAm, int64_t sAk, const float *B, int64_t sBn, int64_t sBk, float *C,
-                int64_t ldc, const float *bias, int32_t M, int32_t N, int32_t K, int32_t relu, void *stream_) {
-    if (!A || !B || !C || M < 0 || N < 0 || K < 0) PN_FAIL(PN_ERR_ARG, "pn_gemm_f32: bad argument");
-    if ((sAm != 1 && sAk != 1) || (sBn != 1 && sBk != 1)) PN_FAIL(PN_ERR_ARG, "pn_gemm_f32: one stride per operand must be 1");
-    return launch_gemm((hipStream_t)stream_, A, sAm, sAk, nullptr, B, sBn, sBk, C, ldc, bias, M, N, K, relu,
-                       GEMM_STORE, 1);
-}
-
-int pn_linear_forward(pn_context *ctx, const float *X, const float *W, const float *b, int32_t rows, int32_t in_f,
-                      int32_t out_f, int32_t relu, float *Y, void *workspace, int64_t workspace_bytes, void *stream_) {
-    static_assert(PN_LINEAR_SPLIT_MAX == GEMM_MAX_SPLIT, "header and kernel agree on the split bound");
-    if (!X || !W || !Y || rows < 0 || in_f < 1 || out_f < 1) PN_FAIL(PN_ERR_ARG, "pn_linear_forward: bad argument");
-    if (int rc = context_check_device(ctx)) return rc;
-    if (rows == 0) return PN_OK;
-    hipStream_t stream = (hipStream_t)stream_;
-    const bool split = workspace && workspace_bytes >= (int64_t)GEMM_MAX_SPLIT * rows * out_f * (int64_t)sizeof(float);
-    StageTimer tm(ctx, ST_FC0, stream);
-    return launch_gemm_split(stream, X, in_f, 1, nullptr, W, in_f, 1, Y, out_f, b, rows, out_f, in_f, relu, GEMM_STORE,
-                             split ? reinterpret_cast<float *>(workspace) : nullptr);
-}
-
-int pn_linear_backward(pn_context *ctx, const float *dY, const float *gate, const float *X, const float *W, int32_t rows,
-                       int32_t in_f, int32_t out_f, float *g_W, float *g_b, float *g_X, void *workspace,
-                       int64_t workspace_bytes, void *stream_) {
-    static_assert(PN_LINEAR_BWD_SPLIT_MAX == DET_MAX_SPLIT, "header and kernel agree on the split bound");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!dY || rows < 0 || in_f < 1 || out_f < 1) PN_FAIL(PN_ERR_ARG, "pn_linear_backward: bad argument");
-    if (int rc = context_check_device(ctx)) return rc;
-    StageTimer tm(ctx, ST_FC0_BWD, stream);
-    if (g_W && !X) PN_FAIL(PN_ERR_ARG, "pn_linear_backward: g_W needs X");
-    if (g_W || g_b) {       // both are accumulated with atomics: one zero-fill launch for the two
-        ZeroList zl{};
-        if (g_W) {
-            zl.ptr[zl.n] = g_W;
-            zl.count[zl.n++] = (unsigned long long)out_f * in_f;
-        }
-        if (g_b) {
-            zl.ptr[zl.n] = g_b;
-            zl.count[zl.n++] = (unsigned long long)out_f;
-        }
-        hipLaunchKernelGGL(zero_kernel, dim3(512), dim3(256), 0, stream, zl);
-        PN_CHECK_HIP(hipGetLastError());
-    }
-    if (rows == 0) return PN_OK;
-    // with a workspace: chunk sums added in a fixed order (bitwise reproducible); without: chunks race with atomics
-    const bool det = workspace && workspace_bytes >= (int64_t)(det_gemm_floats(out_f, in_f) * sizeof(float));
-    if (g_W && det) {
-        if (int rc = launch_gemm_det(stream, dY, 1, out_f, gate, X, 1, in_f, g_W, in_f, out_f, in_f, rows, (rows + 255) / 256,
-                                     g_b, reinterpret_cast<float *>(workspace)))
-            return rc;
-    } else if (g_W) {       // g_b rides along as the row sums of the (gated) A operand dY^T
-        if (int rc = launch_gemm(stream, dY, 1, out_f, gate, X, 1, in_f, g_W, in_f, nullptr, out_f, in_f, rows, 0,
-                                 GEMM_ATOMIC, (rows + 255) / 256, g_b))
-            return rc;
-    } else if (g_b) {
-        if (int rc = launch_colsum(stream, dY, gate, out_f, rows, out_f, g_b, workspace != nullptr)) return rc;
-    }
-    if (g_X) {
-        if (!W) PN_FAIL(PN_ERR_ARG, "pn_linear_backward: g_X needs W");
-        if (int rc = launch_gemm(stream, dY, out_f, 1, gate, W, 1, in_f, g_X, in_f, nullptr, rows, in_f, out_f, 0,
-                                 GEMM_STORE, 1))
-            return rc;
-    }
-    return PN_OK;
-}
-
 
 int pn_pagg_paths_stream(pn_context *ctx, const pn_pagg_shape *shape, void *stream, void **out) {
     if (!shape || !out) PN_FAIL(PN_ERR_ARG, "pn_pagg_paths_stream: null");
@@ -2762,7 +2700,7 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
         StageTimer tm(ctx, ST_PLAN_PACK, stream);      // (its own bracket: ST_SEQ_BWD times the BPTT kernel alone)
         // (fp16: packed by the forward that left its saved tensors on this workspace -- run_pack_fwd, or run_tables above)
         if (d.math != PN_SEQ_MATH_F16X2)
-            if (int rc = launch_pack_bwd3(stream, a->w_ih, a->w_hh, H, d.G, d.cell == CELL_GRU ? 1 : 0, c.at<void>(c.w.WpT))) return rc;
+            if (int rc = launch_pack_bwd3(stream, a->w_ih, a->w_hh, H, d.G, d.gru, c.at<void>(c.w.WpT))) return rc;
     }
     // Where the launches nothing waits for go -- the loss sum behind the pooling step, the classifier gradient and the attention
     // reduce (every fork / join is an event between two kernels of the queue and costs ~6 us of idle time there):
