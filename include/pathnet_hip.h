@@ -280,6 +280,46 @@ int pn_path_codes(pn_context *ctx, const pn_sampler_tables *tables, int32_t W, i
                   uint8_t *codes /* dev [rows, W, L] */, pn_path_report *report /* dev or NULL */,
                   void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- second-order (return / in-out biased) walks (pn_bias.hip) ----------------------------------------------------
+ * node2vec's bias over the walker's own tables.  Added without an ABI bump: three symbols, no existing struct changed.
+ * Step t >= 1 of a walk at node cur that came from prev has the target distribution
+ *     P(x) ~ P_table(cur -> x) * a(prev, x),  a = 1/p when x == prev (class 0, return), 1 when the hop source has the
+ *     directed edge prev -> x (class 1, near), 1/q otherwise (class 2, far);
+ * step 0 is the plain table step.  p = +inf never returns (non-backtracking), q = +inf never leaves prev's
+ * neighbourhood -- as far as the table allows, see the trial cap.
+ *
+ * Realisation: rejection sampling from the table.  pn_bias_thresholds (host, fp64, no device) gives the accept
+ * thresholds T_c = floor(2^32 * w_c / max(w)), w = {1/p, 1, 1/q} with weight 0 for an infinite parameter; the largest
+ * class gets exactly 2^32 (always accepted).  p and q must be > 0; 0, negatives and NaN fail with PN_ERR_ARG.
+ * A walk's Philox subsequence is the plain walker's global walk index ((epoch*n + st)*W + wi), the key is the seed.
+ * The trials of one walk are numbered j = 0, 1, 2, .. across all its steps; trial j reads Philox block j (draws
+ * 4j .. 4j+2 of the subsequence): word 0 >> 1 is the slot draw (% table length), word 1 >> 1 the alias probability draw
+ * (>= thr ? A : B; both candidates are the same node in uniform tables), the full word 2 the accept draw -- the proposal
+ * is taken iff word 2 < T_class -- and word 3 is unused.  Step 0 takes its first proposal.
+ * A step takes at most PN_BIAS_MAX_TRIALS trials: a step that comes to its 64th trial takes that proposal whatever the
+ * accept draw says and is counted in *exhausted.  So the realised distribution differs from the target on at most the
+ * `exhausted` share of the steps, and a walk at a leaf under p = inf returns to where it came from (after 64 trials).
+ * A walk of length L makes L-1 transitions and, unlike pn_sample_paths, draws nothing after its last node.  A node with
+ * an empty table at a step that needs one sets status_flag = PN_ERR_EMPTY_TABLE; the rest of that path repeats the
+ * node and no further draws are made.
+ *
+ * ids / codes are dev [epoch_count, node_count, W, L] as for pn_sample_paths, and the codes are those pn_path_codes
+ * gives for the ids over the same tables, bit for bit (on the fly they come from that very launch, enqueued by this
+ * call behind the walk).  exhausted (dev int64, may be NULL) is zeroed by the call.  node_list and step_state as for
+ * pn_sample_paths.  Asynchronous: nothing is read back.  The workspace (size from the query, which needs no device:
+ * 0 with a dense table) may be NULL when the query says 0.  Argument errors -- null tables, W < 1, L < 1, no hop source,
+ * half a CSR, on-the-fly L > 8, bad p / q, a short or missing workspace -- fail with PN_ERR_ARG before any device
+ * call. */
+#define PN_BIAS_MAX_TRIALS 64
+int pn_bias_thresholds(double p, double q, uint64_t thr[3]);
+int pn_sample_paths_biased_workspace_bytes(const pn_sampler_tables *tables, int32_t W, int32_t L, int64_t epoch_count,
+                                           int32_t node_count, int64_t *bytes);
+int pn_sample_paths_biased(pn_context *ctx, const pn_sampler_tables *tables, int32_t W, int32_t L, uint64_t seed,
+                           int64_t epoch_begin, int64_t epoch_count, int32_t node_begin, int32_t node_count, double p,
+                           double q, int32_t *ids, uint8_t *codes, int64_t *exhausted /* dev or NULL */, void *workspace,
+                           int64_t workspace_bytes, int32_t *status_flag, const pn_step_state *step_state,
+                           const int32_t *node_list, void *stream);
+
 /* ---- the synthetic-label generator (pn_census.hip): synthetic_data/gen_cora_syn.cpp, gen_citeseer_syn.cpp ------------
  * For every node, the walks of walk_len steps binned by the symbols of the nodes they visit, and the most frequent bin.
  * Added without an ABI bump: four new symbols, no existing struct or signature changed, so a caller built against

@@ -13,8 +13,8 @@ Everything computes through csrc/libpathnet_hip.so (C ABI: include/pathnet_hip.h
 from . import _lib  # noqa: F401
 from .modules import PAGG, PathNet, PathNet_homo  # noqa: F401
 from .optim import Adam, CrossEntropyLoss, StepState, backward, cross_entropy  # noqa: F401
-from .sampler import (DRAW_GLIBC_REPLAY, DRAW_PHILOX, MerwSampler, PathAnnotator, PathReport,  # noqa: F401
-                      UniformSampler)
+from .sampler import (DRAW_GLIBC_REPLAY, DRAW_PHILOX, BiasedSampler, MerwSampler, PathAnnotator,  # noqa: F401
+                      PathReport, UniformSampler)
 from .synth import PatternCensus  # noqa: F401
 
 __version__ = "0.1.0"

@@ -116,6 +116,13 @@ SIGNATURES = {
                                                      ctypes.c_int32, c_i64p]),
     "pn_path_codes": (ctypes.c_int, [vp, ctypes.POINTER(SamplerTables), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp,
                                      vp, vp, vp, ctypes.c_int64, vp]),
+    "pn_bias_thresholds": (ctypes.c_int, [ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_uint64)]),
+    "pn_sample_paths_biased_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(SamplerTables), ctypes.c_int32, ctypes.c_int32,
+                                                              ctypes.c_int64, ctypes.c_int32, c_i64p]),
+    "pn_sample_paths_biased": (ctypes.c_int, [vp, ctypes.POINTER(SamplerTables), ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp,
+                                              ctypes.c_int64, vp, vp, vp, vp]),
     "pn_census_lists_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, c_i64p]),
     "pn_census_lists": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp, vp, ctypes.c_int64, vp]),
     "pn_pattern_census_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_i64p]),

@@ -397,23 +397,15 @@ class MerwSampler(_HopSource):
         n, u, v, p = read_edge_file(path)
         return cls(n, u, v, p, seq_len, device=device, hops=hops, build=build)
 
-    def sample(self, W, seed, epoch_begin=0, epoch_count=1, node_begin=0, node_count=None,
-               draw_source=DRAW_PHILOX, check=True, out=None, step_state=None, nodes=None):
-        """-> ids int32 [epoch_count, node_count, W, L], codes uint8 [...] on the GPU.
-        nodes (int32 device tensor, Philox only): sample the paths of these source nodes (in this order) instead of the
-        range [node_begin, node_begin + node_count) -- e.g. the step's masked nodes; a walk's draws depend on (epoch,
-        source node, walk index) only, so the paths are the ones a full-epoch sample holds for those nodes.
-        step_state (pathnet_amd.StepState, Philox only): seed and epoch_begin are read from device memory when the
-        kernel runs, so the call can be captured in a hipGraph and replayed."""
-        lib = _lib.load()
+    def _window(self, W, epoch_count, node_begin, node_count, out, nodes):
+        """-> node_begin, node_count and the two output tensors of a sample() call (checked `out`, or new ones)."""
         if nodes is not None:
             if nodes.dtype != torch.int32 or not nodes.is_cuda or not nodes.is_contiguous() or nodes.dim() != 1:
                 raise ValueError("sample(nodes=...): contiguous 1-D int32 device tensor of node ids expected")
             node_begin, node_count = 0, int(nodes.numel())
         elif node_count is None:
             node_count = self.n - node_begin
-        L = self.L
-        shape = (epoch_count, node_count, W, L)
+        shape = (epoch_count, node_count, W, self.L)
         if out is None:
             ids = torch.empty(shape, dtype=torch.int32, device=self.device)
             codes = torch.empty(shape, dtype=torch.uint8, device=self.device)
@@ -424,12 +416,33 @@ class MerwSampler(_HopSource):
                         (self.device.index is not None and t.device != self.device)):
                     raise ValueError("sample(out=...): contiguous %s tensor of shape %s on %s expected, got %s %s on %s"
                                      % (dt, shape, self.device, t.dtype, tuple(t.shape), t.device))
+        return node_begin, node_count, ids, codes
+
+    def _tables(self):
+        dp = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        return _lib.SamplerTables(self.n, self.total, self.d_off.data_ptr(), self.d_triples.data_ptr(), dp(self.d_dis),
+                                  dp(self.d_adj_off), dp(self.d_adj), dp(self.d_radj_off), dp(self.d_radj),
+                                  self.draws_per_step, dp(self.d_node_ref))
+
+    def biased(self, p, q):
+        """A view of this sampler that walks with node2vec's return parameter p and in-out parameter q (BiasedSampler):
+        same device tables, same sample() signature; p = inf is a non-backtracking walk."""
+        return BiasedSampler(self, p, q)
+
+    def sample(self, W, seed, epoch_begin=0, epoch_count=1, node_begin=0, node_count=None,
+               draw_source=DRAW_PHILOX, check=True, out=None, step_state=None, nodes=None):
+        """-> ids int32 [epoch_count, node_count, W, L], codes uint8 [...] on the GPU.
+        nodes (int32 device tensor, Philox only): sample the paths of these source nodes (in this order) instead of the
+        range [node_begin, node_begin + node_count) -- e.g. the step's masked nodes; a walk's draws depend on (epoch,
+        source node, walk index) only, so the paths are the ones a full-epoch sample holds for those nodes.
+        step_state (pathnet_amd.StepState, Philox only): seed and epoch_begin are read from device memory when the
+        kernel runs, so the call can be captured in a hipGraph and replayed."""
+        lib = _lib.load()
+        node_begin, node_count, ids, codes = self._window(W, epoch_count, node_begin, node_count, out, nodes)
+        L = self.L
         need = ctypes.c_int64(0)
         _lib.check(lib.pn_sample_workspace_bytes(W, L, draw_source, epoch_count, node_count, ctypes.byref(need)))
-        dp = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-        tb = _lib.SamplerTables(self.n, self.total, self.d_off.data_ptr(), self.d_triples.data_ptr(), dp(self.d_dis),
-                                dp(self.d_adj_off), dp(self.d_adj), dp(self.d_radj_off), dp(self.d_radj),
-                                self.draws_per_step, dp(self.d_node_ref))
+        tb = self._tables()
         dev = ids.device
         with torch.cuda.device(dev):        # the library launches on the current device
             if need.value and (self._ws is None or self._ws.numel() < need.value):
@@ -467,6 +480,72 @@ class UniformSampler(MerwSampler):
         return cls(n, u, v, seq_len, device=device, hops=hops)
 
 
+def bias_thresholds(p, q):
+    """pn_bias_thresholds: the accept thresholds (T_return, T_near, T_far), integers in [0, 2^32], of a walk with return
+    parameter p and in-out parameter q -- floor(2^32 * w / max(w)) for w = (1/p, 1, 1/q) in fp64.  No device needed."""
+    thr = (ctypes.c_uint64 * 3)()
+    rc = _lib.load().pn_bias_thresholds(float(p), float(q), thr)
+    if rc == _lib.PN_ERR_ARG:
+        raise ValueError("p and q must be > 0 (inf allowed), got p=%r q=%r" % (p, q))
+    _lib.check(rc)
+    return tuple(int(t) for t in thr)
+
+
+class BiasedSampler:
+    """sampler.biased(p, q): second-order walks over the tables of a MerwSampler / UniformSampler (pn_sample_paths_biased).
+    Step t >= 1 at node cur, having come from prev, goes to x with probability ~ P_table(cur -> x) * a, a = 1/p for
+    x == prev, 1 when prev -> x is an edge, 1/q otherwise; realised by rejection from the table with at most 64 trials a
+    step (the 64th proposal is taken as it is and the step counted in exhausted_steps()), so the realised distribution
+    differs from the target on at most that share of the steps, and p = inf at a leaf returns.
+    A light view: it owns no tables, only the device counter.  Takes the place of the sampler wherever one is taken."""
+
+    def __init__(self, base, p, q):
+        self.base, self.p, self.q = base, float(p), float(q)
+        self.thresholds = bias_thresholds(p, q)     # refuses bad p / q here, not at the first sample()
+        self._exhausted = self._ws = None
+
+    n = property(lambda self: self.base.n)
+    L = property(lambda self: self.base.L)
+    device = property(lambda self: self.base.device)
+
+    def annotate(self, *args, **kw):
+        return self.base.annotate(*args, **kw)
+
+    def exhausted_steps(self):
+        """Steps of the latest sample() that came to their 64th trial (one read-back); 0 before the first call."""
+        return 0 if self._exhausted is None else int(self._exhausted.item())
+
+    def sample(self, W, seed, epoch_begin=0, epoch_count=1, node_begin=0, node_count=None,
+               draw_source=DRAW_PHILOX, check=True, out=None, step_state=None, nodes=None):
+        """MerwSampler.sample's signature and results; Philox draws only (trial j of a walk reads Philox block j)."""
+        if draw_source != DRAW_PHILOX:
+            raise ValueError("biased walks draw from Philox only (draw_source=DRAW_PHILOX)")
+        base, lib = self.base, _lib.load()
+        node_begin, node_count, ids, codes = base._window(W, epoch_count, node_begin, node_count, out, nodes)
+        tb = base._tables()
+        need = ctypes.c_int64(0)
+        _lib.check(lib.pn_sample_paths_biased_workspace_bytes(ctypes.byref(tb), W, base.L, epoch_count, node_count,
+                                                              ctypes.byref(need)))
+        dev = ids.device
+        with torch.cuda.device(dev):        # the library launches on the current device
+            if need.value and (self._ws is None or self._ws.numel() < need.value):
+                self._ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+            if self._exhausted is None:
+                self._exhausted = torch.zeros(1, dtype=torch.int64, device=dev)
+            if check:
+                base._status.zero_()
+            _lib.check(lib.pn_sample_paths_biased(_lib.context(dev), ctypes.byref(tb), W, base.L,
+                                                  seed & 0xFFFFFFFFFFFFFFFF, epoch_begin, epoch_count, node_begin,
+                                                  node_count, self.p, self.q, _lib.ptr(ids), _lib.ptr(codes),
+                                                  _lib.ptr(self._exhausted), _lib.ptr(self._ws) if need.value else None,
+                                                  need.value, _lib.ptr(base._status),
+                                                  step_state.ptr() if step_state is not None else None,
+                                                  _lib.ptr(nodes) if nodes is not None else None, _lib.stream_ptr(dev)))
+        if check and int(base._status.item()) != 0:
+            raise _lib.PnError(int(base._status.item()), "ERROR:: A.size() == 0 in Alias Table")
+        return ids, codes
+
+
 def main(argv=None):
     """Drop-in for ./gen_merw and ./gen_epoch_merw (argv: <data_name> <path_num> <path_length>); with --uniform for
     ./gen and ./gen_epoch (the uniform random-walk sampler)."""
@@ -474,7 +553,8 @@ def main(argv=None):
     per_epoch = "--per-epoch" in argv
     uniform = "--uniform" in argv        # gen.cpp / gen_epoch.cpp instead of gen_merw.cpp / gen_epoch_merw.cpp
     binary = "--binary" in argv          # also write the PNPATHS1 sidecar(s) next to the text file(s)
-    opts = {"--seed": None, "--epochs": "1000", "--draw": "glibc", "--in": None, "--out-root": "./"}
+    opts = {"--seed": None, "--epochs": "1000", "--draw": "glibc", "--in": None, "--out-root": "./", "--bias": None,
+            "--marker": None}
     pos = []
     i = 0
     while i < len(argv):
@@ -495,11 +575,20 @@ def main(argv=None):
     epochs = int(opts["--epochs"])
     draw = DRAW_GLIBC_REPLAY if opts["--draw"] == "glibc" else DRAW_PHILOX
     root = opts["--out-root"]
+    bias = None
+    if opts["--bias"] is not None:      # --bias P,Q: second-order walks (BiasedSampler); inf is accepted
+        if draw != DRAW_PHILOX:
+            print("ERROR: --bias needs --draw philox (a biased walk has no glibc draw stream to replay)", file=sys.stderr)
+            return 2
+        bias = tuple(float(x) for x in opts["--bias"].split(","))
+        if len(bias) != 2:
+            print("ERROR: --bias P,Q expected", file=sys.stderr)
+            return 2
     if uniform:
         # gen.cpp:50-68 reads <name>_nsl.in and writes <name>_<W>_<L>_nsl.txt; gen_epoch.cpp:50-56,:84-95 reads <name>.in
         # and writes <name>_<W>_<L>_<epoch>.txt
         edge = opts["--in"] or ("../edge_input/%s.in" % name if per_epoch else "../edge_input/%s_nsl.in" % name)
-        whole = pathfile.whole_run_name(root, name, W, L, marker="nsl")
+        whole = pathfile.whole_run_name(root, name, W, L, marker=opts["--marker"] or "nsl")
         if not per_epoch:
             print("File input: " + edge)                                     # gen.cpp:73-74
             print("File output: " + whole)
@@ -513,7 +602,9 @@ def main(argv=None):
         edge = opts["--in"] or "../edge_input/%s.in" % name
         smp = MerwSampler.from_edge_file(edge, L)
         print(name + ": " + str(smp.n), file=sys.stderr)                    # :164
-        whole = pathfile.whole_run_name(root, name, W, L)
+        whole = pathfile.whole_run_name(root, name, W, L, marker=opts["--marker"] or "merw")
+    if bias is not None:
+        smp = smp.biased(*bias)
     chunk = max(1, min(epochs, (64 << 20) // max(1, smp.n * W * L * 5)))
     for e0 in range(0, epochs, chunk):
         ec = min(chunk, epochs - e0)
@@ -528,7 +619,7 @@ def main(argv=None):
         for k in range(ec):
             if per_epoch:
                 fn = ("%s%s_%d_%d_%d.txt" % (root, name, W, L, e0 + k) if uniform       # gen_epoch.cpp:84-95: no marker
-                      else pathfile.per_epoch_name(root, name, W, L, e0 + k))
+                      else pathfile.per_epoch_name(root, name, W, L, e0 + k, marker=opts["--marker"] or "merw"))
                 pathfile.write_paths(fn, ids[k], codes[k])
                 if binary:
                     pathfile.write_paths_binary(fn[:-4] + ".bin", ids[k], codes[k])
