@@ -352,6 +352,56 @@ int pn_pattern_census(pn_context *ctx, int32_t n, const int64_t *off, const int3
                       int64_t *counts /* dev [n, B^k] or NULL */, int64_t *labels /* dev [n] or NULL */, void *workspace,
                       int64_t workspace_bytes, void *stream);
 
+/* ---- walk statistics (pn_stats.hip): what sampled paths look like, counted on the device ----------------------------
+ * pn_path_codes counts what is wrong with paths; this describes paths that are right.  Added without an ABI bump: two new
+ * symbols and one new struct, no existing struct or signature changed, so pn_abi_version keeps answering 12.
+ *
+ * One pass over ids / codes [rows, W, L]; a row is the W paths of one (epoch, source node), and the source of row s is
+ * sources[s] when given, else ids[s, 0, 0].  Every result is an exact integer count: it depends neither on the launch
+ * geometry nor on the order of the atomics.  The outputs are caller-owned device memory, described by one
+ * pn_walk_stats_out; each pointer may be NULL, meaning "not wanted, never written".
+ *   step_code[t][d]      path nodes at step t whose code is d.  A code >= L counts in counters[1] (bad_codes) and nowhere
+ *                        else: such a node is in neither step_code, label_pairs nor unlabeled.
+ *   label_pairs[d][a][b] path nodes with code d whose row's source has label a and which themselves have label b; needs
+ *                        labels (dev int32 [n]) and C.  A node or source outside [0, n), or whose label lies outside
+ *                        [0, C) (-1 = unlabelled), counts in unlabeled[d] instead, so label_pairs[d].sum() + unlabeled[d]
+ *                        = step_code[:, d].sum().  Edge homophily by distance is trace / sum per d.
+ *   stay[t], back[t]     stay[t], t >= 1: ids[t] == ids[t-1].  back[t], t >= 2: ids[t] == ids[t-2] and ids[t] != ids[t-1].
+ *                        The other entries are 0.
+ *   distinct_hist[k]     paths that visit exactly k distinct ids (k = 1 .. L; entry 0 stays 0).
+ *   unique_paths[s]      distinct id sequences among the W paths of row s.
+ *   cover[s]             distinct ids among the W * L entries of row s.
+ *   visits[v]            times node v occurs at a step t >= 1.
+ *   counters             {out_of_range, bad_codes}: entries of ids outside [0, n) / entries of codes >= L.
+ * An id outside [0, n) never indexes labels or visits; in the distinct, unique and cover counts it is an ordinary integer.
+ * A source outside [0, n) (possible only through `sources`) is no entry of ids and is not counted in out_of_range.
+ * accumulate == 0: the call zeroes the global tables (every output but unique_paths and cover) before it counts;
+ * accumulate != 0: it adds to what they hold, so a loop over epochs profiles a run without keeping its paths.
+ * Limits, refused with PN_ERR_ARG before any device call: 1 <= L <= 16, W >= 1, W * L <= 8192, rows >= 0, n >= 1,
+ * 1 <= C <= 64 when labels are given (C is ignored without them); label_pairs or unlabeled without labels; NULL ids or
+ * codes with rows > 0; NULL out.  rows == 0 is valid: it zeroes the tables when not accumulating and launches nothing
+ * over rows.  Asynchronous on `stream`: nothing is read back.  The workspace size comes from the query, which needs no
+ * device and answers 0 today (a row is counted in LDS); the workspace may be NULL when it does. */
+typedef struct pn_walk_stats_out {   /* device pointers, caller-owned, each may be NULL */
+    int64_t *step_code;              /* [L, L] */
+    int64_t *label_pairs;            /* [L, C, C] */
+    int64_t *unlabeled;              /* [L] */
+    int64_t *stay;                   /* [L] */
+    int64_t *back;                   /* [L] */
+    int64_t *distinct_hist;          /* [L + 1] */
+    int32_t *unique_paths;           /* [rows] */
+    int32_t *cover;                  /* [rows] */
+    int64_t *visits;                 /* [n] */
+    int64_t *counters;               /* [2] */
+} pn_walk_stats_out;
+
+int pn_walk_stats_workspace_bytes(int32_t n, int32_t W, int32_t L, int64_t rows, int32_t C, int64_t *bytes);
+int pn_walk_stats(pn_context *ctx, int32_t n, int32_t W, int32_t L, int64_t rows,
+                  const int32_t *ids /* dev [rows, W, L] */, const uint8_t *codes /* dev [rows, W, L] */,
+                  const int32_t *sources /* dev [rows] or NULL */, const int32_t *labels /* dev [n] or NULL */, int32_t C,
+                  int32_t accumulate, const pn_walk_stats_out *out, void *workspace, int64_t workspace_bytes,
+                  void *stream);
+
 /* ================================================================================================
  * Path file.  The on-disk interface between sampler and trainer: one line per path,
  * "[v0, v1, ..., v_{L-1}, d0, ..., d_{L-1}]\n"  (writer gen_merw.cpp:189-206; reader

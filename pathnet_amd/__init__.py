@@ -6,6 +6,7 @@
   pathnet_amd.dist      node sharding across the GPUs of one box (RCCL)
   pathnet_amd.optim     CrossEntropyLoss / Adam of the reference's training step as single launches
   pathnet_amd.trainer   train_fixed_indices with everything resident on the GPU
+  pathnet_amd.walkstats statistics of sampled paths, counted on the GPU (the walkstats CLI)
   pathnet_amd.synth     path-pattern census: the labels of the synthetic experiment (the gen_*_syn CLI)
 
 Everything computes through csrc/libpathnet_hip.so (C ABI: include/pathnet_hip.h).
@@ -16,5 +17,6 @@ from .optim import Adam, CrossEntropyLoss, StepState, backward, cross_entropy  #
 from .sampler import (DRAW_GLIBC_REPLAY, DRAW_PHILOX, BiasedSampler, MerwSampler, PathAnnotator,  # noqa: F401
                       PathReport, UniformSampler)
 from .synth import PatternCensus  # noqa: F401
+from .walkstats import WalkStats, walk_stats  # noqa: F401
 
 __version__ = "0.1.0"

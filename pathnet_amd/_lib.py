@@ -72,6 +72,13 @@ class PaggArgs(ctypes.Structure):
                  ("out_embed", vp), ("out_path_weight", vp), ("out_path_state", vp), ("g_embed", vp)])
 
 
+class WalkStatsOut(ctypes.Structure):
+    """struct pn_walk_stats_out: device pointers, None = not wanted"""
+    FIELDS = ("step_code", "label_pairs", "unlabeled", "stay", "back", "distinct_hist", "unique_paths", "cover", "visits",
+              "counters")
+    _fields_ = [(k, vp) for k in FIELDS]
+
+
 # name -> (restype, argtypes): every symbol include/pathnet_hip.h declares
 class AdamTensor(ctypes.Structure):
     """struct pn_adam_tensor"""
@@ -128,6 +135,10 @@ SIGNATURES = {
     "pn_pattern_census_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_i64p]),
     "pn_pattern_census": (ctypes.c_int, [vp, ctypes.c_int32, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp,
                                          ctypes.c_int64, vp]),
+    "pn_walk_stats_workspace_bytes": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                     ctypes.c_int32, c_i64p]),
+    "pn_walk_stats": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp,
+                                     ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(WalkStatsOut), vp, ctypes.c_int64, vp]),
     "pn_paths_write_text": (ctypes.c_int, [ctypes.c_char_p, c_i32p, c_u8p, ctypes.c_int64, ctypes.c_int32,
                                            ctypes.c_int32]),
     "pn_paths_read_text": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, c_i32p, c_u8p, ctypes.c_int64, c_i64p]),

@@ -273,6 +273,12 @@ class _HopSource:
                              % (rep.out_of_range, self.n, rep.first_bad))
         return (codes, rep) if report else codes
 
+    def walk_stats(self, ids, codes, **kw):
+        """walkstats.walk_stats(ids, codes, n=self.n, ...): statistics of sampled (or annotated) paths, counted on the
+        device -> WalkStats."""
+        from . import walkstats
+        return walkstats.walk_stats(ids, codes, self.n, **kw)
+
 
 class PathAnnotator(_HopSource):
     """The hop source of a graph without a sampler around it: annotate() for callers that bring their own paths and
@@ -510,6 +516,9 @@ class BiasedSampler:
 
     def annotate(self, *args, **kw):
         return self.base.annotate(*args, **kw)
+
+    def walk_stats(self, ids, codes, **kw):
+        return self.base.walk_stats(ids, codes, **kw)
 
     def exhausted_steps(self):
         """Steps of the latest sample() that came to their 64th trial (one read-back); 0 before the first call."""
