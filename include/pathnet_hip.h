@@ -402,6 +402,52 @@ int pn_walk_stats(pn_context *ctx, int32_t n, int32_t W, int32_t L, int64_t rows
                   int32_t accumulate, const pn_walk_stats_out *out, void *workspace, int64_t workspace_bytes,
                   void *stream);
 
+/* ---- transition probabilities and path likelihoods (pn_prob.hip): the walker's tables, evaluated --------------------
+ * pn_sample_paths draws from the tables; this says how likely given paths are under them.  Added without an ABI bump: two
+ * new symbols and one new struct, no existing struct or signature changed, so pn_abi_version keeps answering 12.
+ *
+ * The walker's step at a node cur whose table holds k triples {A, B, thr} is  slot = r0 % k,  next = r1 >= thr[slot] ? A : B
+ * with r0, r1 uniform on [0, 2^31) -- glibc replay and Philox word >> 1 alike, in pn_sample_paths and in
+ * pn_sample_paths_biased.  So the realised probability of cur -> x is the integer
+ *     N(cur -> x) = sum_s c_s * (max(0, 2^31 - thr_s) * [A_s == x] + min(thr_s, 2^31) * [B_s == x]),
+ *     c_s = 2^31 / k + (s < 2^31 % k),
+ * over 2^62; the N of a non-empty table sum to exactly 2^62.  Uniform tables have A = B, so the same sum serves them.
+ * ids is dev [rows, W, L]; a path of L nodes has L-1 transitions, and transition t is ids[t] -> ids[t+1].
+ *   num[r, w, t]      N(ids[t] -> ids[t+1]).
+ *   second_order != 0 (the biased walker's view; reads the hop source as well): for t >= 1, prev = ids[t-1], a node y is
+ *     of class 0 when y == prev (also when prev has a self loop), 1 when the hop source has the directed edge prev -> y
+ *     (dis[prev][y] == 2, or y in prev's sorted out-list: the test pn_sample_paths_biased makes), 2 otherwise.
+ *   mass[r, w, t, c]  the sum of N(ids[t] -> y) over the y of class c; the three sum to 2^62 over a non-empty table.
+ *   cls[r, w, t]      the class of ids[t+1]; 3 = none.
+ *     Transition 0 has no prev, and a prev outside [0, n) classifies nothing: cls = 3 and mass = 0 there.
+ *     p and q do not enter: the accept probabilities are applied by the caller (pathnet_amd/pathprob.py), so one call
+ *     serves every (p, q).
+ *   counters          {bad_ids, empty_tables, impossible, 0}.  A transition with ids[t] or ids[t+1] outside [0, n) has
+ *     num = 0, mass = 0, cls = 3, adds the number of its ids that are outside (1 or 2) to bad_ids -- so a bad id in the
+ *     middle of a path is seen by the two transitions it belongs to -- and never indexes a table.  A transition inside the
+ *     graph from a node with an empty table has num = 0 and counts in empty_tables; one from a non-empty table with N = 0
+ *     counts in impossible.
+ * Every output pointer may be NULL: not wanted, never written.  No floating point is used: every sum is a 64-bit integer
+ * add, so the result depends neither on the launch geometry nor on any order.
+ * Asynchronous on `stream`: nothing is read back.  counters is zeroed by the call.  L == 1 or rows == 0 is valid and only
+ * zeroes the counters.  Argument errors fail with PN_ERR_ARG before any device call: null tables or out, null ids with
+ * rows > 0; n < 1, W < 1, L < 1, rows < 0; null triples, or neither off nor node_ref; second_order with neither a dense hop table nor all four
+ * CSR arrays (the walker's notion of a hop source, though only the out-lists are read); mass or cls without second_order;
+ * a negative workspace size, or a short or missing workspace when the query asks for one.  The query needs no device
+ * and answers 0 today (a transition is summed in registers); the workspace may be NULL when it does. */
+typedef struct pn_path_prob_out {      /* device pointers, caller-owned; NULL = not wanted, never written */
+    int64_t *num;                      /* [rows, W, L-1]     N(ids[t] -> ids[t+1]), numerator over 2^62 */
+    int64_t *mass;                     /* [rows, W, L-1, 3]  second order only: class masses given prev */
+    uint8_t *cls;                      /* [rows, W, L-1]     second order only: class of ids[t+1]; 3 = none */
+    int64_t *counters;                 /* [4] zeroed by the call: {bad_ids, empty_tables, impossible, reserved 0} */
+} pn_path_prob_out;
+
+int pn_path_prob_workspace_bytes(const pn_sampler_tables *tables, int32_t W, int32_t L, int64_t rows, int32_t second_order,
+                                 int64_t *bytes);
+int pn_path_prob(pn_context *ctx, const pn_sampler_tables *tables, int32_t W, int32_t L, int64_t rows,
+                 const int32_t *ids /* dev [rows, W, L] */, int32_t second_order, const pn_path_prob_out *out,
+                 void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ================================================================================================
  * Path file.  The on-disk interface between sampler and trainer: one line per path,
  * "[v0, v1, ..., v_{L-1}, d0, ..., d_{L-1}]\n"  (writer gen_merw.cpp:189-206; reader

@@ -7,6 +7,7 @@
   pathnet_amd.optim     CrossEntropyLoss / Adam of the reference's training step as single launches
   pathnet_amd.trainer   train_fixed_indices with everything resident on the GPU
   pathnet_amd.walkstats statistics of sampled paths, counted on the GPU (the walkstats CLI)
+  pathnet_amd.pathprob  transition probabilities and path likelihoods under the sampler's tables; importance weights
   pathnet_amd.synth     path-pattern census: the labels of the synthetic experiment (the gen_*_syn CLI)
 
 Everything computes through csrc/libpathnet_hip.so (C ABI: include/pathnet_hip.h).
@@ -16,6 +17,7 @@ from .modules import PAGG, PathNet, PathNet_homo  # noqa: F401
 from .optim import Adam, CrossEntropyLoss, StepState, backward, cross_entropy  # noqa: F401
 from .sampler import (DRAW_GLIBC_REPLAY, DRAW_PHILOX, BiasedSampler, MerwSampler, PathAnnotator,  # noqa: F401
                       PathReport, UniformSampler)
+from .pathprob import PathProb, importance_weights  # noqa: F401
 from .synth import PatternCensus  # noqa: F401
 from .walkstats import WalkStats, walk_stats  # noqa: F401
 

@@ -79,6 +79,12 @@ class WalkStatsOut(ctypes.Structure):
     _fields_ = [(k, vp) for k in FIELDS]
 
 
+class PathProbOut(ctypes.Structure):
+    """struct pn_path_prob_out: device pointers, None = not wanted"""
+    FIELDS = ("num", "mass", "cls", "counters")
+    _fields_ = [(k, vp) for k in FIELDS]
+
+
 # name -> (restype, argtypes): every symbol include/pathnet_hip.h declares
 class AdamTensor(ctypes.Structure):
     """struct pn_adam_tensor"""
@@ -139,6 +145,10 @@ SIGNATURES = {
                                                      ctypes.c_int32, c_i64p]),
     "pn_walk_stats": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp,
                                      ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(WalkStatsOut), vp, ctypes.c_int64, vp]),
+    "pn_path_prob_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(SamplerTables), ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_int64, ctypes.c_int32, c_i64p]),
+    "pn_path_prob": (ctypes.c_int, [vp, ctypes.POINTER(SamplerTables), ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp,
+                                    ctypes.c_int32, ctypes.POINTER(PathProbOut), vp, ctypes.c_int64, vp]),
     "pn_paths_write_text": (ctypes.c_int, [ctypes.c_char_p, c_i32p, c_u8p, ctypes.c_int64, ctypes.c_int32,
                                            ctypes.c_int32]),
     "pn_paths_read_text": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32, c_i32p, c_u8p, ctypes.c_int64, c_i64p]),

@@ -32,6 +32,7 @@
 #include <cmath>
 
 #include "pn_internal.h"
+#include "pn_otf.h"
 
 namespace {
 
@@ -77,33 +78,6 @@ __device__ __forceinline__ uint4 philox_block(uint64_t seed, uint64_t sub, uint3
     return make_uint4(c0, c1, c2, c3);
 }
 
-__device__ __forceinline__ void node_table(const BiasParams &p, int32_t x, int64_t &o0, int32_t &len) {
-    if (p.node_ref) {
-        const uint2 r = p.node_ref[x];
-        o0 = r.x;
-        len = (int32_t)r.y;
-    } else {
-        o0 = p.off[x];
-        len = (int32_t)(p.off[x + 1] - o0);
-    }
-}
-
-// the directed edge a -> b (a != b) in the hop source
-__device__ __forceinline__ bool has_edge(const BiasParams &p, int32_t a, int32_t b) {
-    if (p.dis) return p.dis[(size_t)a * (size_t)p.n + (size_t)b] == 2;
-    int64_t lo = p.adj_off[a], hi = p.adj_off[a + 1];
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        const int32_t v = p.adj[mid];
-        if (v == b) return true;
-        if (v < b)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return false;
-}
-
 // pn_path_codes' dense formula: 0 = unreached, else hops + 1
 __device__ __forceinline__ uint8_t dense_code(const BiasParams &p, int32_t st, int32_t x) {
     const int b = p.dis[(size_t)st * (size_t)p.n + (size_t)x];
@@ -142,7 +116,7 @@ __global__ __launch_bounds__(kBiasThreads) void bias_walk_kernel(BiasParams p) {
         if (out_codes) out_codes[0] = code = dense_code(p, st, st);
         int64_t o0 = 0;
         int32_t len = 0;
-        if (last > 0) node_table(p, x, o0, len);
+        if (last > 0) node_table(p.node_ref, p.off, x, o0, len);
         // every iteration is one trial of this lane's current step; at most 64 per step
         for (int32_t it = 0; it < last * PN_BIAS_MAX_TRIALS && t < last; it++) {
             if (len <= 0) {
@@ -165,7 +139,7 @@ __global__ __launch_bounds__(kBiasThreads) void bias_walk_kernel(BiasParams p) {
                 else if (flat_far)
                     T = p.thr[1];
                 else
-                    T = has_edge(p, prev, cand) ? p.thr[1] : p.thr[2];
+                    T = has_edge(p.dis, p.adj_off, p.adj, p.n, prev, cand) ? p.thr[1] : p.thr[2];
                 take = (unsigned long long)w.z < T;
                 if (k == PN_BIAS_MAX_TRIALS) {
                     take = true;
@@ -179,7 +153,7 @@ __global__ __launch_bounds__(kBiasThreads) void bias_walk_kernel(BiasParams p) {
                 k = 0;
                 out_ids[t] = x;
                 if (out_codes) out_codes[t] = code = dense_code(p, st, x);
-                if (t < last) node_table(p, x, o0, len);
+                if (t < last) node_table(p.node_ref, p.off, x, o0, len);
             }
         }
     }

@@ -2,12 +2,45 @@
 // (pn_codes.hip): the per-wave LDS hash table that holds the out-ball of a source node with exact distances, and the
 // Bloom filter over the out-neighbours of the ball's outermost level.  Why the ball and a bounded search over
 // in-neighbour chains give exact hop counts: the comment above merw_walk_otf_kernel.
+// Also the two table look-ups that the biased walker (pn_bias.hip) and its likelihood (pn_prob.hip) must agree on:
+// node_table and has_edge.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 namespace {
+
+// the table of node x: its first triple and its length, from node_ref ({first triple, count}: one 8-byte load) or, when
+// that is null, from two words of off[]
+__device__ __forceinline__ void node_table(const uint2 *node_ref, const int64_t *off, int32_t x, int64_t &o0, int32_t &len) {
+    if (node_ref) {
+        const uint2 r = node_ref[x];
+        o0 = r.x;
+        len = (int32_t)r.y;
+    } else {
+        o0 = off[x];
+        len = (int32_t)(off[x + 1] - o0);
+    }
+}
+
+// the directed edge a -> b (a != b) in the hop source: one byte of the dense table, or (dis == null) a binary search of
+// a's sorted out-list
+__device__ __forceinline__ bool has_edge(const uint8_t *dis, const int64_t *adj_off, const int32_t *adj, int32_t n, int32_t a,
+                                         int32_t b) {
+    if (dis) return dis[(size_t)a * (size_t)n + (size_t)b] == 2;
+    int64_t lo = adj_off[a], hi = adj_off[a + 1];
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        const int32_t v = adj[mid];
+        if (v == b) return true;
+        if (v < b)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return false;
+}
 
 constexpr int kOtfWaves = 2;                  // source nodes per workgroup (16 KB of LDS each; a workgroup's 32 KB plus its
                                               // few counter words let four workgroups share a CU's 160 KiB)

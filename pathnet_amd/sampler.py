@@ -435,6 +435,12 @@ class MerwSampler(_HopSource):
         same device tables, same sample() signature; p = inf is a non-backtracking walk."""
         return BiasedSampler(self, p, q)
 
+    def path_prob(self, ids):
+        """pathprob.path_prob(self, ids): the likelihood of the paths ids [..., W, L] under this sampler's own tables --
+        exact transition numerators over 2^62, their fp64 probabilities and every path's log-likelihood -> PathProb."""
+        from . import pathprob
+        return pathprob.path_prob(self, ids)
+
     def sample(self, W, seed, epoch_begin=0, epoch_count=1, node_begin=0, node_count=None,
                draw_source=DRAW_PHILOX, check=True, out=None, step_state=None, nodes=None):
         """-> ids int32 [epoch_count, node_count, W, L], codes uint8 [...] on the GPU.
@@ -519,6 +525,13 @@ class BiasedSampler:
 
     def walk_stats(self, ids, codes, **kw):
         return self.base.walk_stats(ids, codes, **kw)
+
+    def path_prob(self, ids, kind="realised"):
+        """pathprob.biased_path_prob(self, ids, kind): the likelihood of the paths under this second-order walk --
+        kind="realised": what sample() does, trial cap included; kind="target": the distribution it aims at -> PathProb
+        with the class masses and classes beside the numerators."""
+        from . import pathprob
+        return pathprob.biased_path_prob(self, ids, kind)
 
     def exhausted_steps(self):
         """Steps of the latest sample() that came to their 64th trial (one read-back); 0 before the first call."""
