@@ -86,7 +86,7 @@ typedef struct pn_context pn_context;
 int pn_context_create(pn_context **out);
 int pn_context_destroy(pn_context *ctx);
 /* Kernel-selection knobs for A/B measurements and tests (none changes a result beyond rounding): PN_NODE_GEMM3, PN_EVAL_ZW,
- * PN_POOL_STEP, PN_EVENT_DEVICE_SCOPE, PN_NODE_RGRAD, PN_SAMPLER_STAGE, PN_SEQ4, PN_SEQH_TAIL (pn_internal.h: struct Knobs).  A context
+ * PN_POOL_STEP, PN_EVENT_DEVICE_SCOPE, PN_NODE_RGRAD, PN_SAMPLER_STAGE, PN_SEQ4, PN_SEQH_TAIL, PN_FC0_SPARSE (pn_internal.h: struct Knobs).  A context
  * takes its values from the environment variables of the same names ONCE, in pn_context_create; afterwards only these two
  * calls read or change them -- device entry points never call getenv, so a captured step keeps its selection and a setenv
  * on another thread cannot race a launch.  get accepts ctx = NULL (the defaults a NULL context runs with). */
@@ -670,6 +670,48 @@ int pn_pagg_backward(pn_context *ctx, const pn_pagg_args *args, void *stream);
  * micro-batch's forward, loss gradient and backward follow each other on the tensors still in the workspace. */
 int pn_pagg_train_step(pn_context *ctx, const pn_pagg_args *args, const int64_t *target, float grad_scale, float *loss,
                        void *stream);
+
+/* ---- fc0 over prepared sparse features (pn_sparse.hip): bag-of-words X, its non-zeros extracted once -------------------
+ * Cora's feature matrix is 98.7 % zeros, and it is the dataset: the same tensor in every step of a training run.  Its
+ * structure is extracted ONCE into two indexes in device memory, and the three calls above then have a twin that takes
+ * them and runs fc0's forward and weight gradient over the non-zeros instead of the dense GEMMs.  Added without an ABI
+ * bump: five new symbols and one new struct, no existing struct or signature changed (pn_pagg_args is as it was: the
+ * features travel as an argument of their own), so pn_abi_version keeps answering 12.
+ *
+ * An element is a non-zero when x != 0.0f: -0.0f is not one, NaN and Inf are.
+ *   CSR: row_off int32 [N + 1]; col / val [nnz]: the features and values of row n at row_off[n] .. row_off[n + 1], features
+ *        ascending.
+ *   CSC: col_off int32 [F + 1]; row / valc [nnz]: the nodes and values of column f at col_off[f] .. col_off[f + 1], nodes
+ *        ascending.
+ * Two steps, because the caller owns every buffer: pn_sparse_count fills and scans both offset arrays (asynchronous); the
+ * caller reads nnz = row_off[N] (= col_off[F]) back, allocates the four [nnz] arrays and calls pn_sparse_fill, which
+ * writes them from the same X.  Positions come from integer counts and prefix sums alone: the same index in every run.
+ * Limits, PN_ERR_ARG before any launch: N, F >= 1 and N * F <= 2^28 (positions stay in int32; the build is a one-time
+ * cost and is not tuned: a lane per column walks the rows).  nnz = 0 is valid (the [nnz] pointers may then be NULL). */
+typedef struct pn_sparse_features {   /* device pointers, caller-owned */
+    int64_t nnz;
+    int32_t *row_off;                 /* [N + 1] */
+    int32_t *col;                     /* [nnz] */
+    float *val;                       /* [nnz] */
+    int32_t *col_off;                 /* [F + 1] */
+    int32_t *row;                     /* [nnz] */
+    float *valc;                      /* [nnz] */
+} pn_sparse_features;
+int pn_sparse_count(pn_context *ctx, const float *X, int32_t N, int32_t F, int32_t *row_off, int32_t *col_off, void *stream);
+int pn_sparse_fill(pn_context *ctx, const float *X, int32_t N, int32_t F, const pn_sparse_features *features, void *stream);
+/* pn_pagg_forward / pn_pagg_backward / pn_pagg_train_step with the prepared features of args->X (features = NULL: exactly
+ * those calls).  The caller vouches that the features were built from the X the call is given, with its N and F.  With them
+ *   Xh[n, :] = act(fc0_b + sum_k val_k * fc0_w[:, col_k])          fp32 FMAs in ascending feature order,
+ *   g_fc0_w[h, f] = sum over column f of valc * dXh'[n, h]          four interleaved partial sums added in a fixed order,
+ * g_fc0_b is the column sum of dXh' and g_X stays the dense GEMM.  Every sum has a fixed order, so the deterministic mode
+ * takes the same route.  The features are ignored -- the dense kernels run, unchanged -- when Xh_in is set, when the hidden
+ * size is above 256, and when the context knob PN_FC0_SPARSE is 0 (default 1; the A/B switch).  The one place where the
+ * routes differ beyond rounding: a zero of X times a non-finite weight is NaN on the dense route and absent here.  The
+ * forward transposes fc0_w into the workspace on every call (the weights change from step to step; X does not). */
+int pn_pagg_forward_sparse(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *features, void *stream);
+int pn_pagg_backward_sparse(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *features, void *stream);
+int pn_pagg_train_step_sparse(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *features,
+                              const int64_t *target, float grad_scale, float *loss, void *stream);
 
 /* Stand-alone stages of the same path, exposed for measurement and tests. */
 /* rows[q, t, :] = table[(node(q,t) * L + code(q,t)), :] for the variant's index plan: the

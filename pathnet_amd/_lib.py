@@ -72,6 +72,11 @@ class PaggArgs(ctypes.Structure):
                  ("out_embed", vp), ("out_path_weight", vp), ("out_path_state", vp), ("g_embed", vp)])
 
 
+class SparseFeatures(ctypes.Structure):
+    """struct pn_sparse_features: the non-zeros of a feature matrix as CSR (row_off, col, val) and CSC (col_off, row, valc)"""
+    _fields_ = [("nnz", ctypes.c_int64), ("row_off", vp), ("col", vp), ("val", vp), ("col_off", vp), ("row", vp), ("valc", vp)]
+
+
 class WalkStatsOut(ctypes.Structure):
     """struct pn_walk_stats_out: device pointers, None = not wanted"""
     FIELDS = ("step_code", "label_pairs", "unlabeled", "stay", "back", "distinct_hist", "unique_paths", "cover", "visits",
@@ -171,6 +176,12 @@ SIGNATURES = {
     "pn_linear_backward": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp,
                                           vp, vp, ctypes.c_int64, vp]),
     "pn_pagg_train_step": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), vp, ctypes.c_float, vp, vp]),
+    "pn_sparse_count": (ctypes.c_int, [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]),
+    "pn_sparse_fill": (ctypes.c_int, [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(SparseFeatures), vp]),
+    "pn_pagg_forward_sparse": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures), vp]),
+    "pn_pagg_backward_sparse": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures), vp]),
+    "pn_pagg_train_step_sparse": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures), vp,
+                                                 ctypes.c_float, vp, vp]),
     "pn_pagg_debug_offsets": (ctypes.c_int, [ctypes.POINTER(PaggShape), c_i64p]),
     "pn_pagg_range_offset": (ctypes.c_int, [ctypes.POINTER(PaggShape), c_i64p]),
     "pn_pagg_paths_stream": (ctypes.c_int, [vp, ctypes.POINTER(PaggShape), vp, ctypes.POINTER(ctypes.c_void_p)]),

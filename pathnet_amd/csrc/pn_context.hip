@@ -80,7 +80,8 @@ struct KnobName {
 const KnobName kKnobs[] = {{"PN_NODE_GEMM3", &pn::Knobs::node_gemm3}, {"PN_EVAL_ZW", &pn::Knobs::eval_zw},
                            {"PN_POOL_STEP", &pn::Knobs::pool_step}, {"PN_EVENT_DEVICE_SCOPE", &pn::Knobs::event_dev},
                            {"PN_NODE_RGRAD", &pn::Knobs::node_rgrad}, {"PN_SAMPLER_STAGE", &pn::Knobs::sampler_stage},
-                           {"PN_SEQ4", &pn::Knobs::seq4}, {"PN_SEQH_TAIL", &pn::Knobs::seqh_tail}};
+                           {"PN_SEQ4", &pn::Knobs::seq4}, {"PN_SEQH_TAIL", &pn::Knobs::seqh_tail},
+                           {"PN_FC0_SPARSE", &pn::Knobs::fc0_sparse}};
 
 }  // namespace
 

@@ -57,6 +57,7 @@ struct Knobs {
     int seq4 = 4;               // PN_SEQ4: bit 2 = the two-stage weight-gradient GEMM of pn_seq4.hip serves the bf16 mode at hid 128
     int seqh_tail = PN_SEQH_TAIL_DEFAULT;   // PN_SEQH_TAIL: 0 = 32-path tiles only (default); 1 = the remainder round of the fp16
                                 //                recurrent launches in smaller tiles, one per CU; 8 / 16 / 24 = that size, always
+    int fc0_sparse = 1;         // PN_FC0_SPARSE: a call that carries prepared sparse features uses them for fc0 (0: ignores them, the A/B switch)
 };
 const Knobs &knobs_of(const pn_context *ctx);
 

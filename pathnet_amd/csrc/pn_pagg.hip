@@ -42,6 +42,7 @@
 #include "pn_internal.h"
 #include "pn_kernels.h"
 #include "pn_seq.h"
+#include "pn_sparse.h"
 
 using namespace pn;
 
@@ -1451,6 +1452,7 @@ int make_dims(const pn_pagg_shape &s, Dims &d) {
 #define PN_WGRAD_CUS_SHARED 224    // (tuning builds 176 .. 240: profiles/r06_glue.txt section 11 -- 208 won while fc0's weight
 #endif                             //  gradient was a 150 us gemm_kernel launch beside it, 224 again once that ran on rgrad_kernel)
 constexpr int WGRAD_CUS_SHARED = PN_WGRAD_CUS_SHARED;   // CUs of the weight-gradient launch when something is meant to run beside it (of 256)
+// (a call over prepared sparse features keeps the same split: 232 .. 256 each lost ~30 us there, profiles/sparse_fc0.txt)
 // fc0's weight gradient runs on rgrad_kernel (16-byte row loads) also when F is not a multiple of 4 -- Cora's 1433 -- from a
 // copy of X with padded rows, made per backward (pad_rows_kernel: 2 x 15 MB at the headline shape, ~5 us, for a GEMM that
 // takes 150 us on the 48 CUs the recurrent weight gradient leaves it and ~60 as a row reduction).  Graphs from 2 048 nodes
@@ -1470,6 +1472,7 @@ struct WsLayout {
     size_t dx, keys, iota, skey, stmp, cpart, dsel, dds, datt, dgemm;  // deterministic backward (Dims.det)
     size_t okey, osrc;                  // its three destination orders, sorted once per micro-batch into one block each: segment
                                         // offsets are running sums over the segments present (det_params), nothing is laid out here
+    size_t w0t;                         // fc0_w transposed [F, H]: the sparse forward reads its rows (last: appended to the layout)
     size_t stmp_bytes;
     int wgrad_split, wgrad_tiles;
     size_t total;
@@ -1563,6 +1566,7 @@ WsLayout ws_layout(const Dims &d) {
         w.dds = take(Pb * 4);
         w.dgemm = take(std::max({det_gemm_floats(C, 2 * H), det_gemm_floats(d.compact ? H : L * H, H), det_gemm_floats(H, F)}) * 4);
     }
+    w.w0t = take(d.H <= 256 ? (size_t)d.F * H * 4 : 0);    // (sized by the shape alone: a call may or may not carry features)
     w.total = at;
     return w;
 }
@@ -1598,6 +1602,7 @@ struct Call {
     char *ws;
     const float *Xh;
     float *Z;
+    const pn_sparse_features *sp;       // prepared features of a->X that this call uses for fc0, or null: the dense kernels
     template <class T>
     T *at(size_t off) const { return reinterpret_cast<T *>(ws + off); }
     int groups(int b) const { return std::min(d.Sb, d.S - b * d.Sb); }                 // pooling groups of micro-batch b
@@ -1605,7 +1610,8 @@ struct Call {
     const int32_t *sel(int b) const { return a->sel + (a->index_rows_local ? (int64_t)b * d.Sb : group0(b)); }
 };
 
-int resolve_call(Call &c, pn_context *ctx, const pn_pagg_args *a, hipStream_t stream, const char *who) {
+int resolve_call(Call &c, pn_context *ctx, const pn_pagg_args *a, hipStream_t stream, const char *who,
+                 const pn_sparse_features *sp = nullptr) {
     if (!a) PN_FAIL(PN_ERR_ARG, "%s: null args", who);
     if (int rc = context_check_device(ctx)) return rc;
     if (int rc = make_dims(a->shape, c.d)) return rc;
@@ -1620,6 +1626,8 @@ int resolve_call(Call &c, pn_context *ctx, const pn_pagg_args *a, hipStream_t st
     c.ws = reinterpret_cast<char *>(a->workspace);
     c.Xh = a->Xh_in ? a->Xh_in : c.at<const float>(c.w.Xh);
     c.Z = c.at<float>(c.w.Z);
+    // prepared features serve fc0 where the library runs it itself, at the fused hidden sizes; PN_FC0_SPARSE = 0 ignores them
+    c.sp = (sp && !a->Xh_in && c.d.H <= 256 && (int64_t)c.d.N * c.d.F <= SPARSE_MAX_ELEMS && knobs_of(ctx).fc0_sparse != 0) ? sp : nullptr;
     if (a->index_rows_local && c.d.variant == PN_VARIANT_HETERO && (c.d.group_begin != 0 || c.d.S != c.d.S_total))
         PN_FAIL(PN_ERR_ARG, "%s: the hetero class reads paths of the whole batch (PathNet_run.py:196-197): "
                 "index_rows_local needs the whole batch's ids / codes", who);
@@ -1966,7 +1974,11 @@ int run_tables(const Call &c, JoinGuard &joiner, ZeroFill *zero_fill = nullptr) 
             g.bias = a->fc0_b;
             g.relu = homo;
             g.clear_word = epi_range ? &c.at<SeqRange>(c.w.range)->x : nullptr;     // (epi_range: never with gemm3)
-            if (gemm3_pays(c.ctx, d.N, H, d.F, G3_FC0)) {          // large graphs: fp32 results from the bf16 matrix pipe (six MFMAs per product)
+            if (c.sp) {         // prepared features: the non-zeros of a row against rows of fc0_w^T, same epilogue
+                float *W0T = c.at<float>(c.w.w0t);
+                if (int rc = launch_transpose(stream, a->fc0_w, H, d.F, W0T)) return rc;
+                if (int rc = launch_sparse_fc0_fwd(stream, *c.sp, d.N, H, W0T, g.bias, g.relu, g.clear_word, g.C)) return rc;
+            } else if (gemm3_pays(c.ctx, d.N, H, d.F, G3_FC0)) {          // large graphs: fp32 results from the bf16 matrix pipe (six MFMAs per product)
                 if (int rc = launch_gemm3(stream, gemm3_of(g))) return rc;
             } else if (int rc = launch_gemm_split(stream, g, c.at<float>(c.w.gpart)))
                 return rc;
@@ -2486,7 +2498,12 @@ int run_fc0_bwd(const Call &c, const float *dXh) {
     g.gateA = xgate;
     g.rowsum = a->g_fc0_b;
     g.mode = GEMM_ATOMIC;
-    if (a->g_fc0_w && d.det) {
+    if (a->g_fc0_w && c.sp) {       // prepared features: a column's entries in a fixed order (deterministic mode included)
+        // (the bias gradient rides along as extra workgroups of the launch; fixed-order mode: the one-add-per-output column sum)
+        if (int rc = launch_sparse_fc0_wgrad(stream, *c.sp, d.N, d.F, H, dXh, xgate, a->g_fc0_w, d.det ? nullptr : a->g_fc0_b)) return rc;
+        if (a->g_fc0_b && d.det)
+            if (int rc = launch_colsum(stream, dXh, xgate, H, d.N, H, a->g_fc0_b, true)) return rc;
+    } else if (a->g_fc0_w && d.det) {
         if (int rc = launch_gemm_det(stream, g, (d.N + 255) / 256, c.at<float>(c.w.dgemm))) return rc;
     } else if (a->g_fc0_w && d.F % 4 == 0 && rgrad_pays(ctx, d.N, H, d.F)) {
         const RgradParams rp{dXh, xgate, a->X, H, d.F, d.N, H, d.F, a->g_fc0_w, d.F, a->g_fc0_b, nullptr, nullptr};
@@ -2604,10 +2621,14 @@ int pn_pagg_gather(pn_context *ctx, const pn_pagg_shape *shape, const float *tab
     return PN_OK;
 }
 
-int pn_pagg_forward(pn_context *ctx, const pn_pagg_args *a, void *stream_) {
+int pn_pagg_forward(pn_context *ctx, const pn_pagg_args *a, void *stream) {
+    return pn_pagg_forward_sparse(ctx, a, nullptr, stream);
+}
+
+int pn_pagg_forward_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     Call c;
-    if (int rc = resolve_call(c, ctx, a, stream, "pn_pagg_forward")) return rc;
+    if (int rc = resolve_call(c, ctx, a, stream, "pn_pagg_forward", sp)) return rc;
     const Dims &d = c.d;
     if (int rc = check_forward_args(c, "pn_pagg_forward")) return rc;
     if (d.S == 0) return PN_OK;
@@ -2630,11 +2651,11 @@ int pn_pagg_forward(pn_context *ctx, const pn_pagg_args *a, void *stream_) {
 // pn_pagg_backward, and -- with `target` -- pn_pagg_train_step: the forward of every micro-batch runs right before its
 // backward (saved tensors in place), the loss gradient of its rows is formed in between
 static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stream_, const int64_t *target, float grad_scale,
-                              float *loss) {
+                              float *loss, const pn_sparse_features *sp) {
     hipStream_t stream = (hipStream_t)stream_;
     const bool fused = target != nullptr;
     Call c;
-    if (int rc = resolve_call(c, ctx, a, stream, fused ? "pn_pagg_train_step" : "pn_pagg_backward")) return rc;
+    if (int rc = resolve_call(c, ctx, a, stream, fused ? "pn_pagg_train_step" : "pn_pagg_backward", sp)) return rc;
     const Dims &d = c.d;
     if (fused) {
         if (d.S > 0)
@@ -2765,11 +2786,20 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
 }
 
 int pn_pagg_backward(pn_context *ctx, const pn_pagg_args *a, void *stream) {
-    return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr);
+    return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, nullptr);
+}
+
+int pn_pagg_backward_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, void *stream) {
+    return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp);
 }
 
 int pn_pagg_train_step(pn_context *ctx, const pn_pagg_args *a, const int64_t *target, float grad_scale, float *loss,
                        void *stream) {
+    return pn_pagg_train_step_sparse(ctx, a, nullptr, target, grad_scale, loss, stream);
+}
+
+int pn_pagg_train_step_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const int64_t *target,
+                              float grad_scale, float *loss, void *stream) {
     if (!a) PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step: null args");
     if (a->out_embed || a->out_path_weight || a->out_path_state || a->g_embed)
         PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step: out_embed / out_path_weight / out_path_state / g_embed are for pn_pagg_forward / "
@@ -2777,9 +2807,9 @@ int pn_pagg_train_step(pn_context *ctx, const pn_pagg_args *a, const int64_t *ta
     if (!loss || (a->shape.S > 0 && !target)) PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step: null target / loss");
     if (a->shape.S == 0) {          // nothing to aggregate: zero loss, zero gradients
         PN_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float), (hipStream_t)stream));
-        return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr);
+        return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp);
     }
-    return pagg_backward_impl(ctx, a, stream, target, grad_scale, loss);
+    return pagg_backward_impl(ctx, a, stream, target, grad_scale, loss, sp);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@ fallback -- if the library is missing, construction fails.
 import collections
 import ctypes
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -85,12 +86,12 @@ class PaggCall:
                     "deterministic", "compact", "seq_math")
     __slots__ = SHAPE_FIELDS + ("p_seq", "p_cls", "seed", "mask_seq", "mask_cls", "step_state", "index_rows_local", "bank_w",
                                 "bank_b", "grad", "reuse_tables", "grad_scale", "path_state", "sparse_plan", "workspace",
-                                "_shape", "_ws_bytes")
+                                "features", "_shape", "_ws_bytes")
 
     def __init__(self, variant, N, F, H, C, S, W, L, S_total=0, group_begin=0, batch_groups=0, cell=None, deterministic=False,
                  compact=None, seq_math=None, *, p_seq=0.0, p_cls=0.0, seed=0, mask_seq=None, mask_cls=None, step_state=None,
                  index_rows_local=False, bank_w=None, bank_b=None, grad=True, reuse_tables=0, grad_scale=1.0,
-                 path_state=False, sparse_plan=None, workspace=None):
+                 path_state=False, sparse_plan=None, workspace=None, features=None):
         self.variant, self.N, self.F, self.H, self.C, self.S, self.W, self.L = variant, N, F, H, C, S, W, L
         self.S_total, self.group_begin, self.batch_groups, self.cell = S_total, group_begin, batch_groups, cell
         # decisions that shape the workspace are taken once per call and travel with its shape
@@ -103,6 +104,7 @@ class PaggCall:
         # workspace are valid, 2: Xh only
         self.grad, self.reuse_tables, self.grad_scale, self.path_state = grad, reuse_tables, grad_scale, path_state
         self.sparse_plan, self.workspace = sparse_plan, workspace
+        self.features = features        # PreparedFeatures of the call's X (fc0 over its non-zeros), or None: the dense kernels
         self._shape = self._ws_bytes = None
 
     def get(self, name, default=None):
@@ -145,6 +147,10 @@ class PaggCall:
         if have is not None and have.numel() >= need and have.device == dev:
             return have
         return torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+
+    def features_ref(self):
+        """the call's pn_sparse_features for the pn_pagg_*_sparse entry points (None = NULL: the plain calls)"""
+        return ctypes.byref(self.features.c) if self.features is not None else None
 
     def args(self, ids, codes, sel, p, X=None, Xh=None):
         """A _lib.PaggArgs with the call's inputs: shape, index arrays, parameters (p: _split_params), dropout, flags.
@@ -189,6 +195,50 @@ class PaggCall:
         gX = torch.empty_like(X) if X is not None else None
         a.g_X = gX.data_ptr() if gX is not None else None
         return grads, gX, buf
+
+
+SPARSE_MAX_ELEMS = 1 << 28      # pn_sparse_count's limit: positions of the non-zeros stay in int32
+SPARSE_CACHE_ENTRIES = 4        # prepared feature matrices a module keeps (train / validation / test splits share one X)
+SPARSE_DENSE_KEYS = 16          # keys remembered as dense (no tensor is kept for them)
+SPARSE_SEEN_KEYS = 8            # keys seen once and not looked at yet (after SPARSE_MISS_LIMIT misses)
+SPARSE_MISS_LIMIT = 2           # scanned matrices in a row that never came back before first sights stop being scanned
+
+
+class PreparedFeatures:
+    """The non-zeros of a feature matrix X [N, F] (fp32, contiguous, on the GPU) as the library's pn_sparse_features: CSR
+    (row_off, col, val: features ascending in a row) and CSC (col_off, row, valc: nodes ascending in a column), built by
+    pn_sparse_count / pn_sparse_fill.  count() costs one launch chain and ONE host read (nnz); fill() allocates exactly.
+    The object keeps X alive: while it exists no other tensor can take X's address."""
+    __slots__ = ("X", "nnz", "row_off", "col_off", "col", "val", "row", "valc", "c", "pinned")
+
+    def __init__(self, X):
+        N, F = X.shape
+        dev = X.device
+        self.X = X
+        with torch.cuda.device(dev):
+            self.row_off = torch.empty(N + 1, dtype=torch.int32, device=dev)
+            self.col_off = torch.empty(F + 1, dtype=torch.int32, device=dev)
+            _lib.check(_lib.load().pn_sparse_count(_lib.context(dev), X.data_ptr(), N, F, self.row_off.data_ptr(),
+                                                   self.col_off.data_ptr(), _lib.stream_ptr(dev)))
+            self.nnz = int(self.row_off[N].item())
+        self.col = self.val = self.row = self.valc = self.c = None
+        self.pinned = False         # handed to a call while its stream was being captured
+
+    def density(self):
+        return self.nnz / float(self.X.shape[0] * self.X.shape[1])
+
+    def fill(self):
+        N, F = self.X.shape
+        dev = self.X.device
+        with torch.cuda.device(dev):
+            # (zeros: an entry the fill does not reach -- X written to between count and fill -- is feature / node 0 with value 0)
+            self.col, self.row = (torch.zeros(self.nnz, dtype=torch.int32, device=dev) for _ in range(2))
+            self.val, self.valc = (torch.zeros(self.nnz, dtype=torch.float32, device=dev) for _ in range(2))
+            self.c = _lib.SparseFeatures(self.nnz, self.row_off.data_ptr(), self.col.data_ptr(), self.val.data_ptr(),
+                                         self.col_off.data_ptr(), self.row.data_ptr(), self.valc.data_ptr())
+            _lib.check(_lib.load().pn_sparse_fill(_lib.context(dev), self.X.data_ptr(), N, F, ctypes.byref(self.c),
+                                                  _lib.stream_ptr(dev)))
+        return self
 
 
 def _shape(variant, N, F, H, C, S, W, L, S_total=0, group_begin=0, batch_groups=0, cell=None, deterministic=False,
@@ -294,7 +344,8 @@ class _PaggFunction(torch.autograd.Function):
                 a.out_embed, a.out_path_weight = encode_out[0].data_ptr(), encode_out[1].data_ptr()
                 a.out_path_state = encode_out[2].data_ptr() if encode_out[2] is not None else None
             if call.S > 0:
-                _lib.check(_lib.load().pn_pagg_forward(_lib.context(dev), ctypes.byref(a), _lib.stream_ptr(dev)))
+                _lib.check(_lib.load().pn_pagg_forward_sparse(_lib.context(dev), ctypes.byref(a), call.features_ref(),
+                                                              _lib.stream_ptr(dev)))
         ctx.call, ctx.ws = call, ws
         ctx.present = [t is not None for t in params]
         ctx.save_for_backward(X, ids, codes, sel, *[t for t in params if t is not None])
@@ -327,7 +378,8 @@ class _PaggFunction(torch.autograd.Function):
             a.g_out = g_out.data_ptr() if g_out is not None else None
             a.g_embed = g_embed.data_ptr() if g_embed is not None else None
             if call.S > 0:
-                _lib.check(_lib.load().pn_pagg_backward(_lib.context(dev), ctypes.byref(a), _lib.stream_ptr(dev)))
+                _lib.check(_lib.load().pn_pagg_backward_sparse(_lib.context(dev), ctypes.byref(a), call.features_ref(),
+                                                               _lib.stream_ptr(dev)))
             else:
                 for g in list(grads.values()) + [gX] * (gX is not None):
                     g.zero_()
@@ -378,8 +430,9 @@ class _PaggLossFunction(torch.autograd.Function):
             grads, gX, flat = call.grad_buffers(a, p, X if ctx.needs_input_grad[1] else None, flat=True)
             target = target.to(device=dev, dtype=torch.int64).contiguous()
             if call.S > 0:
-                _lib.check(_lib.load().pn_pagg_train_step(_lib.context(dev), ctypes.byref(a), target.data_ptr(),
-                                                          float(call.grad_scale), loss.data_ptr(), _lib.stream_ptr(dev)))
+                _lib.check(_lib.load().pn_pagg_train_step_sparse(_lib.context(dev), ctypes.byref(a), call.features_ref(),
+                                                                 target.data_ptr(), float(call.grad_scale), loss.data_ptr(),
+                                                                 _lib.stream_ptr(dev)))
             else:
                 flat.zero_()
                 if gX is not None:
@@ -501,6 +554,30 @@ class _Aggregator(nn.Module):
         self._range_calls = 0
         self._range_pending = None        # (pinned int32[6], event) of a read-back in flight
         self.range_spread_bits = None     # last evaluated spread: exponent(max |Z|) - mean exponent of the sampled tiles
+        # fc0 over the non-zeros of X (pn_sparse.hip), for the resident dataset matrix.  A matrix is looked at ONCE, when its
+        # key (address, shape, in-place version, device) is first seen and it has at least sparse_min_nodes rows and at most 2^28
+        # elements: a count launch and one host read.  It is prepared when its density is at most sparse_max_density, else
+        # remembered as dense and not scanned again.  A caller whose X is a new tensor, or a new version, in every call would pay
+        # that scan per call: when SPARSE_MISS_LIMIT scanned matrices in a row have not come back, scanning at first sight stops
+        # (two scans at the most), and a matrix is then looked at only when the same tensor object comes back unchanged.
+        # "never": always the dense kernels; "always": prepared at first sight, no size / density gate (small tests).
+        # While the stream is being captured an unprepared X is not prepared: that call runs dense.  Calls that compute a part
+        # of a batch (group_slice, batch_position: the runners of pathnet_amd.dist) always run dense.  Same convention as
+        # _tables_key: a write to X that bypasses its version counter (X.data, a raw kernel) is not seen.
+        # At most SPARSE_CACHE_ENTRIES prepared matrices are kept, each with its X; the oldest makes room for a new one, except
+        # that an entry a captured graph was given stays for as long as the module lives (with four of those, a fifth matrix
+        # runs dense).
+        self.sparse_features = "auto"
+        self.sparse_min_nodes = 2048      # the floor of the row-reduction kernel the dense weight gradient uses (rgrad_pays)
+        self.sparse_max_density = 1.0 / 64  # (profiles/sparse_fc0.txt: Cora's 1.3 % is inside, Pubmed's 10 % TF-IDF rows are not)
+        self._sparse_cache = collections.OrderedDict()     # key -> PreparedFeatures
+        self._sparse_dense = collections.OrderedDict()     # keys looked at and found too dense
+        self._sparse_seen = collections.OrderedDict()      # key -> weak reference to the tensor seen once under it
+        self.sparse_scans = 0             # matrices counted so far (each is a launch chain and a host read)
+        self._sparse_misses = 0           # scanned matrices in a row that did not come back
+        self._sparse_scan_open = False    # the matrix scanned last has not been seen again yet
+        self.fc0_route = None             # "sparse" / "dense": what the last call handed to the library
+        self.fc0_route_calls = {"sparse": 0, "dense": 0}
         self._mask_seq = None     # test hook: explicit dropout masks (reference order)
         self._mask_cls = None
         self._bank_flat = (None, None)
@@ -521,6 +598,61 @@ class _Aggregator(nn.Module):
         lins = [self.fc0] + list(self._bank_layers())
         return (X.data_ptr(), tuple(X.shape), int(X._version), int(L),
                 tuple(int(t._version) for l in lins for t in (l.weight, l.bias)))
+
+    def _features_for(self, X, Hk):
+        """PreparedFeatures for this call's X, or None for the dense route (see _common_init)"""
+        mode = self.sparse_features
+        if mode not in ("auto", "never", "always"):
+            raise ValueError("sparse_features: auto, never or always")
+        N, F = X.shape
+        if mode == "never" or Hk > 256 or N * F == 0 or N * F > SPARSE_MAX_ELEMS:
+            return None
+        key = (X.data_ptr(), (N, F), int(X._version), X.device)
+        cache, capturing = self._sparse_cache, torch.cuda.is_current_stream_capturing()
+        feat = cache.get(key)
+        if feat is not None:
+            cache.move_to_end(key)
+            feat.pinned = feat.pinned or capturing      # a captured graph holds its pointers: never evicted from here on
+            self._sparse_misses, self._sparse_scan_open = 0, False
+            return feat
+        if mode == "auto" and key in self._sparse_dense:
+            self._sparse_misses, self._sparse_scan_open = 0, False
+            return None
+        if capturing or (mode == "auto" and N < self.sparse_min_nodes):
+            return None             # (a capture remembers nothing: the next eager call looks at X)
+        if mode == "auto" and self._sparse_scan_open:   # the matrix scanned last never came back: a miss
+            self._sparse_misses += 1
+            self._sparse_scan_open = False
+        if mode == "auto" and self._sparse_misses >= SPARSE_MISS_LIMIT:
+            # X is not a resident matrix here -- a fresh tensor per step (feature dropout, a gathered sub-matrix) or one that
+            # changes in place every step: the scans stop.  From now on the first sight of a key costs nothing, it is only noted,
+            # with a weak reference to the tensor, and a matrix is scanned when the same tensor object comes back unchanged
+            seen = self._sparse_seen.pop(key, None)
+            if seen is None or seen() is not X:
+                self._sparse_seen[key] = weakref.ref(X)
+                while len(self._sparse_seen) > SPARSE_SEEN_KEYS:
+                    self._sparse_seen.popitem(last=False)
+                return None
+        if len(cache) >= SPARSE_CACHE_ENTRIES:          # room: the oldest entry no captured graph has been given, if there is one
+            old = next((k for k, f in cache.items() if not f.pinned), None)
+            if old is None:
+                return self._remember_dense(key)
+        feat = PreparedFeatures(X)
+        self.sparse_scans += 1
+        self._sparse_scan_open = mode == "auto"
+        if mode == "auto" and feat.density() > self.sparse_max_density:
+            return self._remember_dense(key)
+        if len(cache) >= SPARSE_CACHE_ENTRIES:
+            del cache[old]
+        cache[key] = feat.fill()
+        return feat
+
+    def _remember_dense(self, key):
+        """a verdict costs no slot of the prepared matrices: keys only, the oldest forgotten first"""
+        self._sparse_dense[key] = True
+        while len(self._sparse_dense) > SPARSE_DENSE_KEYS:
+            self._sparse_dense.popitem(last=False)
+        return None
 
     def _make_cell(self, default):
         """the recurrent sub-module, under the attribute name torch users expect (LSTM / RNN / GRU); none for mean / sum"""
@@ -732,6 +864,7 @@ class _Aggregator(nn.Module):
         dev = X.device
         if dev.type != "cuda":
             raise RuntimeError("pathnet_amd aggregators run on the GPU only (X is on %s); no CPU fallback" % dev)
+        X_given = X
         X = X.contiguous().float()
         ids, codes, sel, S = _as_index_tensors(neis, layer_type, indices, num_w, walk_len, dev, n_nodes=X.shape[0])
         H, L = self.hidden_size, int(walk_len)
@@ -775,6 +908,11 @@ class _Aggregator(nn.Module):
                         self._cell_kind, det, compact, math, p_seq=p_drop, p_cls=p_drop, seed=seed, mask_seq=ms, mask_cls=mc,
                         step_state=self.step_state, index_rows_local=batch_position is not None, bank_w=fw, bank_b=fb,
                         grad=grad, path_state=bool(_encode))
+        # (a converted copy of X is a new tensor in every call: nothing to remember it by)
+        whole = batch_position is None and group_slice is None
+        call.features = self._features_for(X, Hk) if (X is X_given and S > 0 and whole) else None
+        self.fc0_route = "sparse" if call.features is not None else "dense"
+        self.fc0_route_calls[self.fc0_route] += 1
         call.pick_batch_groups(self.workspace_budget, dev)
         self._last_shape = (call.shape(), dev)       # (paths_stream: where the NEXT call of this shape reads its paths)
         if not grad:

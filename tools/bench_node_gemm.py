@@ -2,7 +2,12 @@
 pn_linear_forward / pn_gemm_f32 / pn_linear_backward at the headline (Cora) and Pubmed shapes, HIP events around blocks of
 launches.  Used for the A/Bs of gemm_kernel variants in round 6 (the 32 x 32-tile bf16 x 3 kernel, the split-K target, two K
 tiles in flight: profiles/r06_node_gemm.txt, r06_glue.txt sections 16-17), run against two builds of the library
-(PN_LIB_PATH).   python tools/bench_node_gemm.py [reps]"""
+(PN_LIB_PATH).   python tools/bench_node_gemm.py [reps]
+
+    python tools/bench_node_gemm.py sparse [steps]
+fc0 over prepared sparse features against the dense kernels (profiles/sparse_fc0.txt: the density threshold): the fc0 and
+fc0_bwd stages of a training step, bracketed one by one (pn_profile_configure mode 1: stages back to back on one stream), with
+module.sparse_features "never" and "always" at F = 1433 (N = 2708) and F = 500 (N = 19717) over a range of densities."""
 import json
 import os
 import sys
@@ -30,7 +35,60 @@ def timed(fn, reps):
     return round(best[len(best) // 2], 2)
 
 
+def stage_ms(lib, ctx, fn, steps):
+    """{stage name: ms per call} of `steps` calls of fn with every stage bracketed"""
+    import ctypes
+    n = lib.pn_profile_stage_count()
+    names = [lib.pn_profile_stage_name(i).decode() for i in range(n)]
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    _lib.check(lib.pn_profile_configure(ctx, 1, 0))
+    for _ in range(steps):
+        fn()
+    ms, cnt = (ctypes.c_double * n)(), (ctypes.c_int64 * n)()
+    _lib.check(lib.pn_profile_read(ctx, ms, cnt))
+    _lib.check(lib.pn_profile_configure(ctx, 0, 0))
+    return {names[i]: ms[i] / cnt[i] for i in range(n) if cnt[i]}
+
+
+def sparse_table(steps):
+    import pathnet_amd
+    lib = _lib.load()
+    ctx = _lib.context("cuda")
+    H, C, L, S, W = 128, 7, 4, 256, 8
+    out = {}
+    for F, N in ((1433, 2708), (500, 19717)):
+        torch.manual_seed(F)
+        m = pathnet_amd.PathNet_homo(F, H, C, L, dropout=0.5).cuda().train()
+        m.range_guard = False
+        ids = torch.randint(0, N, (S, W * L), dtype=torch.int32, device="cuda")
+        sel = torch.arange(S, dtype=torch.int32, device="cuda")
+        ids[:, 0::L] = sel[:, None]
+        codes = torch.randint(0, L, (S, W, L), dtype=torch.uint8, device="cuda")
+        y = torch.randint(0, C, (S,), device="cuda")
+        for density in (0.005, 0.013, 0.02, 0.03, 0.06, 0.12):
+            X = ((torch.rand(N, F, device="cuda") < density).float() * torch.rand(N, F, device="cuda")).contiguous()
+            row = {}
+            for mode in ("never", "always"):
+                m.sparse_features = mode
+
+                def step():
+                    m.zero_grad(set_to_none=True)
+                    loss, _ = m.forward_loss(X, ids, W, L, sel, codes, y, fused=True)
+                    loss.backward()
+                st = stage_ms(lib, ctx, step, steps)
+                row[mode] = {"fc0_us": round(st["fc0"] * 1e3, 2), "fc0_bwd_us": round(st["fc0_bwd"] * 1e3, 2)}
+            row["ratio_fwd"] = round(row["always"]["fc0_us"] / row["never"]["fc0_us"], 3)
+            row["ratio_bwd"] = round(row["always"]["fc0_bwd_us"] / row["never"]["fc0_bwd_us"], 3)
+            out["F%d_d%g" % (F, density)] = row
+            print("F=%d N=%d density %.3f  %s" % (F, N, density, json.dumps(row)), flush=True)
+    print("RESULT " + json.dumps(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "sparse":
+        return sparse_table(int(sys.argv[2]) if len(sys.argv) > 2 else 20)
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     lib = _lib.load()
     ctx = _lib.context("cuda")
