@@ -667,7 +667,9 @@ int pn_pagg_backward(pn_context *ctx, const pn_pagg_args *args, void *stream);
  * target: dev int64 [S] class indices of the slice's rows; loss: dev float.  Same values as pn_pagg_forward +
  * pn_cross_entropy + pn_pagg_backward; what it saves is the second forward of every micro-batch: with batch_groups > 0
  * pn_pagg_forward keeps no per-path tensors and pn_pagg_backward has to re-run each micro-batch's recurrence, here a
- * micro-batch's forward, loss gradient and backward follow each other on the tensors still in the workspace. */
+ * micro-batch's forward, loss gradient and backward follow each other on the tensors still in the workspace.
+ * A target outside [0, C) is handled as by pn_cross_entropy: *loss is NaN, the row's d loss / d logits is zero (every
+ * gradient stays finite: the recurrent kernels' range scaling is not specified for non-finite values), no ignore_index. */
 int pn_pagg_train_step(pn_context *ctx, const pn_pagg_args *args, const int64_t *target, float grad_scale, float *loss,
                        void *stream);
 
@@ -762,7 +764,11 @@ int pn_merw_probabilities(int32_t n, int64_t nnz, const int64_t *row_off, const 
 /* ---- training-step glue: the loss and the optimizer of PathNet_run.py:295-297, :346-352 ------
  * Mean softmax cross entropy over `rows` rows of `classes` logits (torch.nn.CrossEntropyLoss(), :297; int64 class
  * targets, no ignore_index / label smoothing -- the reference uses neither): *loss (device float) receives the mean,
- * g_logits [rows, classes] (may be NULL) d loss / d logits = (softmax - onehot) / rows. */
+ * g_logits [rows, classes] (may be NULL) d loss / d logits = (softmax - onehot) / rows.  The log softmax is formed as
+ * (x - max) - log(sum exp(x - max)): its error does not grow with the size of the logits.
+ * A target outside [0, classes) -- the -1 that graph datasets give unlabelled nodes, torch's ignore_index = -100, which is
+ * NOT implemented -- is never used as an index: its row contributes NaN to the loss (so *loss is NaN) and zeros to its
+ * row of g_logits.  Filter such rows out before the call. */
 int pn_cross_entropy(const float *logits, const int64_t *target, int32_t rows, int32_t classes, float *loss,
                      float *g_logits, void *stream);
 

@@ -813,11 +813,17 @@ __global__ __launch_bounds__(256) void pool_step_kernel(PoolStepParams p) {
         for (int c = 1; c < classes; c++) m = fmaxf(m, x[c]);
         float sum = 0.0f;
         for (int c = 0; c < classes; c++) sum += expf(x[c] - m);
-        const float lse = m + logf(sum);
-        const int t = (int)p.target[g];
-        p.lossg[g] = lse - x[t];
+        const float ls = logf(sum);
+        const int64_t t64 = p.target[g];        // out of range: NaN loss, zero gradient row, no address formed from it
+        const bool ok = t64 >= 0 && t64 < (int64_t)classes;
+        const int t = ok ? (int)t64 : 0;
+        const float row = ls - (x[t] - m);
+        p.lossg[g] = ok ? row : NAN;
         float *go = p.gout + (int64_t)g * classes;
-        for (int c = 0; c < classes; c++) go[c] = (expf(x[c] - lse) - (c == t ? 1.0f : 0.0f)) * p.scale;
+        for (int c = 0; c < classes; c++) {
+            const float gv = (expf((x[c] - m) - ls) - (c == t ? 1.0f : 0.0f)) * p.scale;
+            go[c] = ok ? gv : 0.0f;
+        }
     }
     __syncthreads();
     pool_bwd_wg_body<HI>(p.b, lds);
@@ -864,7 +870,11 @@ __global__ __launch_bounds__(256, 6) void pool_step2_kernel(PoolStepParams p) { 
     // (the node's own row of Xh, its target and the attention weights are asked for here as well, with the rows: loaded where they
     //  are used they were two more dependent round trips behind barriers)
     const int sel_g = min(max(f.sel[g], 0), f.N - 1);
-    const int tgt = (int)p.target[g];
+    // (a target outside [0, C): NaN loss, zero gradient row; the index into lg[] is clamped -- selects, no branch, no address
+    //  formed from it.  Workgroup-uniform: scalar registers)
+    const int64_t tgt64 = p.target[g];
+    const bool tgt_ok = tgt64 >= 0 && tgt64 < (int64_t)C;
+    const int tgt = tgt_ok ? (int)tgt64 : 0;
     int same = 1;
     const float *hn_g = f.hn + s0 * H;          // (a scalar base + one 32-bit offset per load: twenty 64-bit addresses would not fit)
     // Every load below is unconditional (clamped addresses) and its value always used -- rows past W / columns past H are zeroed by a
@@ -1029,14 +1039,15 @@ __global__ __launch_bounds__(256, 6) void pool_step2_kernel(PoolStepParams p) { 
         m = wave_max(m);
         float sum = 0.0f;
         for (int c = lane; c < C; c += 64) sum += expf(lg[c] - m);
-        const float lse = m + logf(wave_sum_u(sum));
+        const float ls = logf(wave_sum_u(sum));
         const int t = tgt;
-        if (lane == 0) p.lossg[g] = lse - lg[t];
+        const float row = ls - (lg[t] - m);
+        if (lane == 0) p.lossg[g] = tgt_ok ? row : NAN;
         float *go = p.gout + (int64_t)g * C;
         for (int c = lane; c < C; c += 64) {
-            const float gv = (expf(lg[c] - lse) - (c == t ? 1.0f : 0.0f)) * p.scale;
-            go[c] = gv;
-            lg[C + c] = gv;
+            const float gv = (expf((lg[c] - m) - ls) - (c == t ? 1.0f : 0.0f)) * p.scale;
+            go[c] = tgt_ok ? gv : 0.0f;
+            lg[C + c] = tgt_ok ? gv : 0.0f;
         }
     }
     __syncthreads();

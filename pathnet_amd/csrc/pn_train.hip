@@ -27,12 +27,22 @@ __global__ __launch_bounds__(1024) void cross_entropy_kernel(const float *__rest
         for (int c = 1; c < classes; c++) m = fmaxf(m, x[c]);
         float s = 0.0f;
         for (int c = 0; c < classes; c++) s += expf(x[c] - m);
-        const float lse = m + logf(s);
-        const int t = (int)target[r];
-        mine += lse - x[t];
+        // log softmax as (x - m) - log(s): both terms are small whatever the size of the logits.  m + log(s) would be rounded
+        // at the magnitude of the largest logit and every probability would carry ulp(max |x|) / 2 of relative error.
+        const float ls = logf(s);
+        // A target outside [0, classes) poisons the loss (NaN) and leaves a zero gradient row; no address is formed from
+        // it: a clamped index and selects, no branch around a load (pool_step2_kernel, pn_pagg.hip, has the same lines)
+        const int64_t t64 = target[r];
+        const bool ok = t64 >= 0 && t64 < (int64_t)classes;
+        const int t = ok ? (int)t64 : 0;
+        const float row = ls - (x[t] - m);
+        mine += ok ? row : NAN;
         if (g_logits) {
             float *g = g_logits + (int64_t)r * classes;
-            for (int c = 0; c < classes; c++) g[c] = (expf(x[c] - lse) - (c == t ? 1.0f : 0.0f)) * inv_rows;
+            for (int c = 0; c < classes; c++) {
+                const float gv = (expf((x[c] - m) - ls) - (c == t ? 1.0f : 0.0f)) * inv_rows;
+                g[c] = ok ? gv : 0.0f;
+            }
         }
     }
 #pragma unroll

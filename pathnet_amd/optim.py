@@ -69,7 +69,11 @@ def cross_entropy(logits, target):
 
 
 class CrossEntropyLoss(torch.nn.Module):
-    """Drop-in for ``torch.nn.CrossEntropyLoss()`` as the reference constructs it (PathNet_run.py:297)."""
+    """Drop-in for ``torch.nn.CrossEntropyLoss()`` as the reference constructs it (PathNet_run.py:297): the mean over all
+    rows, no class weights, no label smoothing and NO ``ignore_index``.  Every target must lie in ``[0, classes)``.  A row
+    whose target does not -- the ``-1`` of an unlabelled node, torch's default ``ignore_index = -100`` -- is not skipped:
+    it poisons the loss (NaN, so the mistake cannot go unnoticed) and gets a zero gradient row; the kernel never indexes
+    with it.  ``forward_loss(..., fused=True)`` of the modules behaves the same.  Select the labelled rows first."""
 
     def forward(self, logits, target):
         return cross_entropy(logits, target)

@@ -29,7 +29,8 @@ MODES = (("registers", 1, False), ("pool_step", 2, False), ("three_launches", 0,
 class Case:
     """A module, a batch of S masked nodes with W paths each, targets 0 and C - 1 among them, explicit dropout masks."""
 
-    def __init__(self, variant, S, W, H, C, cell=None, seed=0, split_ego=False, fc2_scale=None, loss_weight=1.0, micro=0):
+    def __init__(self, variant, S, W, H, C, cell=None, seed=0, split_ego=False, fc2_scale=None, loss_weight=1.0, micro=0,
+                 min_logit=None):
         import pathnet_amd
         torch.manual_seed(seed)
         rng = np.random.default_rng(seed)
@@ -58,6 +59,7 @@ class Case:
         self.mask_seq = (torch.rand(L, S * W, H) < 0.5).float() / 0.5
         self.mask_cls = (torch.rand(S, 2 * H) < 0.5).float() / 0.5
         self.loss_weight, self.micro = loss_weight, micro
+        self.min_logit = min_logit      # the fp64 oracle's largest |logit| must exceed it (run_all asserts)
         self.zero_ok = ZERO_OK_HETERO if variant == "hetero" else ()
         self.dev = (torch.as_tensor(ids, dtype=torch.int32).cuda(), torch.as_tensor(codes, dtype=torch.uint8).cuda(),
                     torch.as_tensor(sel, dtype=torch.int32).cuda(), self.y.cuda())
@@ -127,6 +129,8 @@ def _check_logits(tag, out, ref):
 def run_all(case, modes=MODES):
     """every pooling path of the case against the one fp64 reference; the eval forward against the eval reference"""
     rl, ro, rg = case.oracle(train=True)
+    if case.min_logit is not None:
+        assert ro.abs().max().item() > case.min_logit, "largest |logit| %.3g" % ro.abs().max().item()
     for name, knob, det in modes:
         tag = "%s (PN_POOL_STEP=%d, deterministic=%s)" % (name, knob, det)
         loss, out, grads = case.step(knob, det)
@@ -171,6 +175,8 @@ CASES = {
     "homo_split_ego_W40_H128_C5": dict(variant="homo", S=105, W=40, H=128, C=5, split_ego=True),
     # saturated softmax: fc2 x 50, some logits' gradients ~0 and others ~ -1 / S: step2
     "homo_saturated_W40_H128_C7": dict(variant="homo", S=100, W=40, H=128, C=7, fc2_scale=50.0),
+    # logits past 1e3 (fc2 x 1000: the oracle's largest is 1.27e3): the softmax must not lose bits with their size: step2
+    "homo_large_logits_W40_H128_C7": dict(variant="homo", S=100, W=40, H=128, C=7, fc2_scale=1000.0, min_logit=1e3),
     # three micro-batches of 34, 34 and 32 nodes, the loss added over them: step2
     "homo_micro_W40_H128_C7": dict(variant="homo", S=100, W=40, H=128, C=7, micro=34),
     "hetero_micro_W40_H128_C7": dict(variant="hetero", S=100, W=40, H=128, C=7, micro=34),
