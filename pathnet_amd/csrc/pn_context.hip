@@ -7,7 +7,6 @@
 #include <cstring>
 #include <map>
 #include <new>
-#include <tuple>
 #include <vector>
 
 #include "pn_internal.h"
@@ -24,8 +23,6 @@ struct pn_context {
     std::vector<Rec> recs;
     std::vector<hipEvent_t> free_events;
     std::map<const void *, int> lds_attr;      // kernel -> dynamic LDS bytes already granted on this device
-    std::map<std::tuple<const void *, size_t, int>, int> slots;    // (kernel, dynamic LDS bytes, threads) -> resident workgroups per CU
-    int cus = 0;
     pn::Knobs knobs;
 };
 
@@ -80,8 +77,7 @@ struct KnobName {
 const KnobName kKnobs[] = {{"PN_NODE_GEMM3", &pn::Knobs::node_gemm3}, {"PN_EVAL_ZW", &pn::Knobs::eval_zw},
                            {"PN_POOL_STEP", &pn::Knobs::pool_step}, {"PN_EVENT_DEVICE_SCOPE", &pn::Knobs::event_dev},
                            {"PN_NODE_RGRAD", &pn::Knobs::node_rgrad}, {"PN_SAMPLER_STAGE", &pn::Knobs::sampler_stage},
-                           {"PN_SEQ4", &pn::Knobs::seq4}, {"PN_SEQH_TAIL", &pn::Knobs::seqh_tail},
-                           {"PN_FC0_SPARSE", &pn::Knobs::fc0_sparse}};
+                           {"PN_SEQ4", &pn::Knobs::seq4}, {"PN_FC0_SPARSE", &pn::Knobs::fc0_sparse}};
 
 }  // namespace
 
@@ -93,28 +89,6 @@ const Knobs &knobs_of(const pn_context *ctx) {
 }
 
 bool profiling_every_stage(const pn_context *ctx) { return ctx && ctx->prof_mode == 1; }
-
-int resident_slots(pn_context *ctx, const void *kernel, int threads, size_t lds_bytes, int *slots, int *cus) {
-    if (ctx) {
-        auto it = ctx->slots.find(std::make_tuple(kernel, lds_bytes, threads));
-        if (it != ctx->slots.end() && ctx->cus > 0) {
-            *slots = it->second * ctx->cus;
-            *cus = ctx->cus;
-            return PN_OK;
-        }
-    }
-    int dev = 0, n_cu = 0, per_cu = 0;
-    PN_CHECK_HIP(hipGetDevice(&dev));
-    PN_CHECK_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    PN_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds_bytes));
-    if (ctx) {
-        ctx->slots[std::make_tuple(kernel, lds_bytes, threads)] = per_cu;
-        ctx->cus = n_cu;
-    }
-    *slots = per_cu * n_cu;
-    *cus = n_cu;
-    return PN_OK;
-}
 
 int context_check_device(const pn_context *ctx) {
     if (!ctx) return PN_OK;

@@ -112,7 +112,7 @@ struct Gemm3Params {
     int64_t ldc;
     const float *bias;
     int M, N, K;
-    // node-level GEMMs over row lists (the compact distance bank, GEMM_IND_A_ROWS / GEMM_IND_C_ROWS as in gemm_kernel: the
+    // node-level GEMMs over a row list (the compact distance bank's forward, GEMM_IND_A_ROWS as in gemm_kernel: the
     // row count lives in device memory, M bounds it), a ReLU gate on A (element kept where gate > 0, same indexing as A),
     // ReLU on the result, C += instead of C =
     const float *gate;
@@ -120,7 +120,7 @@ struct Gemm3Params {
     int relu, add;
 };
 // the same launch from a linear-forward description (gemm_linear_fwd: both operands K-contiguous), GEMM_STORE or GEMM_ADD; the
-// kernel has no row sums and no range words, and takes the row-list kind (g.ind) as launch_gemm3's argument
+// kernel has no row sums and no range words, and takes the row-list kind (g.ind: none or GEMM_IND_A_ROWS) as launch_gemm3's argument
 inline Gemm3Params gemm3_of(const GemmParams &g) {
     Gemm3Params p{};
     p.A = g.A, p.lda = g.sAm;
@@ -134,7 +134,7 @@ inline Gemm3Params gemm3_of(const GemmParams &g) {
     return p;
 }
 int launch_gemm3(hipStream_t stream, const Gemm3Params &p, int ind = GEMM_IND_NONE);
-// the bf16 x 3 GEMM pays once its 128 x 128 tiles fill the GPU; `which`: bit of the context knob PN_NODE_GEMM3
+// the bf16 x 3 GEMM pays once its 128 x 128 tiles fill the GPU; `which`: bit of the context knob PN_NODE_GEMM3 (a mask of these three)
 enum { G3_FC0 = 1, G3_BANK = 2, G3_BANK_DX = 4 };
 bool gemm3_pays(const pn_context *ctx, int64_t M, int64_t N, int K, int which);
 

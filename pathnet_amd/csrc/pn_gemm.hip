@@ -331,7 +331,6 @@ __global__ __launch_bounds__(256, 2) void gemm3_kernel(Gemm3Params p) {
     for (int i = 0; i < 4; i++) {
         int arow = min(m0 + lr + 32 * i, pM - 1);
         if (IND == GEMM_IND_A_ROWS) arow = p.list[ib + arow];
-        else if (IND == GEMM_IND_C_ROWS) arow += ib;
         ap[i] = p.A + (int64_t)arow * p.lda + lk;
         gp[i] = GATE ? p.gate + (int64_t)arow * p.lda + lk : nullptr;
         bp[i] = p.B + (int64_t)min(n0 + lr + 32 * i, p.N - 1) * p.ldb + lk;
@@ -412,7 +411,7 @@ __global__ __launch_bounds__(256, 2) void gemm3_kernel(Gemm3Params p) {
             for (int r = 0; r < 16; r++) {
                 const int row = m0 + wm * 64 + i * 32 + acc_row(r, lane);
                 if (row >= pM) continue;
-                const int crow = IND == GEMM_IND_A_ROWS ? ib + row : IND == GEMM_IND_C_ROWS ? p.list[ib + row] : row;
+                const int crow = IND == GEMM_IND_A_ROWS ? ib + row : row;
                 float v = acc[i][j][r] + bias;
                 if (p.relu) v = fmaxf(v, 0.0f);
                 float *dst = p.C + (int64_t)crow * p.ldc + col;
@@ -431,10 +430,6 @@ int launch_gemm3(hipStream_t stream, const Gemm3Params &p, int ind) {
     const dim3 grid((p.N + G3_BN - 1) / G3_BN, (p.M + G3_BM - 1) / G3_BM);
     if (ind == GEMM_IND_A_ROWS && !gate)
         hipLaunchKernelGGL((gemm3_kernel<GEMM_IND_A_ROWS, false>), grid, dim3(256), 0, stream, p);
-    else if (ind == GEMM_IND_C_ROWS && gate)
-        hipLaunchKernelGGL((gemm3_kernel<GEMM_IND_C_ROWS, true>), grid, dim3(256), 0, stream, p);
-    else if (ind == GEMM_IND_C_ROWS)
-        hipLaunchKernelGGL((gemm3_kernel<GEMM_IND_C_ROWS, false>), grid, dim3(256), 0, stream, p);
     else if (ind == GEMM_IND_NONE && gate)
         hipLaunchKernelGGL((gemm3_kernel<GEMM_IND_NONE, true>), grid, dim3(256), 0, stream, p);
     else if (ind == GEMM_IND_NONE)

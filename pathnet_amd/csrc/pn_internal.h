@@ -43,20 +43,15 @@ GlibcState glibc_seed_state(uint32_t seed);
 // created (pn_context_create) and changed afterwards only through pn_context_set_knob -- no call reads the environment,
 // so a concurrent setenv cannot race a launch and a captured step replays the selection it was captured with.
 // A NULL context runs the defaults.
-#ifndef PN_SEQH_TAIL_DEFAULT
-#define PN_SEQH_TAIL_DEFAULT 0      // measured neutral at the headline shape (profiles/r05_tune_scatter_tiling.txt): off
-#endif
 struct Knobs {
     int node_gemm3 = 7;         // PN_NODE_GEMM3: bit mask -- 1 fc0, 2 distance bank, 4 dense bank dX on the bf16 x 3 GEMM when its
-                                //                tiles fill the GPU; 8: the compact bank dX as well (measured slower)
+                                //                tiles fill the GPU
     int eval_zw = 1;            // PN_EVAL_ZW: inference forwards apply W_ih to the bank rows before the gather
     int event_dev = 1;          // PN_EVENT_DEVICE_SCOPE: fork / join / timing events without the system-scope release of a recorded event (a change makes the events again)
     int pool_step = 1;          // PN_POOL_STEP: pn_pagg_train_step runs pooling forward, loss and pooling backward of a node in one launch
     int node_rgrad = 1;         // PN_NODE_RGRAD: row-reduction kernel for the node-level weight gradients of large graphs
     int sampler_stage = -1;     // PN_SAMPLER_STAGE: first-hop tables in LDS (-1: by launch size)
     int seq4 = 4;               // PN_SEQ4: bit 2 = the two-stage weight-gradient GEMM of pn_seq4.hip serves the bf16 mode at hid 128
-    int seqh_tail = PN_SEQH_TAIL_DEFAULT;   // PN_SEQH_TAIL: 0 = 32-path tiles only (default); 1 = the remainder round of the fp16
-                                //                recurrent launches in smaller tiles, one per CU; 8 / 16 / 24 = that size, always
     int fc0_sparse = 1;         // PN_FC0_SPARSE: a call that carries prepared sparse features uses them for fc0 (0: ignores them, the A/B switch)
 };
 const Knobs &knobs_of(const pn_context *ctx);
@@ -82,8 +77,6 @@ int context_wait_side(pn_context *ctx, void *stream);
 // hipFuncSetAttribute(kernel, MaxDynamicSharedMemorySize, bytes), remembered per context (= per device) so that the
 // steady state issues no runtime call besides the launches (a captured step must not)
 int ensure_dynamic_lds(pn_context *ctx, const void *kernel, int bytes);
-// resident workgroups of `kernel` on the whole device (occupancy x compute units), remembered per context like the above
-int resident_slots(pn_context *ctx, const void *kernel, int threads, size_t lds_bytes, int *slots, int *cus);
 // RAII bracket: records a start event now and a stop event at scope exit when the context's profiling selects `stage`
 struct StageTimer {
     StageTimer(pn_context *ctx, int stage, void *stream);

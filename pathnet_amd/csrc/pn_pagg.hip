@@ -2425,25 +2425,16 @@ int run_bank_bwd(const Call &c, float *dXh, const float *dZ) {
         if (a->g_bank_b && !a->g_bank_w) PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: compact rows need g_bank_w with g_bank_b");
         const int mmax = (int)std::min<int64_t>(d.N, d.ZR);
         const int32_t *seg = c.at<const int32_t>(c.w.seg), *list = c.at<const int32_t>(c.w.list);
-        // (measured at the 10 M-node shape: the 128 x 128 tiles' read-modify-write of scattered dXh rows at two workgroups
-        //  per CU is slower than the 64 x 64 kernel's, 24.1 vs 21.6 ms for the stage; PN_NODE_GEMM3 bit 3 switches it on)
-        const bool g3 = (knobs_of(ctx).node_gemm3 & 8) && gemm3_pays(ctx, mmax, H, H, G3_BANK_DX);
-        float *bankT = c.at<float>(c.w.bankT);
-        if (g3)             // bank_w[code] [out, in] -> [in, out]: the reduction index (out) contiguous
-            for (int code = 0; code < L; code++)
-                launch_transpose(stream, a->bank_w + (size_t)code * H * H, H, H, bankT + (size_t)code * H * H);
-        for (int code = 0; code < L; code++) {      // (gemm3: a forward through the transposed weights)
-            GemmParams g = g3 ? gemm_linear_fwd(dZ, H, bankT + (size_t)code * H * H, H, dXh, H, mmax, H, H)
-                              : gemm_input_grad(dZ, H, a->bank_w + (size_t)code * H * H, H, dXh, H, mmax, H, H);
+        // (the 64 x 64 kernel: at the 10 M-node shape the 128 x 128 tiles' read-modify-write of scattered dXh rows at two
+        //  workgroups per CU measured slower, 24.1 vs 21.6 ms for the stage)
+        for (int code = 0; code < L; code++) {
+            GemmParams g = gemm_input_grad(dZ, H, a->bank_w + (size_t)code * H * H, H, dXh, H, mmax, H, H);
             g.gateA = zgate;
             g.mode = GEMM_ADD;
             g.ind = GEMM_IND_C_ROWS;
             g.seg = seg + code;
             g.list = list;
-            if (g3) {
-                if (int rc = launch_gemm3(stream, gemm3_of(g), g.ind)) return rc;
-            } else if (int rc = launch_gemm(stream, g))
-                return rc;
+            if (int rc = launch_gemm(stream, g)) return rc;
         }
         if (a->Xh_in && a->g_Xh_ready) PN_CHECK_HIP(hipEventRecord((hipEvent_t)a->g_Xh_ready, stream));
         for (int code = 0; code < L; code++) {

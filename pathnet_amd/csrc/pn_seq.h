@@ -24,15 +24,6 @@ struct SeqRange {           // (= struct pn_seq_range of include/pathnet_hip.h: 
     uint32_t dg;            // max |dG| of the BPTT launch the weight-gradient GEMM follows (seq_bwdh_kernel)
 };
 
-// tile geometry of the fp16 recurrent kernels (pn_seqh.hip "tile geometry"): n_big tiles of 32 paths and n_small tiles of
-// small_rows (8 / 16 / 24; 0 = every tile has 32) -- the small ones after the big ones, or before them (small_first)
-struct SeqTiling {
-    int n_big, n_small, small_rows, small_first;
-};
-struct SeqTile {
-    int q0, rows;
-};
-
 struct SeqFwdParams {
     const float *Z;         // [N*L, H] bank output (post activation)
     const int32_t *rowidx;  // [P, L]
@@ -54,7 +45,6 @@ struct SeqFwdParams {
     const SeqRange *range;  // fp16 kernels: operand ranges (device)
     float xmul;             // fp16 kernels: bound of the factor dropout applies to a gathered row (1 / (1 - p), or 16 for explicit masks)
     const float *ZW;        // seq_fwdzw_kernel: [rows of Z, G*H] = Z . W_ih^T + b (inference without dropout)
-    SeqTiling tiling;       // fp16 kernels: filled in by the launcher
 };
 
 struct SeqBwdParams {
@@ -73,7 +63,6 @@ struct SeqBwdParams {
     const float *mask;
     SeqRange *range;        // fp16 kernels: reads w_ih / w_hh, leaves max |dG| in dg
     int store_dx;           // fp16 kernel, deterministic mode: rowidx is the identity -- mask * dx is STORED (no zero-fill, no atomics)
-    SeqTiling tiling;       // fp16 kernels: filled in by the launcher
 };
 
 struct WgradParams {

@@ -20,19 +20,15 @@
 using namespace pn;
 
 // tuning knobs (variant builds with -D...)
-#ifndef PN_SEQ_RG
-#define PN_SEQ_RG 1         // row groups (of 32 sequence slots) per workgroup of the recurrent kernels (2: measured slower)
-#endif
 #ifndef PN_FWD_WAVES
 #define PN_FWD_WAVES 3      // __launch_bounds__ min waves per SIMD = workgroups per CU, forward (3: 168 registers)
 #endif
 #ifndef PN_BWD_WAVES
 #define PN_BWD_WAVES 2      // backward: 2 (a 168-register build re-reads the (g, o) gradients and A fragments: slower)
 #endif
-#ifndef PN_BWD_NB
-#define PN_BWD_NB 16        // cell backward: accumulator elements per batch of saved-gate loads (16: one memory round
-                            // trip per step; 8: two, measured 2 % slower)
-#endif
+// Settled by measurement in rounds 1-4 and no longer build options (the alternatives and their numbers: profiles/HISTORY_r1_r4.md):
+// one row group of 32 paths per workgroup and one row block per wave in both recurrent kernels (two of either: slower, the
+// forward 0.411 vs 0.308 ms with two row blocks); the saved gates of a step's 16 accumulator elements loaded as one batch (two of 8: 2 % slower).
 
 namespace {
 
@@ -86,37 +82,33 @@ __global__ void pack_fwd3_kernel(const float *__restrict__ w_ih, const float *__
     dst[2 * G * 64] = q2;
 }
 
-// RG row groups of 32 sequence slots per workgroup.  The waves (rg, w) of the RG groups walk the same weight stream
-// in step (they meet at every barrier), so the fragments one of them pulls from L2 are L1 hits for the others: the
-// L2 -> CU weight traffic, which bounds this kernel (4.4 GB per launch at RG = 1 on the bench workload, ~15 TB/s),
-// drops by the factor RG.
 // waves per SIMD the forward kernel is compiled for: H = 256 fills the LDS with one workgroup of 8 waves, H = 32 is
 // a single wave per workgroup (no register cap: a spill next to the asm loads would be a hazard)
-template <int H, int RG>
-constexpr int fwd_waves() { return H == 32 && RG == 1 ? 1 : (H > 128 || RG > 1) ? 2 : PN_FWD_WAVES; }
+template <int H>
+constexpr int fwd_waves() { return H == 32 ? 1 : H > 128 ? 2 : PN_FWD_WAVES; }
 
 // GC: 4 = LSTM, 1 = tanh RNN, 3 = GRU (on the LSTM's four gate slots, see pack_fwd3_kernel)
-// RB: row blocks of 32 paths per wave.  RB = 2: a wave keeps two accumulator sets and uses every weight fragment twice --
-// the fragment stream per path, which bounds the kernel, halves; the 64-row tile takes 101 KB of LDS, so
-// one workgroup per CU, one wave per SIMD with the whole register file.
-template <int H, int GC, int RG, int RB = 1>
-__global__ __launch_bounds__(H / 32 * 64 * RG, (RB > 1 ? 1 : fwd_waves<H, RG>())) void seq_fwd3_kernel(SeqFwdParams p) {
+template <int H, int GC>
+__global__ __launch_bounds__(H / 32 * 64, (fwd_waves<H>())) void seq_fwd3_kernel(SeqFwdParams p) {
     constexpr int G = GC == 3 ? 4 : GC;
     constexpr bool GRU = GC == 3;
-    constexpr int MT = 32 * RG * RB;
-    constexpr int NW = H / 32, NT = NW * 64 * RG, SV = (G == 4 ? 5 : 1);
+    constexpr int MT = 32;
+    constexpr int NW = H / 32, NT = NW * 64, SV = (G == 4 ? 5 : 1);
     constexpr int KS = H / 8, KX = KS / 2;    // k-steps of 16 over [x | h]; the first KX walk x
     constexpr int PB = 4 * H + 16;            // row pitch of a plane of the tile [x | h], bytes: conflict-free ds_read_b128
     constexpr int PLANE = MT * PB;
     // three workgroups per CU (168 registers): no register room for the x_{t+1} rows or a second plane-0 fragment set,
     // the third workgroup covers those latencies instead
-    constexpr bool PREFETCH_X = RB > 1 || fwd_waves<H, RG>() < 3, PING_PONG = RB > 1 || fwd_waves<H, RG>() < 3;
+    constexpr bool PREFETCH_X = fwd_waves<H>() < 3, PING_PONG = PREFETCH_X;
     // LDS: three bf16 planes of the tile [MT][x_t | h_{t-1}] | row indices
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
     int *s_rowidx = reinterpret_cast<int *>(ldsb + 3 * PLANE);  // [MT][L] gather rows of this tile
     int *s_slotof = s_rowidx + MT * p.L;                        // [MT]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31;
-    const int ws = wave % NW, r0 = 32 * RB * (wave / NW);       // column slice / first tile row of this wave
+    // column slice / first tile row of this wave.  A workgroup is NW waves, so ws == wave and r0 == 0 at run time; the compiler
+    // does not bound threadIdx by the launch bounds and computes both.  Folding them by hand changes the generated code of every
+    // instantiation (registers and instruction counts): a change to measure on its own.
+    const int ws = wave % NW, r0 = 32 * (wave / NW);
     const int q0 = blockIdx.x * MT;
     const int col = 32 * ws + li;
     const int ws_u = __builtin_amdgcn_readfirstlane(ws);        // the wave's column slice as a scalar (weight stream base)
@@ -124,11 +116,9 @@ __global__ __launch_bounds__(H / 32 * 64 * RG, (RB > 1 ? 1 : fwd_waves<H, RG>())
     for (int i = tid; i < MT * p.L; i += NT) s_rowidx[i] = q0 + i / p.L < p.P ? p.rowidx[(int64_t)q0 * p.L + i] : 0;
     for (int i = tid; i < MT; i += NT) s_slotof[i] = q0 + i < p.P ? p.slotof[q0 + i] : 0;
 
-    f32x16 cst[RB];
+    f32x16 cst;
 #pragma unroll
-    for (int rb = 0; rb < RB; rb++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) cst[rb][r] = 0.0f;
+    for (int r = 0; r < 16; r++) cst[r] = 0.0f;
     const float keep_scale = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.0f / (1.0f - p.p_drop))));
     const bool builtin_drop = !p.mask && p.p_drop > 0.0f;
     const uint64_t seed = p.dyn ? p.dyn->seed : p.seed;
@@ -147,7 +137,7 @@ __global__ __launch_bounds__(H / 32 * 64 * RG, (RB > 1 ? 1 : fwd_waves<H, RG>())
     //      ones to their use -- with the dropout keep bits drawn right behind them; with three workgroups per CU the
     //      rows are fetched in the cell-update phase instead (the other workgroups cover the latency).  Either
     //      way the mask is applied when the rows are committed to LDS.
-    constexpr int NLD = 4 * RB;   // float4 per thread = MT * (H/4) / NT
+    constexpr int NLD = 4;        // float4 per thread = MT * (H/4) / NT
     f32x4 xr[NLD];
     uint32_t keepbits = 0;        // 4 bits per row of this thread
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -175,10 +165,7 @@ __global__ __launch_bounds__(H / 32 * 64 * RG, (RB > 1 ? 1 : fwd_waves<H, RG>())
         keepbits = bits;
     };
     auto gather_commit = [&](int t) {
-        if constexpr (RB == 1)
-            wait_vm<0>(xr[0], xr[1], xr[2], xr[3]);
-        else
-            wait_vm<0>(xr[0], xr[1], xr[2], xr[3], xr[4 % NLD], xr[5 % NLD], xr[6 % NLD], xr[7 % NLD]);
+        wait_vm<0>(xr[0], xr[1], xr[2], xr[3]);
 #pragma unroll
         for (int i = 0; i < NLD; i++) {
             const int idx = tid_g + NT * i;
@@ -222,14 +209,12 @@ __global__ __launch_bounds__(H / 32 * 64 * RG, (RB > 1 ? 1 : fwd_waves<H, RG>())
         tid_g = wave_u * 64 + fresh_lane();
         if (PREFETCH_X && t + 1 < p.L) gather_issue(t + 1);
 
-        f32x16 acc[RB][G];
+        f32x16 acc[G];
 #pragma unroll
         for (int g = 0; g < G; g++) {
             const float bias = p.biasc[g * H + col];      // (re-read per step: G registers less across the kernel)
 #pragma unroll
-            for (int rb = 0; rb < RB; rb++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[rb][g][r] = bias;
+            for (int r = 0; r < 16; r++) acc[g][r] = bias;
         }
 
         // ---- [x_t ; h_{t-1}] x [W_ih ; W_hh]^T.  Weight fragments stream L2 -> VGPR ahead of their MFMAs: the
@@ -254,20 +239,11 @@ __global__ __launch_bounds__(H / 32 * 64 * RG, (RB > 1 ? 1 : fwd_waves<H, RG>())
             // a2.P0, a1.P0, a0.P0 | a1.P1, a0.P1 | a0.P2, so plane 2 of the A tile is dead after the first G MFMAs, plane
             // 1 after the P1 group, plane 0 at the end -- each is re-read for k-step s+1 right there, and the next
             // k-step again starts with a2 (read longest ago) and needs a0 (read last) only after 2G MFMAs.
-            u32x4 a[RB][3];
-            auto aread = [&](int rb, int s, int pl) {
-                return *reinterpret_cast<const u32x4 *>(arow + rb * 32 * PB + 32 * s + pl * PLANE);
-            };
-            // all RB row blocks of a product before the next product: every weight fragment feeds RB MFMAs
+            u32x4 a[3];
+            auto areads = [&](int s, int pl) { a[pl] = *reinterpret_cast<const u32x4 *>(arow + 32 * s + pl * PLANE); };
             auto prod = [&](int pa, u32x4 (&B)[G]) {
 #pragma unroll
-                for (int rb = 0; rb < RB; rb++)
-#pragma unroll
-                    for (int g = 0; g < G; g++) acc[rb][g] = mfma_bf16(a[rb][pa], B[g], acc[rb][g]);
-            };
-            auto areads = [&](int s, int pl) {
-#pragma unroll
-                for (int rb = 0; rb < RB; rb++) a[rb][pl] = aread(rb, s, pl);
+                for (int g = 0; g < G; g++) acc[g] = mfma_bf16(a[pa], B[g], acc[g]);
             };
             auto kstep = [&](int s, u32x4 (&P0)[G], u32x4 (&P0next)[G]) {
                 const int sn = min(s + 1, nsteps - 1);
@@ -313,65 +289,62 @@ __global__ __launch_bounds__(H / 32 * 64 * RG, (RB > 1 ? 1 : fwd_waves<H, RG>())
 
         // ---- cell update in registers; h_t goes back to LDS (split) for the next step ----------------------
         const int lane_o = fresh_lane();    // row offsets are re-derived in every step: hoisted out of the t loop they spill
+        float hv[16];
 #pragma unroll
-        for (int rb = 0; rb < RB; rb++) {
-            float hv[16];
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int row = r0 + 32 * rb + acc_row(r, lane_o);
-                const int q = q0 + row;
-                float h;
-                if (GRU) {
-                    // saved: r, z, n, the pre-activation W_hn h + b_hn, h_{t-1}
-                    const float rg = sigmoidf_(acc[rb][0][r]);
-                    const float zg = sigmoidf_(acc[rb][G > 1 ? 1 : 0][r]);
-                    const float nh = acc[rb][G > 3 ? 3 : 0][r];
-                    const float ng = tanhf_(acc[rb][G > 2 ? 2 : 0][r] + rg * nh);
-                    const float hp = cst[rb][r];
-                    h = (1.0f - zg) * ng + zg * hp;
-                    cst[rb][r] = h;
-                    if (saved_t && q < p.P) {
-                        float *sv = &at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)(SV * H) + col) * 4u);
-                        sv[0] = rg; sv[H] = zg; sv[2 * H] = ng; sv[3 * H] = nh; sv[4 * H] = hp;
-                    }
-                } else if (G == 4) {
-                    const float ig = sigmoidf_(acc[rb][0][r]);
-                    const float fg = sigmoidf_(acc[rb][G > 1 ? 1 : 0][r]);
-                    const float gg = tanhf_(acc[rb][G > 2 ? 2 : 0][r]);
-                    const float og = sigmoidf_(acc[rb][G > 3 ? 3 : 0][r]);
-                    const float c = fg * cst[rb][r] + ig * gg;
-                    cst[rb][r] = c;
-                    h = og * tanhf_(c);
-                    if (saved_t && q < p.P) {
-                        // (constant displacements on top of base + zext(offset) fold into the instructions' immediates)
-                        float *sv = &at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)(SV * H) + col) * 4u);
-                        sv[0] = ig; sv[H] = fg; sv[2 * H] = gg; sv[3 * H] = og; sv[4 * H] = c;
-                    }
-                } else {
-                    h = tanhf_(acc[rb][0][r]);
-                    if (saved_t && q < p.P) at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)H + col) * 4u) = h;
+        for (int r = 0; r < 16; r++) {
+            const int row = r0 + acc_row(r, lane_o);
+            const int q = q0 + row;
+            float h;
+            if (GRU) {
+                // saved: r, z, n, the pre-activation W_hn h + b_hn, h_{t-1}
+                const float rg = sigmoidf_(acc[0][r]);
+                const float zg = sigmoidf_(acc[G > 1 ? 1 : 0][r]);
+                const float nh = acc[G > 3 ? 3 : 0][r];
+                const float ng = tanhf_(acc[G > 2 ? 2 : 0][r] + rg * nh);
+                const float hp = cst[r];
+                h = (1.0f - zg) * ng + zg * hp;
+                cst[r] = h;
+                if (saved_t && q < p.P) {
+                    float *sv = &at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)(SV * H) + col) * 4u);
+                    sv[0] = rg; sv[H] = zg; sv[2 * H] = ng; sv[3 * H] = nh; sv[4 * H] = hp;
                 }
-                hv[r] = h;
-                if (q < p.P) {
-                    if (t == p.L - 1)
-                        at_bytes(hn_t, ((uint32_t)row * (uint32_t)H + col) * 4u) = h;
-                    else if (xh_t)
-                        at_bytes(xh_t, (((uint32_t)row * (uint32_t)p.L + t + 1) * (uint32_t)(2 * H) + H + col) * 4u) = h;
+            } else if (G == 4) {
+                const float ig = sigmoidf_(acc[0][r]);
+                const float fg = sigmoidf_(acc[G > 1 ? 1 : 0][r]);
+                const float gg = tanhf_(acc[G > 2 ? 2 : 0][r]);
+                const float og = sigmoidf_(acc[G > 3 ? 3 : 0][r]);
+                const float c = fg * cst[r] + ig * gg;
+                cst[r] = c;
+                h = og * tanhf_(c);
+                if (saved_t && q < p.P) {
+                    // (constant displacements on top of base + zext(offset) fold into the instructions' immediates)
+                    float *sv = &at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)(SV * H) + col) * 4u);
+                    sv[0] = ig; sv[H] = fg; sv[2 * H] = gg; sv[3 * H] = og; sv[4 * H] = c;
                 }
+            } else {
+                h = tanhf_(acc[0][r]);
+                if (saved_t && q < p.P) at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)H + col) * 4u) = h;
             }
-            if (t + 1 < p.L) {
+            hv[r] = h;
+            if (q < p.P) {
+                if (t == p.L - 1)
+                    at_bytes(hn_t, ((uint32_t)row * (uint32_t)H + col) * 4u) = h;
+                else if (xh_t)
+                    at_bytes(xh_t, (((uint32_t)row * (uint32_t)p.L + t + 1) * (uint32_t)(2 * H) + H + col) * 4u) = h;
+            }
+        }
+        if (t + 1 < p.L) {
 #pragma unroll
-                for (int r = 0; r < 16; r += 2) {       // accumulator registers r, r+1 are tile rows row, row+1
-                    uint32_t h0, h1, h2;
-                    split3(hv[r], hv[r + 1], h0, h1, h2);
-                    unsigned char *d = ldsb + (r0 + 32 * rb + acc_row(r, lane_o)) * PB + 2 * (H + col);
-                    *reinterpret_cast<uint16_t *>(d) = (uint16_t)h0;
-                    *reinterpret_cast<uint16_t *>(d + PB) = (uint16_t)(h0 >> 16);
-                    *reinterpret_cast<uint16_t *>(d + PLANE) = (uint16_t)h1;
-                    *reinterpret_cast<uint16_t *>(d + PLANE + PB) = (uint16_t)(h1 >> 16);
-                    *reinterpret_cast<uint16_t *>(d + 2 * PLANE) = (uint16_t)h2;
-                    *reinterpret_cast<uint16_t *>(d + 2 * PLANE + PB) = (uint16_t)(h2 >> 16);
-                }
+            for (int r = 0; r < 16; r += 2) {       // accumulator registers r, r+1 are tile rows row, row+1
+                uint32_t h0, h1, h2;
+                split3(hv[r], hv[r + 1], h0, h1, h2);
+                unsigned char *d = ldsb + (r0 + acc_row(r, lane_o)) * PB + 2 * (H + col);
+                *reinterpret_cast<uint16_t *>(d) = (uint16_t)h0;
+                *reinterpret_cast<uint16_t *>(d + PB) = (uint16_t)(h0 >> 16);
+                *reinterpret_cast<uint16_t *>(d + PLANE) = (uint16_t)h1;
+                *reinterpret_cast<uint16_t *>(d + PLANE + PB) = (uint16_t)(h1 >> 16);
+                *reinterpret_cast<uint16_t *>(d + 2 * PLANE) = (uint16_t)h2;
+                *reinterpret_cast<uint16_t *>(d + 2 * PLANE + PB) = (uint16_t)(h2 >> 16);
             }
         }
         if (t + 1 < p.L) {
@@ -430,24 +403,23 @@ __global__ void pack_bwd3_kernel(const float *__restrict__ w_ih, const float *__
     dst[8 * 64] = q2;
 }
 
-// RG row groups per workgroup share the weight stream through L1, as in seq_fwd3_kernel.
-template <int H, int GC, int RG>
-__global__ __launch_bounds__(H / 32 * 64 * RG, H == 32 && RG == 1 ? 1 : PN_BWD_WAVES) void seq_bwd3_kernel(SeqBwdParams p) {
+template <int H, int GC>
+__global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWD_WAVES) void seq_bwd3_kernel(SeqBwdParams p) {
     constexpr int G = GC == 3 ? 4 : GC;         // GC: 4 = LSTM, 1 = tanh RNN, 3 = GRU on the LSTM's four gate slots
     constexpr bool GRU = GC == 3;
-    constexpr int MT = 32 * RG, NW = H / 32;
-    constexpr int NT = NW * 64 * RG, GH = G * H, SV = (G == 4 ? 5 : 1);
+    constexpr int MT = 32, NW = H / 32;
+    constexpr int NT = NW * 64, GH = G * H, SV = (G == 4 ? 5 : 1);
     constexpr int NPASS = G == 4 ? 2 : 1, KP = GH / NPASS;      // K extent of one pass (one gate pair)
     constexpr int PB = 2 * KP + 16, PLANE = MT * PB;            // plane row pitch / plane size, bytes
     constexpr int NU = GH / 32, NUP = NU / NPASS;               // units of two k-steps, total / per pass
-    constexpr int NB = PN_BWD_NB;       // accumulator elements per batch of saved-tensor loads in the cell backward
+    constexpr int NB = 16;              // accumulator elements per batch of saved-gate loads: all 16, one memory round trip per step
     constexpr bool CARRY_C = false;     // true: c_t stays in registers from one step to the next (16 registers the kernel does not have)
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
     int *s_rowidx = reinterpret_cast<int *>(ldsb + 3 * PLANE);   // [MT][L] gather rows of this tile
     int *s_slotof = s_rowidx + MT * p.L;                         // [MT]
     uint8_t *s_keep = reinterpret_cast<uint8_t *>(s_slotof + MT); // [2][MT][H/4] dropout keep bits of step t (t & 1)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31;
-    const int ws = wave % NW, r0 = 32 * (wave / NW);             // column slice / first tile row of this wave
+    const int ws = wave % NW, r0 = 32 * (wave / NW);             // column slice / first tile row of this wave (== wave, 0: seq_fwd3_kernel)
     // tiles in descending order -- the forward wrote the saved tensors of the last tiles last, they are the ones still in
     // the 256 MB Infinity Cache when the backward starts
     const int q0 = (int)(gridDim.x - 1 - blockIdx.x) * MT;
@@ -688,7 +660,7 @@ __global__ __launch_bounds__(H / 32 * 64 * RG, H == 32 && RG == 1 ? 1 : PN_BWD_W
         // (hidden sizes that are not powers of two sit at the register limit already: they keep the plain scatter)
         constexpr bool MERGE_STEP0 = (H & (H - 1)) == 0;
         if (MERGE_STEP0 && t == 0 && p.merge0) {
-            static_assert(3 * PLANE >= NW * RG * 32 * 33 * 4, "the scatter scratch fits the plane region");
+            static_assert(3 * PLANE >= NW * 32 * 33 * 4, "the scatter scratch fits the plane region");
             const int lane_s = fresh_lane(), li_s = lane_s & 31;       // (re-derived here: nothing of this block is hoisted)
             float *scr = reinterpret_cast<float *>(ldsb) + wave_u * (32 * 33);
 #pragma unroll
@@ -794,9 +766,7 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad3_kernel(WgradParams p) {
     const int sa = (li & 3) * 68 + (li >> 2) + wm * 16, sb = (li & 3) * 68 + (li >> 2) + wn * 32;
 
     issue(rbeg);
-    [[maybe_unused]] int tile_i = 0;     // (tuning builds stamp tiles 8..19, five stamps per tile)
-    [[maybe_unused]] const int wblk = blockIdx.z * gridDim.y + blockIdx.y;
-    for (int64_t k0 = rbeg; k0 < rend; k0 += kstep, tile_i++) {
+    for (int64_t k0 = rbeg; k0 < rend; k0 += kstep) {
         wait_vm<0>(rg[0], rg[1], rg[2], rg[3], rg[4], rg[5], rg[6], rg[7]);
 #pragma unroll
         for (int e = 0; e < 8; e++)
@@ -965,14 +935,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
 
 template <int H, int G>
 int launch_seq_bwd(pn_context *ctx, hipStream_t stream, const SeqBwdParams &sp) {
-    constexpr int RG = H <= 128 ? PN_SEQ_RG : 1;
-    constexpr int MT = 32 * RG;
+    constexpr int MT = 32;
     const size_t lds_bytes = (size_t)3 * MT * (2 * (G >= 3 ? 2 * H : H) + 16) + (size_t)(MT * sp.L + MT) * 4 +
                              (size_t)2 * MT * (H / 4);      // (G = 3: GRU, on four gate slots)
-    auto kern = seq_bwd3_kernel<H, G, RG>;
+    auto kern = seq_bwd3_kernel<H, G>;
     if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), (int)lds_bytes)) return rc;
     const int blocks = (sp.P + MT - 1) / MT;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(H / 32 * 64 * RG), lds_bytes, stream, sp);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(H / 32 * 64), lds_bytes, stream, sp);
     PN_CHECK_HIP(hipGetLastError());
     return PN_OK;
 }
@@ -994,14 +963,12 @@ int dispatch_seq_bwd(pn_context *ctx, hipStream_t stream, int H, const SeqBwdPar
 
 template <int H, int G>
 int launch_seq_fwd(pn_context *ctx, hipStream_t stream, const SeqFwdParams &sp) {
-    constexpr int RG = H <= 128 ? PN_SEQ_RG : 1;      // H = 256: one row group already fills the LDS
-    constexpr int RB = 1;       // row blocks of 32 paths per wave (2 measured slower: 0.411 vs 0.308 ms, profiles/HISTORY_r1_r4.md)
-    constexpr int MT = 32 * RG * RB;
+    constexpr int MT = 32;
     const size_t lds_bytes = (size_t)3 * MT * (4 * H + 16) + (size_t)(MT * sp.L + MT) * 4;
-    auto kern = seq_fwd3_kernel<H, G, RG, RB>;
+    auto kern = seq_fwd3_kernel<H, G>;
     if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), (int)lds_bytes)) return rc;
     const int blocks = (sp.P + MT - 1) / MT;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(H / 32 * 64 * RG), lds_bytes, stream, sp);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(H / 32 * 64), lds_bytes, stream, sp);
     PN_CHECK_HIP(hipGetLastError());
     return PN_OK;
 }

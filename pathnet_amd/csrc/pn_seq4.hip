@@ -111,7 +111,6 @@ __global__ __launch_bounds__(W4_THREADS, 2) void wgrad4_kernel(WgradParams p) {
         W4_FENCE();
     };
     auto step = [&](int buf, u32x4 (&A0)[2], u32x4 (&A1)[2], u32x4 (&B0)[4], u32x4 (&B1)[4], f32x4 (&rg)[4], int64_t inext) {
-        [[maybe_unused]] const int ts = ((int)inext - 1 - 8) * 5;       // (tuning builds stamp tiles 8 .. 8 + 101)
         const u32x4 *fa = lds4 + buf * W4_STAGE + sa, *fb = lds4 + buf * W4_STAGE + sb;
         const u32x4 *na = lds4 + (buf ^ 1) * W4_STAGE + sa, *nb = lds4 + (buf ^ 1) * W4_STAGE + sb;
         group(A0, B0);                                  // a0.b0

@@ -35,7 +35,8 @@ using namespace pn;
 // ONE 16-byte quad {packed gates (3 dwords), c_{t-1}} per path step and unit; c carried in registers across the BPTT's steps; the next
 // step's saved values requested ahead of the scatter; descending tile order in the BPTT; no atomic for elements dropout zeroed;
 // gate gradients as [R][4][H] planes; no LDS-DMA "touch" prefetch, no early x gather, no XCD pairing of the weight gradient's
-// column blocks (each measured neutral or slower).
+// column blocks, no tiles of 8 / 16 / 24 paths for a launch's remainder round (profiles/r05_tune_scatter_tiling.txt) -- each
+// measured neutral or slower.
 #ifndef PN_TRACE_H
 #define PN_TRACE_H 0        // 1: tuning builds only -- wave 0 of every workgroup stamps the cycle counter at phase boundaries
 #endif
@@ -61,82 +62,6 @@ __device__ long long *g_trace_h = nullptr;      // [blocks][64] stamps, set with
 namespace {
 
 __device__ __forceinline__ uint32_t fbits_abs(float v) { return __float_as_uint(v) & 0x7fffffffu; }
-
-// ---- tile geometry ------------------------------------------------------------------------------------------------
-// A launch of T = ceil(P / 32) tiles on S resident workgroup slots runs as ceil(T / S) synchronised rounds (every tile costs
-// the same): at the headline shape 1624 tiles on 768 (forward) / 512 (BPTT) slots, and the last 20 % / 14 % of the launch
-// keeps 143 / 78 workgroups in flight (profiles/r04_tail_experiments.txt).  A lone workgroup's step is bound by its memory
-// phases and by the weight-fragment stream, not by the matrix pipe, so the remainder round is cut into SMALLER tiles --
-// small_rows = 8, 16 or 24 paths, the accumulator registers of the missing rows are whole-wave dead (acc_row: rows < 8k are
-// registers r < 4k) and their stores / atomics never issue -- one per CU instead of a 32-path tile on a third of the CUs.
-// Tile j < n_big * (1 - small_first):  paths [32 j, 32 j + 32);  the small ones follow (forward) or come first (BPTT,
-// whose dispatch order is descending: its remainder round is the START of the path range).
-// MEASURED (round 5, profiles/r05_tune_scatter_tiling.txt): no gain -- forward 0.236 = 0.236 ms, BPTT 0.371 / 0.368 against
-// 0.375 / 0.364 with 16-path tiles, slower with 8 (0.252 / 0.387): a lone workgroup's step is its latency chain and the
-// 512 KB weight stream, neither of which shrinks with the rows.  Kept behind the context knob PN_SEQH_TAIL (default 0) with
-// its parity tests (tests/test_gpu_seqh.py runs under forced sizes), as the evidence that a 16-path MFMA instantiation for
-// the remainder round would not pay either.
-__device__ __forceinline__ SeqTile seq_tile_of(const SeqTiling tg, int j, int MT, int P) {
-    SeqTile t;
-    if (tg.small_rows == 0) {
-        t.q0 = j * MT;
-        t.rows = min(MT, P - t.q0);
-    } else if (tg.small_first) {
-        if (j < tg.n_small) {
-            t.q0 = j * tg.small_rows;
-            t.rows = min(tg.small_rows, P - t.q0);
-        } else {
-            t.q0 = tg.n_small * tg.small_rows + (j - tg.n_small) * MT;
-            t.rows = min(MT, P - t.q0);
-        }
-    } else {
-        if (j < tg.n_big) {
-            t.q0 = j * MT;
-            t.rows = MT;
-        } else {
-            t.q0 = tg.n_big * MT + (j - tg.n_big) * tg.small_rows;
-            t.rows = min(tg.small_rows, P - t.q0);
-        }
-    }
-    t.q0 = __builtin_amdgcn_readfirstlane(t.q0);
-    t.rows = __builtin_amdgcn_readfirstlane(t.rows);
-    return t;
-}
-
-// host side: the split of P paths into n_big tiles of MT and n_small of small_rows for a kernel with `slots` resident
-// workgroups on `cus` compute units.  Pure arithmetic (tests/test_abi.py drives it through pn_debug_seq_tiling).
-void seq_tiling_for(int64_t P, int MT, int slots, int cus, int mode, bool small_first, SeqTiling *tg, int *blocks) {
-    *tg = SeqTiling{0, 0, 0, small_first ? 1 : 0};
-    const int64_t T = (P + MT - 1) / MT;
-    *blocks = (int)T;
-    if (mode == 0 || MT != 32 || slots <= 0 || cus <= 0 || P <= 0) return;
-    const int64_t full = T / slots * slots;             // tiles of the full rounds
-    const int64_t rem_paths = P - full * MT;            // what the remainder round holds
-    if (rem_paths <= 0) return;
-    int rows = mode >= 8 ? mode : (int)((rem_paths + (int64_t)cus * 8 - 1) / ((int64_t)cus * 8)) * 8;      // one tile per CU
-    if (rows >= MT) return;                             // the remainder round fills the CUs as it is
-    const int64_t n_small = (rem_paths + rows - 1) / rows;
-    if (small_first) {
-        const int64_t rest = P - n_small * rows;
-        tg->n_small = (int)n_small;
-        tg->n_big = (int)(rest > 0 ? (rest + MT - 1) / MT : 0);
-    } else {
-        tg->n_big = (int)full;
-        tg->n_small = (int)n_small;
-    }
-    tg->small_rows = rows;
-    *blocks = tg->n_big + tg->n_small;
-}
-
-int plan_tiling(pn_context *ctx, const void *kernel, int threads, size_t lds_bytes, int64_t P, int MT, bool small_first,
-                SeqTiling *tg, int *blocks) {
-    int slots = 0, cus = 0;
-    const int mode = knobs_of(ctx).seqh_tail;
-    if (mode != 0)
-        if (int rc = resident_slots(ctx, kernel, threads, lds_bytes, &slots, &cus)) return rc;
-    seq_tiling_for(P, MT, slots, cus, mode, small_first, tg, blocks);
-    return PN_OK;
-}
 
 // ---- operand ranges ---------------------------------------------------------------------------------------------------
 // max |W_ih|, max |W_hh| in two steps without an atomic or a slot to clear: RANGE_PARTS workgroups leave the maxima of their
@@ -289,19 +214,15 @@ __device__ __forceinline__ void pack_fwdh_body(int idx, const float *__restrict_
     dst[G * 64] = q1;
 }
 
-// RB: row blocks of 32 paths per wave.  RB = 2: a wave keeps two accumulator sets and every weight fragment feeds two MFMAs --
-// the fragment stream per path, which bounds the k loop (35 B/clk/CU through the vector-memory return path: 14.7 k cycles
-// per step where the matrix pipe needs 6.1 k, profiles/r04_phase_trace.txt), halves.  With two fp16 planes the 64-row tile
-// is 68 KB: two workgroups per CU (the bf16 form of this needed 101 KB, one workgroup per CU, and was slower).
-template <int H, int RB>
-constexpr int fwdh_waves() { return H == 32 && RB == 1 ? 1 : (H > 128 || RB > 1) ? 2 : PN_FWDH_WAVES; }
+template <int H>
+constexpr int fwdh_waves() { return H == 32 ? 1 : H > 128 ? 2 : PN_FWDH_WAVES; }
 
 // GC: 4 = LSTM, 1 = tanh RNN, 3 = GRU
-template <int H, int GC, int RB>
-__global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_kernel(SeqFwdParams p) {
+template <int H, int GC>
+__global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H>())) void seq_fwdh_kernel(SeqFwdParams p) {
     constexpr int G = GC == 3 ? 4 : GC;
     constexpr bool GRU = GC == 3;
-    constexpr int MT = 32 * RB;
+    constexpr int MT = 32;
     constexpr bool PACKED = GC == 4;          // LSTM: {gates as 3 dwords (pack_gates), c_{t-1}}: 4 H dwords per path step
     constexpr int NW = H / 32, NT = NW * 64, SV = PACKED ? 4 : (G == 4 ? 5 : 1);
     constexpr int KS = H / 8, KX = KS / 2;    // k-steps of 16 over [x | h]; the first KX walk x
@@ -309,15 +230,13 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_k
     constexpr int PLANE = MT * PB;
     // three workgroups per CU: no register room for the x_{t+1} rows or a second hi-plane fragment set, the third
     // workgroup covers those latencies instead (as in seq_fwd3_kernel)
-    constexpr bool PREFETCH_X = RB == 1 && fwdh_waves<H, RB>() < 3, PING_PONG = fwdh_waves<H, RB>() < 3 && RB == 1;
+    constexpr bool PREFETCH_X = fwdh_waves<H>() < 3, PING_PONG = PREFETCH_X;
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
     int *s_rowidx = reinterpret_cast<int *>(ldsb + 2 * PLANE);  // [MT][L] gather rows of this tile
     int *s_slotof = s_rowidx + MT * p.L;                        // [MT]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31;
-    // tile geometry (SeqTiling): the first n_big workgroups take MT paths each, the rest -- the launch's remainder round --
-    // small_rows each, so that the last round runs on every CU instead of a third of them
-    const SeqTile tl = seq_tile_of(p.tiling, (int)blockIdx.x, MT, p.P);
-    const int q0 = tl.q0, rows_here = tl.rows;
+    const int q0 = __builtin_amdgcn_readfirstlane((int)blockIdx.x * MT);
+    const int rows_here = __builtin_amdgcn_readfirstlane(min(MT, p.P - q0));    // the last tile of a launch is ragged
     const int col = 32 * wave + li;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);    // the wave's column slice as a scalar (weight stream base)
 
@@ -325,11 +244,9 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_k
     for (int i = tid; i < MT; i += NT) s_slotof[i] = i < rows_here ? p.slotof[q0 + i] : 0;
 
     const FwdScales sc = fwd_scales(p.range, p.xmul);
-    f32x16 cst[RB];
+    f32x16 cst;
 #pragma unroll
-    for (int rb = 0; rb < RB; rb++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) cst[rb][r] = 0.0f;
+    for (int r = 0; r < 16; r++) cst[r] = 0.0f;
     const float keep_scale = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.0f / (1.0f - p.p_drop))));
     const bool builtin_drop = !p.mask && p.p_drop > 0.0f;
     const uint64_t seed = p.dyn ? p.dyn->seed : p.seed;
@@ -343,7 +260,7 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_k
 
     // ---- coalesced row gather of x_{t+1} (H*4 bytes per row), dropout keep bits drawn behind the loads, mask and
     //      scale applied when the rows are committed to LDS
-    constexpr int NLD = 4 * RB;   // float4 per thread = MT * (H/4) / NT
+    constexpr int NLD = 4;        // float4 per thread = MT * (H/4) / NT
     f32x4 xr[NLD];
     uint32_t keepbits = 0;        // 4 bits per row of this thread
     int tid_g = tid;              // re-derived per step (fresh_lane): offsets derived from it must not live across the MFMA loop
@@ -369,10 +286,7 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_k
         keepbits = bits;
     };
     auto gather_commit = [&](int t) {
-        if constexpr (RB == 1)
-            wait_vm<0>(xr[0], xr[1], xr[2], xr[3]);
-        else
-            wait_vm<0>(xr[0], xr[1], xr[2], xr[3], xr[4 % NLD], xr[5 % NLD], xr[6 % NLD], xr[7 % NLD]);
+        wait_vm<0>(xr[0], xr[1], xr[2], xr[3]);
 #pragma unroll
         for (int i = 0; i < NLD; i++) {
             const int idx = tid_g + NT * i;
@@ -417,14 +331,12 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_k
         tid_g = wave_u * 64 + fresh_lane();
         if (PREFETCH_X && t + 1 < p.L) gather_issue(t + 1);
 
-        f32x16 acc[RB][G];
+        f32x16 acc[G];
 #pragma unroll
         for (int g = 0; g < G; g++) {
             const float bias = p.biasc[g * H + col] * sc.S;
 #pragma unroll
-            for (int rb = 0; rb < RB; rb++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[rb][g][r] = bias;
+            for (int r = 0; r < 16; r++) acc[g][r] = bias;
         }
 
         // ---- [x_t ; h_{t-1}] x [W_ih ; W_hh]^T.  Per k-step the products run  a_lo.B_hi, a_hi.B_hi | a_hi.B_lo : the lo
@@ -441,18 +353,11 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_k
             auto load = [&](u32x4 (&B)[G], int s, int pl) {
                 async_load_frags<G>(B, wb + (size_t)(s * 2 + pl) * (G * 1024), voff);
             };
-            u32x4 a[RB][2];
-            auto areads = [&](int s, int pl) {
-#pragma unroll
-                for (int rb = 0; rb < RB; rb++)
-                    a[rb][pl] = *reinterpret_cast<const u32x4 *>(arow + rb * 32 * PB + 32 * s + pl * PLANE);
-            };
-            // all RB row blocks of a product before the next product: every weight fragment feeds RB MFMAs
+            u32x4 a[2];
+            auto areads = [&](int s, int pl) { a[pl] = *reinterpret_cast<const u32x4 *>(arow + 32 * s + pl * PLANE); };
             auto prod = [&](int pa, u32x4 (&B)[G]) {
 #pragma unroll
-                for (int rb = 0; rb < RB; rb++)
-#pragma unroll
-                    for (int g = 0; g < G; g++) acc[rb][g] = mfma_f16(a[rb][pa], B[g], acc[rb][g]);
+                for (int g = 0; g < G; g++) acc[g] = mfma_f16(a[pa], B[g], acc[g]);
             };
             // vmcnt (in order) at the top of k-step s: PING_PONG [Bh(s) Bl(s)] + the Bh(s+1) just issued; else [Bh(s) Bl(s)]
             auto kstep = [&](int s, u32x4 (&Bh)[G], u32x4 (&Bhnext)[G]) {
@@ -491,35 +396,33 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_k
 
         // ---- cell update in registers; h_t goes back to LDS (scaled, split) for the next step ----------------------
         const int lane_o = fresh_lane();    // row offsets are re-derived in every step: hoisted out of the t loop they spill
-#pragma unroll
-        for (int rb = 0; rb < RB; rb++) {
         float hv[16];
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int row = 32 * rb + acc_row(r, lane_o);
+            const int row = acc_row(r, lane_o);
             const bool live = row < rows_here;
             float h;
             if (GRU) {
                 // saved: r, z, n, the pre-activation W_hn h + b_hn, h_{t-1}
-                const float rg = sigmoidf_(acc[rb][0][r] * sc.inv_S);
-                const float zg = sigmoidf_(acc[rb][G > 1 ? 1 : 0][r] * sc.inv_S);
-                const float nh = acc[rb][G > 3 ? 3 : 0][r] * sc.inv_S;
-                const float ng = tanhf_(acc[rb][G > 2 ? 2 : 0][r] * sc.inv_S + rg * nh);
-                const float hp = cst[rb][r];
+                const float rg = sigmoidf_(acc[0][r] * sc.inv_S);
+                const float zg = sigmoidf_(acc[G > 1 ? 1 : 0][r] * sc.inv_S);
+                const float nh = acc[G > 3 ? 3 : 0][r] * sc.inv_S;
+                const float ng = tanhf_(acc[G > 2 ? 2 : 0][r] * sc.inv_S + rg * nh);
+                const float hp = cst[r];
                 h = (1.0f - zg) * ng + zg * hp;
-                cst[rb][r] = h;
+                cst[r] = h;
                 if (saved_t && live) {
                     float *sv = &at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)(SV * H) + col) * 4u);
                     sv[0] = rg; sv[H] = zg; sv[2 * H] = ng; sv[3 * H] = nh; sv[4 * H] = hp;
                 }
             } else if (G == 4) {
-                const float ig = sigmoidf_(acc[rb][0][r] * sc.inv_S);
-                const float fg = sigmoidf_(acc[rb][G > 1 ? 1 : 0][r] * sc.inv_S);
-                const float gg = tanhf_(acc[rb][G > 2 ? 2 : 0][r] * sc.inv_S);
-                const float og = sigmoidf_(acc[rb][G > 3 ? 3 : 0][r] * sc.inv_S);
-                const float cprev = cst[rb][r];
+                const float ig = sigmoidf_(acc[0][r] * sc.inv_S);
+                const float fg = sigmoidf_(acc[G > 1 ? 1 : 0][r] * sc.inv_S);
+                const float gg = tanhf_(acc[G > 2 ? 2 : 0][r] * sc.inv_S);
+                const float og = sigmoidf_(acc[G > 3 ? 3 : 0][r] * sc.inv_S);
+                const float cprev = cst[r];
                 const float c = fg * cprev + ig * gg;
-                cst[rb][r] = c;
+                cst[r] = c;
                 h = og * tanhf_(c);
                 if (saved_t && live) {
                     const uint32_t base = ((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)(SV * H);
@@ -529,7 +432,7 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_k
                         make_uint4(pk.x, pk.y, pk.z, __float_as_uint(cprev));
                 }
             } else {
-                h = tanhf_(acc[rb][0][r] * sc.inv_S);
+                h = tanhf_(acc[0][r] * sc.inv_S);
                 if (saved_t && live) at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)H + col) * 4u) = h;
             }
             hv[r] = h;
@@ -545,13 +448,12 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_k
             for (int r = 0; r < 16; r += 2) {       // accumulator registers r, r+1 are tile rows row, row+1
                 uint32_t h0, h1;
                 split2h(hv[r] * sc.s_h, hv[r + 1] * sc.s_h, h0, h1);
-                unsigned char *d = ldsb + (32 * rb + acc_row(r, lane_o)) * PB + 2 * (H + col);
+                unsigned char *d = ldsb + acc_row(r, lane_o) * PB + 2 * (H + col);
                 *reinterpret_cast<uint16_t *>(d) = (uint16_t)h0;
                 *reinterpret_cast<uint16_t *>(d + PB) = (uint16_t)(h0 >> 16);
                 *reinterpret_cast<uint16_t *>(d + PLANE) = (uint16_t)h1;
                 *reinterpret_cast<uint16_t *>(d + PLANE + PB) = (uint16_t)(h1 >> 16);
             }
-        }
         }
         if (t + 1 < p.L) {
             tid_g = wave_u * 64 + fresh_lane();
@@ -576,13 +478,13 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, RB>())) void seq_fwdh_k
 //   packed planes, of which only the k-steps KX .. KS-1 (the h half) are read.
 // =====================================================================================================================
 template <int H, int GC>
-__global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H, 1>())) void seq_fwdzw_kernel(SeqFwdParams p) {
+__global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H>())) void seq_fwdzw_kernel(SeqFwdParams p) {
     constexpr int G = GC == 3 ? 4 : GC;
     constexpr bool GRU = GC == 3;
     constexpr int MT = 32, NW = H / 32, NT = NW * 64, GH = G * H;
     constexpr int KS = H / 8, KX = KS / 2, KH = KS - KX;      // k-steps of 16 over [x | h]: the last KH walk h
     constexpr int PB = 2 * H + 16, PLANE = MT * PB;           // the tile holds h_{t-1} only
-    constexpr bool PING_PONG = fwdh_waves<H, 1>() < 3;
+    constexpr bool PING_PONG = fwdh_waves<H>() < 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
     int *s_rowidx = reinterpret_cast<int *>(ldsb + 2 * PLANE);  // [MT][L] gather rows of this tile
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31;
@@ -774,10 +676,9 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWDH_WAVES) void seq_
     float *s_max = reinterpret_cast<float *>(s_slotof + MT);     // [8] wave maxima of |dG_t|
     uint8_t *s_keep = reinterpret_cast<uint8_t *>(s_max + 8);    // [2][MT][H/4] dropout keep bits of step t (t & 1)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31;
-    // (descending path order: the BPTT starts on the tiles the forward wrote last; its small tiles -- SeqTiling, the
-    //  remainder round -- are therefore the ones at the START of the path range, dispatched last)
-    const SeqTile tl = seq_tile_of(p.tiling, (int)(gridDim.x - 1 - blockIdx.x), MT, p.P);
-    const int q0 = tl.q0, rows_here = tl.rows;          // rows_here >= 1
+    // (descending path order: the BPTT starts on the tiles the forward wrote last)
+    const int q0 = __builtin_amdgcn_readfirstlane((int)(gridDim.x - 1 - blockIdx.x) * MT);
+    const int rows_here = __builtin_amdgcn_readfirstlane(min(MT, p.P - q0));    // >= 1; the last tile of the path range is ragged
     const int col = 32 * wave + li;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 
@@ -1228,17 +1129,11 @@ __global__ __launch_bounds__(WH_THREADS, 2) void wgradh_kernel(WgradParams p, in
 
 template <int H, int GC>
 int launch_fwdh_t(pn_context *ctx, hipStream_t stream, const SeqFwdParams &sp) {
-    constexpr int RB = 1;       // row blocks of 32 paths per wave (the kernel keeps the parameter; 2 measured slower)
-    constexpr int MT = 32 * RB;
+    constexpr int MT = 32;
     const size_t lds_bytes = (size_t)2 * MT * (4 * H + 16) + (size_t)(MT * sp.L + MT) * 4;
-    auto kern = seq_fwdh_kernel<H, GC, RB>;
+    auto kern = seq_fwdh_kernel<H, GC>;
     if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), (int)lds_bytes)) return rc;
-    SeqFwdParams lp = sp;
-    int blocks = 0;
-    if (int rc = plan_tiling(ctx, reinterpret_cast<const void *>(kern), H / 32 * 64, lds_bytes, sp.P, MT, /*small_first=*/false,
-                             &lp.tiling, &blocks))
-        return rc;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(H / 32 * 64), lds_bytes, stream, lp);
+    hipLaunchKernelGGL(kern, dim3((sp.P + MT - 1) / MT), dim3(H / 32 * 64), lds_bytes, stream, sp);
     PN_CHECK_HIP(hipGetLastError());
     return PN_OK;
 }
@@ -1253,12 +1148,7 @@ int launch_bwdh_t(pn_context *ctx, hipStream_t stream, const SeqBwdParams &sp) {
     const size_t lds_bytes = bwdh_lds_bytes<H, GC>(sp.L);
     auto kern = seq_bwdh_kernel<H, GC>;
     if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), (int)lds_bytes)) return rc;
-    SeqBwdParams lp = sp;
-    int blocks = 0;
-    if (int rc = plan_tiling(ctx, reinterpret_cast<const void *>(kern), H / 32 * 64, lds_bytes, sp.P, MT,
-                             /*small_first=*/true, &lp.tiling, &blocks))
-        return rc;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(H / 32 * 64), lds_bytes, stream, lp);
+    hipLaunchKernelGGL(kern, dim3((sp.P + MT - 1) / MT), dim3(H / 32 * 64), lds_bytes, stream, sp);
     PN_CHECK_HIP(hipGetLastError());
     return PN_OK;
 }
@@ -1322,15 +1212,6 @@ extern "C" int pn_debug_set_trace_h(long long *dev_buf) {     // tuning builds o
     return hipMemcpyToSymbol(HIP_SYMBOL(g_trace_h), &dev_buf, sizeof dev_buf) == hipSuccess ? 0 : -4;
 }
 #endif
-
-// the tile split of a launch (host arithmetic only; not part of the ABI): out = {n_big, n_small, small_rows, blocks}
-extern "C" int pn_debug_seq_tiling(int64_t P, int slots, int cus, int mode, int small_first, int32_t out[4]) {
-    pn::SeqTiling tg;
-    int blocks = 0;
-    seq_tiling_for(P, 32, slots, cus, mode, small_first != 0, &tg, &blocks);
-    out[0] = tg.n_big; out[1] = tg.n_small; out[2] = tg.small_rows; out[3] = blocks;
-    return 0;
-}
 
 namespace pn {
 

@@ -772,16 +772,13 @@ def test_compact_rows_on_a_million_node_graph_match_the_oracle():
 
 
 @pytest.mark.parametrize("variant,compact", [("homo", 0), ("homo", 1), ("hetero", 0), ("hetero", 1)])
-def test_node_level_gemms_on_the_bf16_pipe_match_the_oracle(variant, compact, monkeypatch, request):
+def test_node_level_gemms_on_the_bf16_pipe_match_the_oracle(variant, compact, monkeypatch):
     """Graphs of >= ~50 000 rows run fc0 (feature width a multiple of 32), the distance bank and the bank's dX backward on
     gemm3_kernel (fp32 results from six bf16 MFMAs per product, 128 x 128 tiles) instead of the fp32-input MFMA kernel: the
-    dense bank, and the bank over the touched rows (row lists, ReLU gate of the homo class, C += in the backward)."""
+    dense bank, and the bank over the touched rows (row lists, ReLU gate of the homo class; its dX stays on the fp32-input
+    kernel, C += over the row list)."""
     import pathnet_amd
     monkeypatch.setenv("PN_COMPACT", str(compact))
-    from pathnet_amd import _lib
-    # (bit 3: also the compact dX on gemm3, off by default -- measured slower; a context knob, not read from the environment per call)
-    old_knob = _lib.set_knob("PN_NODE_GEMM3", 15)
-    request.addfinalizer(lambda: _lib.set_knob("PN_NODE_GEMM3", old_knob))
     torch.manual_seed(91)
     rng = np.random.default_rng(91)
     N, F, H, C, W, L, S = 70_000, 32, 128, 5, 40, 4, 500          # 80 000 path steps: the compact bank is 80 000 rows at most

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build variants of libpathnet_hip.so that differ in the knobs of pn_seqh.hip (HERE, no GPU needed):
-#   bash tools/seqh_variants.sh "" "FWDH_WAVES=2" "TRACE_H=1" "env:PN_SEQH_TAIL=0" ...
+#   bash tools/seqh_variants.sh "" "FWDH_WAVES=2" "TRACE_H=1" "env:PN_EVAL_ZW=0" ...
 # Each spec becomes pathnet_amd/csrc/_variants/lib_<n>.so (run: tools/tune_run.py / tools/trace_seqh.py with PN_LIB_PATH).
 set -e
 cd "$(dirname "$0")/../pathnet_amd/csrc"
