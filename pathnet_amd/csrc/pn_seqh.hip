@@ -36,7 +36,9 @@ using namespace pn;
 // step's saved values requested ahead of the scatter; descending tile order in the BPTT; no atomic for elements dropout zeroed;
 // gate gradients as [R][4][H] planes; no LDS-DMA "touch" prefetch, no early x gather, no XCD pairing of the weight gradient's
 // column blocks, no tiles of 8 / 16 / 24 paths for a launch's remainder round (profiles/r05_tune_scatter_tiling.txt) -- each
-// measured neutral or slower.
+// measured neutral or slower.  Round 7 (profiles/bwdh_step_boundaries.txt): the BPTT's keep word requested a step ahead and
+// held in a register, the forward kernels' index staging with one wait and their gather's row reads ahead of its loads --
+// neutral, not kept.
 #ifndef PN_TRACE_H
 #define PN_TRACE_H 0        // 1: tuning builds only -- wave 0 of every workgroup stamps the cycle counter at phase boundaries
 #endif
@@ -60,6 +62,8 @@ __device__ long long *g_trace_h = nullptr;      // [blocks][64] stamps, set with
 #endif
 
 namespace {
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t fbits_abs(float v) { return __float_as_uint(v) & 0x7fffffffu; }
 
@@ -671,7 +675,8 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWDH_WAVES) void seq_
     constexpr int PB = 2 * GH + 16, PLANE = MT * PB;            // plane row pitch / plane size, bytes
     constexpr int NU = GH / 32;                                 // units of two k-steps
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
-    int *s_rowidx = reinterpret_cast<int *>(ldsb + 2 * PLANE);   // [MT][L] gather rows of this tile
+    int *s_rowidx = reinterpret_cast<int *>(ldsb + 2 * PLANE);   // [L][MT] gather rows of this tile, step-major: the four
+                                                                 // consecutive rows of an accumulator quad are one 16-byte read
     int *s_slotof = s_rowidx + MT * p.L;                         // [MT]
     float *s_max = reinterpret_cast<float *>(s_slotof + MT);     // [8] wave maxima of |dG_t|
     uint8_t *s_keep = reinterpret_cast<uint8_t *>(s_max + 8);    // [2][MT][H/4] dropout keep bits of step t (t & 1)
@@ -682,8 +687,17 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWDH_WAVES) void seq_
     const int col = 32 * wave + li;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 
-    for (int i = tid; i < MT * p.L; i += NT) s_rowidx[i] = i / p.L < rows_here ? p.rowidx[(int64_t)q0 * p.L + i] : 0;
-    for (int i = tid; i < MT; i += NT) s_slotof[i] = i < rows_here ? p.slotof[q0 + i] : 0;
+    // ---- prologue: the tile's index entries, dhn and the saved values of the last step are all requested before anything
+    //      waits (the LDS writes of the entries below wait for their own two loads only).  Every load is unconditional and
+    //      stays inside its tensor: rows_here >= 1, a padded row reads row rows_here - 1 of the tile (q0 + rows_here - 1
+    //      <= P - 1), entry i < MT L has step i / MT <= L - 1.  A padded row so carries the entries of the tile's last live row.
+    const int nidx = MT * p.L;
+    auto rowidx_of = [&](int i) {       // entry i = t * MT + row of s_rowidx
+        const int rc = min(i & (MT - 1), rows_here - 1);
+        return p.rowidx[((int64_t)q0 + rc) * p.L + i / MT];
+    };
+    const int ri0 = rowidx_of(min(tid, nidx - 1));
+    const int sl0 = p.slotof[q0 + min(tid, rows_here - 1)];
 
     const float keep_scale = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(1.0f / (1.0f - p.p_drop))));
     const int e_ih = scale_exp(__uint_as_float(p.range->w_ih)), e_hh = scale_exp(__uint_as_float(p.range->w_hh));
@@ -730,6 +744,10 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWDH_WAVES) void seq_
         }
     };
     load_saved(p.L - 1, lane);
+    if (tid < nidx) s_rowidx[tid] = ri0;
+    if (tid < MT) s_slotof[tid] = sl0;
+#pragma unroll 1        // (entered only where L > H / 16: kept rolled)
+    for (int i = tid + NT; i < nidx; i += NT) s_rowidx[i] = rowidx_of(i);
 
     for (int t = p.L - 1; t >= 0; t--) {
         // (row numbers are re-derived from an opaque copy of the lane id in every step: as loop invariants the
@@ -737,14 +755,15 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWDH_WAVES) void seq_
         const int lane_t = fresh_lane();
         if (t == p.L - 1) HSTAMP_RT(62);
         HSTAMP(6 * (p.L - 1 - t) + 0);
-        if (p.keep) {      // this step's keep bytes (MT rows x H/4) -> LDS, read by the scatter phase below
+        if (p.keep) {      // this step's keep bytes (MT rows x H/4) -> LDS, read by the scatter phase below: one word per thread
+            static_assert(MT * (H / 16) == NT, "one keep word per thread");
+            // (requesting the word a step ahead, with the saved values, and holding it in a register measured neutral:
+            //  profiles/bwdh_step_boundaries.txt)
             const int tid_t = wave_u * 64 + lane_t;
-            for (int i = tid_t; i < MT * (H / 16); i += NT) {
-                const int row = i / (H / 16), w = i - row * (H / 16);
-                const uint32_t rc = (uint32_t)min(row, rows_here - 1);
-                reinterpret_cast<uint32_t *>(s_keep + (t & 1) * MT * (H / 4))[i] =
-                    at_bytes(reinterpret_cast<const uint32_t *>(keep_t), (rc * (uint32_t)p.L + t) * (uint32_t)(H / 4) + 4u * w);
-            }
+            const int row = tid_t / (H / 16), w = tid_t - row * (H / 16);
+            const uint32_t rc = (uint32_t)min(row, rows_here - 1);
+            reinterpret_cast<uint32_t *>(s_keep + (t & 1) * MT * (H / 4))[tid_t] =
+                at_bytes(reinterpret_cast<const uint32_t *>(keep_t), (rc * (uint32_t)p.L + t) * (uint32_t)(H / 4) + 4u * w);
         }
         // ---- cell backward into registers
         float dgv[G][16];
@@ -907,64 +926,96 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWDH_WAVES) void seq_
         //      paths' own start nodes: the wave parks its 32 x 32 block in the (then dead) plane region and each half-wave
         //      adds up runs of equal table rows, one atomic per run and column (as seq_bwd3_kernel)
         constexpr bool MERGE_STEP0 = (H & (H - 1)) == 0;
+        // The dropout mode is the same for the whole launch: ONE uniform branch around three straight-line bodies, each of
+        // which issues all its reads (slots and mask values | keep bytes) before it waits.  A padded row carries the index
+        // entries of the tile's last live row (prologue), so its reads are in bounds; its value is zeroed instead.
+        const int hk4 = 4 * (lane_t >> 5);
+        const int col_t = 32 * wave_u + (lane_t & 31);      // (= col, from the step's own lane id: what is derived from it below
+                                                            //  does not become loop invariants that live across the k loop)
+        float dxv[16];
+        auto masked_dx = [&](auto mode_tag) {
+            constexpr int MODE = decltype(mode_tag)::value;       // 0: no dropout, 1: explicit mask, 2: keep bits
+            [[maybe_unused]] float mv[16];
+            [[maybe_unused]] uint32_t kb[16];
+            if constexpr (MODE == 1) {
+                i32x4 sl[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) sl[j] = *reinterpret_cast<const i32x4 *>(s_slotof + 8 * j + hk4);
+#pragma unroll
+                for (int r = 0; r < 16; r++)
+                    mv[r] = p.mask[((uint64_t)t * p.Pmask + sl[r >> 2][r & 3]) * H + col_t];
+            }
+            if constexpr (MODE == 2) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) kb[r] = s_keep[((t & 1) * MT + acc_row(r, lane_t)) * (H / 4) + (col_t >> 2)];
+            }
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                float dx = acc[0][r] * inv_x;
+                if constexpr (MODE == 1) dx *= mv[r];
+                if constexpr (MODE == 2) dx = (kb[r] >> (col_t & 3)) & 1 ? dx * keep_scale : 0.0f;
+                dxv[r] = acc_row(r, lane_t) < rows_here ? dx : 0.0f;
+            }
+        };
+        if (p.mask)
+            masked_dx(std::integral_constant<int, 1>{});
+        else if (p.keep)
+            masked_dx(std::integral_constant<int, 2>{});
+        else
+            masked_dx(std::integral_constant<int, 0>{});
         if (MERGE_STEP0 && t == 0 && p.merge0) {
             static_assert(2 * PLANE >= NW * 32 * 33 * 4, "the scatter scratch fits the plane region");
             __syncthreads();            // every wave is done with the planes
             const int lane_s = fresh_lane(), li_s = lane_s & 31;
             float *scr = reinterpret_cast<float *>(ldsb) + wave_u * (32 * 33);
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int rl = acc_row(r, lane_s), row = rl;
-                float dx = acc[0][r] * inv_x;
-                if (row < rows_here) {
-                    if (p.mask)
-                        dx *= p.mask[((uint64_t)t * p.Pmask + s_slotof[row]) * H + col];
-                    else if (p.keep)
-                        dx = (s_keep[((t & 1) * MT + row) * (H / 4) + (col >> 2)] >> (col & 3)) & 1 ? dx * keep_scale : 0.0f;
-                }
-                scr[rl * 33 + li_s] = dx;
-            }
+            for (int r = 0; r < 16; r++) scr[acc_row(r, lane_s) * 33 + li_s] = dxv[r];
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const int hk = lane_s >> 5;
             int cur = -1;
             float run = 0.0f;
+            // four rows per trip: their ids are one 16-byte read (step 0 is the first MT entries), their values four reads
+            // issued together.  (All sixteen up front spill: the next step's saved values are arriving in 64 registers.)
 #pragma unroll 1
-            for (int i = 0; i < 16; i++) {
-                const int rl = 16 * hk + i, row = rl;
-                const int rid = row < rows_here ? s_rowidx[row * p.L] : -1;       // (uniform over a half-wave)
-                if (rid != cur) {
-                    if (cur >= 0) atomicAdd(p.dZ + ((size_t)(uint32_t)cur * (uint32_t)H + col), run);
-                    cur = rid;
-                    run = 0.0f;
-                }
-                run += scr[rl * 33 + li_s];
-            }
-            if (cur >= 0) atomicAdd(p.dZ + ((size_t)(uint32_t)cur * (uint32_t)H + col), run);
-        } else {
+            for (int j = 0; j < 4; j++) {
+                const i32x4 rqj = *reinterpret_cast<const i32x4 *>(s_rowidx + 16 * hk + 4 * j);
+                float v[4];
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int row = acc_row(r, lane_t);
-                if (row < rows_here) {
-                    float dx = acc[0][r] * inv_x;
-                    if (p.mask)
-                        dx *= p.mask[((uint64_t)t * p.Pmask + s_slotof[row]) * H + col];
-                    else if (p.keep)
-                        dx = (s_keep[((t & 1) * MT + row) * (H / 4) + (col >> 2)] >> (col & 3)) & 1 ? dx * keep_scale : 0.0f;
-                    float *dst = p.dZ + ((size_t)(uint32_t)s_rowidx[row * p.L + t] * (uint32_t)H + col);
-                    if (p.store_dx)
-                        *dst = dx;          // deterministic mode: a row of its own per path step (det_scatter_kernel adds them up)
-                    else if (dx != 0.0f)    // (no atomic for an element dropout zeroed: 70 % of them at p = 0.7; BPTT 0.375 -> 0.361 ms)
-                        atomicAdd(dst, dx);
+                for (int k = 0; k < 4; k++) v[k] = scr[(16 * hk + 4 * j + k) * 33 + li_s];
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int rid = 16 * hk + 4 * j + k < rows_here ? rqj[k] : -1;      // (uniform over a half-wave)
+                    if (rid != cur) {
+                        if (cur >= 0) atomicAdd(p.dZ + ((size_t)(uint32_t)cur * (uint32_t)H + col_t), run);
+                        cur = rid;
+                        run = 0.0f;
+                    }
+                    run += v[k];
                 }
-                dh[r] = GRU ? acc[1][r] * inv_h + dc[r] : acc[1][r] * inv_h;
             }
+            if (cur >= 0) atomicAdd(p.dZ + ((size_t)(uint32_t)cur * (uint32_t)H + col_t), run);
+        } else {
+            i32x4 rid[4];       // accumulator registers 4 j .. 4 j + 3 are four consecutive tile rows
+#pragma unroll
+            for (int j = 0; j < 4; j++) rid[j] = *reinterpret_cast<const i32x4 *>(s_rowidx + t * MT + 8 * j + hk4);
+            if (p.store_dx) {           // deterministic mode: a row of its own per path step (det_scatter_kernel adds them up)
+#pragma unroll
+                for (int r = 0; r < 16; r++)
+                    if (acc_row(r, lane_t) < rows_here) p.dZ[(size_t)(uint32_t)rid[r >> 2][r & 3] * (uint32_t)H + col_t] = dxv[r];
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; r++)    // (no atomic for an element dropout zeroed: 70 % of them at p = 0.7; BPTT 0.375 -> 0.361 ms)
+                    if (dxv[r] != 0.0f) atomicAdd(p.dZ + ((size_t)(uint32_t)rid[r >> 2][r & 3] * (uint32_t)H + col_t), dxv[r]);
+            }
+#pragma unroll
+            for (int r = 0; r < 16; r++) dh[r] = GRU ? acc[1][r] * inv_h + dc[r] : acc[1][r] * inv_h;
         }
         HSTAMP(6 * (p.L - 1 - t) + 5);
     }
     HSTAMP_RT(63);
-    if (tid == 0 && launch_max > 0.0f) atomicMax(&p.range->dg, __float_as_uint(launch_max));
+    if (wave_u == 0 && fresh_lane() == 0 && launch_max > 0.0f) atomicMax(&p.range->dg, __float_as_uint(launch_max));
 }
 
 // =====================================================================================================================
