@@ -283,6 +283,12 @@ __device__ __forceinline__ uint4 philox4(uint64_t seed, uint64_t ctr, uint32_t s
 }
 
 // keep-mask scale for 4 consecutive elements starting at element index 4*vec (keep prob 1-p)
+// The bits are a contract (tests/dropout_ref.py restates them, tests/test_gpu_dropout_masks.py reads them back):
+//   hash     philox4x32-10, counter words (vec lo, vec hi, stream, 0x50415448), key (seed lo, seed hi)
+//   keep     word >= (uint32)(p * 2^32), clamped at 4294967040;  a kept element is 1.0f / (1.0f - p)
+//   stream 1 recurrent input [L, P_total, Hk]: element [t, slot, 4 c4 + k] is word k of vec (t * P_total + slot) * (Hk / 4) + c4
+//   stream 2 classifier input [S_total, 2 Hk]: element e (row-major) is word e & 3 of vec e >> 2
+// with slot / P_total / S_total positions in the WHOLE batch (the explicit masks' layouts, include/pathnet_hip.h)
 __device__ __forceinline__ float4 dropout4(uint64_t seed, uint64_t vec, uint32_t stream, float p) {
     const uint4 r = philox4(seed, vec, stream);
     const float scale = 1.0f / (1.0f - p);
