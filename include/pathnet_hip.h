@@ -669,7 +669,8 @@ int pn_pagg_backward(pn_context *ctx, const pn_pagg_args *args, void *stream);
  * pn_pagg_forward keeps no per-path tensors and pn_pagg_backward has to re-run each micro-batch's recurrence, here a
  * micro-batch's forward, loss gradient and backward follow each other on the tensors still in the workspace.
  * A target outside [0, C) is handled as by pn_cross_entropy: *loss is NaN, the row's d loss / d logits is zero (every
- * gradient stays finite: the recurrent kernels' range scaling is not specified for non-finite values), no ignore_index. */
+ * gradient stays finite: the recurrent kernels' range scaling is not specified for non-finite values).  Class weights,
+ * ignore_index and label smoothing: pn_pagg_train_step_loss (with pn_loss_spec, below). */
 int pn_pagg_train_step(pn_context *ctx, const pn_pagg_args *args, const int64_t *target, float grad_scale, float *loss,
                        void *stream);
 
@@ -766,11 +767,62 @@ int pn_merw_probabilities(int32_t n, int64_t nnz, const int64_t *row_off, const 
  * targets, no ignore_index / label smoothing -- the reference uses neither): *loss (device float) receives the mean,
  * g_logits [rows, classes] (may be NULL) d loss / d logits = (softmax - onehot) / rows.  The log softmax is formed as
  * (x - max) - log(sum exp(x - max)): its error does not grow with the size of the logits.
- * A target outside [0, classes) -- the -1 that graph datasets give unlabelled nodes, torch's ignore_index = -100, which is
- * NOT implemented -- is never used as an index: its row contributes NaN to the loss (so *loss is NaN) and zeros to its
- * row of g_logits.  Filter such rows out before the call. */
+ * A target outside [0, classes) -- the -1 that graph datasets give unlabelled nodes, torch's ignore_index = -100 -- is
+ * never used as an index: its row contributes NaN to the loss (so *loss is NaN) and zeros to its row of g_logits.  This
+ * call has no options; class weights, ignore_index and label smoothing are pn_cross_entropy_ex's (below). */
 int pn_cross_entropy(const float *logits, const int64_t *target, int32_t rows, int32_t classes, float *loss,
                      float *g_logits, void *stream);
+
+/* ---- loss options: class weights, ignore_index, label smoothing (torch.nn.CrossEntropyLoss's arguments) ---------------
+ * With p = softmax(x_r), lp = (x - max) - log sum exp(x - max), w the class weights (all ones when weight is NULL),
+ * Wsum = sum_c w[c], e = label_smoothing, C = classes, and row r KEPT iff has_ignore == 0 or target[r] != ignore_index:
+ *   row loss   l_r         = kept * [ (1 - e) w[t] (-lp[t])  +  (e / C) sum_c w[c] (-lp[c]) ]
+ *   d l_r / d x_c          = kept * [ (1 - e) w[t] (p_c - [c == t])  +  (e / C) (Wsum p_c - w[c]) ]
+ *   D                      = sum over the kept rows of w[t_r]            (the weighted mean's denominator)
+ *   loss                   = k * sum_r l_r,   k = grad_scale / D (PN_LOSS_MEAN)  or  grad_scale (PN_LOSS_SUM)
+ * which is torch.nn.functional.cross_entropy(weight, ignore_index, label_smoothing, reduction) for grad_scale = 1, but
+ * for two cases, where this library's rule -- every gradient stays finite -- wins:
+ *   - a target outside [0, C) that is not the ignore value is handled as by pn_cross_entropy: NaN into the loss, a zero
+ *     gradient row; it adds nothing to D.  The ignore test comes first: an ignore_index that is a valid class drops that
+ *     class's rows.  No address is formed from an unchecked target (a clamped index and selects).
+ *   - D == 0 under PN_LOSS_MEAN (every row ignored, or only zero-weight classes among the kept rows): the loss is NaN and
+ *     every gradient is ZERO (torch: NaN gradients in the zero-weight case).
+ * An ignored row's logits are never looked at for the loss (they may be NaN).  D depends on the targets and is formed ON
+ * THE DEVICE, by one workgroup in a fixed order at any row count (the same bits in every run), into the caller's
+ * `denominator`; the kernels read it from there, so nothing is read back and a step captured in a hipGraph follows
+ * targets whose ignored count changes between replays.  With denominator_given != 0 the calls read the value that is
+ * there instead (a rank of a sharded step passes the all-reduced D).  Added without an ABI bump: three new symbols and
+ * one new struct, no existing struct or signature changed, so pn_abi_version keeps answering 12. */
+#define PN_LOSS_MEAN 0
+#define PN_LOSS_SUM 1
+typedef struct pn_loss_spec {
+    const float *weight;        /* dev [C] or NULL */
+    int64_t ignore_index;
+    int32_t has_ignore;
+    float label_smoothing;      /* [0, 1] */
+    int32_t reduction;          /* PN_LOSS_MEAN (weighted mean, /D) | PN_LOSS_SUM */
+    float grad_scale;           /* multiplies the loss and every gradient; 1 = torch */
+    float *denominator;         /* dev float, caller-owned; written with D by the call ... */
+    int32_t denominator_given;  /* ... or, when != 0, read (a rank of a sharded step passes the all-reduced D) */
+} pn_loss_spec;
+/* Argument errors of the three calls, PN_ERR_ARG before any launch: spec NULL, label_smoothing outside [0, 1] (or NaN),
+ * a reduction that is neither value, PN_LOSS_MEAN without a denominator. */
+/* spec->denominator[0] = D of target[0 .. rows) (needs the denominator whatever the reduction; denominator_given is not
+ * looked at). */
+int pn_loss_denominator(const int64_t *target, int32_t rows, int32_t classes, const pn_loss_spec *spec, void *stream);
+/* pn_cross_entropy with the options: *loss and g_logits [rows, classes] (may be NULL) as above.  Writes D first unless
+ * denominator_given (PN_LOSS_SUM: only when a denominator is set).  With every option off (weight NULL, has_ignore 0,
+ * label_smoothing 0, PN_LOSS_MEAN, grad_scale 1) the loss and the gradient have pn_cross_entropy's bits. */
+int pn_cross_entropy_ex(const float *logits, const int64_t *target, int32_t rows, int32_t classes, const pn_loss_spec *spec,
+                        float *loss, float *g_logits, void *stream);
+/* pn_pagg_train_step_sparse (features may be NULL: pn_pagg_train_step) with the options: spec->grad_scale stands where
+ * grad_scale stood, but multiplies the REDUCED loss (1 with PN_LOSS_MEAN = torch's weighted mean; the plain call's
+ * grad_scale = 1 / S is PN_LOSS_MEAN's 1 when no row is ignored and no weight given).  D is formed once, over the call's
+ * whole S rows, before the micro-batch loop.  Every route of the plain call has its option-aware twin (the one-launch
+ * pooling step, the three launches of the deterministic mode and PN_POOL_STEP=0/2); the deterministic mode is bitwise
+ * reproducible with options as without. */
+int pn_pagg_train_step_loss(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *features /* may be NULL */,
+                            const pn_loss_spec *spec, const int64_t *target, float *loss, void *stream);
 
 /* One Adam update of a list of tensors in a single launch, with the semantics of torch.optim.Adam(lr, betas, eps,
  * weight_decay) (:295-296): g += weight_decay * p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;

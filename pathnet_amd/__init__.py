@@ -14,7 +14,7 @@ Everything computes through csrc/libpathnet_hip.so (C ABI: include/pathnet_hip.h
 """
 from . import _lib  # noqa: F401
 from .modules import PAGG, PathNet, PathNet_homo  # noqa: F401
-from .optim import Adam, CrossEntropyLoss, StepState, backward, cross_entropy  # noqa: F401
+from .optim import Adam, CrossEntropyLoss, StepState, backward, balanced_class_weight, cross_entropy  # noqa: F401
 from .sampler import (DRAW_GLIBC_REPLAY, DRAW_PHILOX, BiasedSampler, MerwSampler, PathAnnotator,  # noqa: F401
                       PathReport, UniformSampler)
 from .pathprob import PathProb, importance_weights  # noqa: F401

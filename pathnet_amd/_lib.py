@@ -90,6 +90,16 @@ class PathProbOut(ctypes.Structure):
     _fields_ = [(k, vp) for k in FIELDS]
 
 
+LOSS_MEAN, LOSS_SUM = 0, 1        # pn_loss_spec.reduction
+
+
+class LossSpec(ctypes.Structure):
+    """struct pn_loss_spec: class weights, ignore_index and label smoothing of the cross entropy"""
+    _fields_ = [("weight", vp), ("ignore_index", ctypes.c_int64), ("has_ignore", ctypes.c_int32),
+                ("label_smoothing", ctypes.c_float), ("reduction", ctypes.c_int32), ("grad_scale", ctypes.c_float),
+                ("denominator", vp), ("denominator_given", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes): every symbol include/pathnet_hip.h declares
 class AdamTensor(ctypes.Structure):
     """struct pn_adam_tensor"""
@@ -189,6 +199,10 @@ SIGNATURES = {
     "pn_merw_probabilities": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp, vp, c_f64p, ctypes.c_int32,
                                              ctypes.c_double, c_i32p, vp, ctypes.c_int64, vp]),
     "pn_cross_entropy": (ctypes.c_int, [vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp]),
+    "pn_loss_denominator": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(LossSpec), vp]),
+    "pn_cross_entropy_ex": (ctypes.c_int, [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(LossSpec), vp, vp, vp]),
+    "pn_pagg_train_step_loss": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures),
+                                               ctypes.POINTER(LossSpec), vp, vp, vp]),
     "pn_adam_step": (ctypes.c_int, [ctypes.POINTER(AdamTensor), ctypes.c_int32, ctypes.c_float, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int64, vp, vp]),
     "pn_adam_step_advance": (ctypes.c_int, [ctypes.POINTER(AdamTensor), ctypes.c_int32, ctypes.c_float, ctypes.c_float,

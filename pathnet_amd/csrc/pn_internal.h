@@ -110,8 +110,15 @@ struct ZeroFill {
 // softmax cross entropy of `rows` rows (pn_train.hip): loss[0] += scale * sum of the rows' losses, g_logits (or null) =
 // (softmax - onehot) * scale.  pn_cross_entropy = zero-fill + this with scale = 1 / rows.
 // overwrite: loss[0] = ... instead of += (the zero fill, when one is needed at all, is issued here)
+// opts (pn_loss.h; null: the plain loss, and nothing below changes): the option-aware kernel, whose k = grad_scale / D or
+// grad_scale is formed on the device -- `scale` is not looked at
+struct LossOpts;
 int launch_cross_entropy(const float *logits, const int64_t *target, int rows, int classes, float scale, float *loss,
-                         float *g_logits, void *stream, bool overwrite = false);
+                         float *g_logits, void *stream, bool overwrite = false, const LossOpts *opts = nullptr);
+// pn_loss_spec, checked, as the kernels take it (PN_ERR_ARG names `who`)
+int loss_opts_from_spec(const pn_loss_spec *spec, const char *who, LossOpts *opts);
+// denom[0] = D = sum of w[target] over the kept rows: one workgroup, a fixed order at any row count
+int launch_loss_denominator(const int64_t *target, int rows, int classes, const LossOpts &opts, float *denom, void *stream);
 
 // ---- stable radix sort of (int32 key, int32 value) pairs (pn_sort.hip; the deterministic backward, pn_tables.hip) -
 size_t sort_temp_reserve(int64_t n);        // bytes of temporary storage to reserve for n pairs (no device needed)

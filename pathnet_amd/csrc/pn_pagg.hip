@@ -41,6 +41,7 @@
 #include "pn_gemm.h"
 #include "pn_internal.h"
 #include "pn_kernels.h"
+#include "pn_loss.h"
 #include "pn_seq.h"
 #include "pn_sparse.h"
 
@@ -828,6 +829,27 @@ __global__ __launch_bounds__(256) void pool_step_kernel(PoolStepParams p) {
     __syncthreads();
     pool_bwd_wg_body<HI>(p.b, lds);
 }
+// ---- the step with pn_loss_spec's options (pn_pagg_train_step_loss): the row is pn_loss.h's, as cross_entropy_opts_kernel
+// walks it; k = grad_scale / D comes from D in device memory.  A kernel of its own: pool_step_kernel is as it was.
+struct PoolStepLossParams {
+    PoolStepParams s;       // (s.scale is not read: the options carry grad_scale)
+    LossOpts o;
+};
+template <int HI>
+__global__ __launch_bounds__(256) void pool_step_loss_kernel(PoolStepLossParams q) {
+    extern __shared__ float lds[];
+    const PoolStepParams &p = q.s;
+    pool_fwd_body(p.f, lds);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int g = blockIdx.x, classes = p.f.C;
+        float k_grad, k_loss;
+        loss_factors(q.o, k_grad, k_loss);
+        p.lossg[g] = ce_row_opts(p.f.out + (int64_t)g * classes, classes, p.target[g], q.o, k_grad, p.gout + (int64_t)g * classes);
+    }
+    __syncthreads();
+    pool_bwd_wg_body<HI>(p.b, lds);
+}
 // ---- the same step with the node's rows held in REGISTERS (round 6).  pool_step_kernel's bodies change the thread layout from
 // phase to phase (eight lanes per member for the dot products, a lane per column for the sums) and therefore read the node's
 // W x H final hidden states four times from memory, behind one another: ~15 dependent round trips per node, 47 us for 1 299
@@ -842,333 +864,11 @@ __device__ long long g_pool_trace[2048 * 12];
 #else
 #define PTRACE(n) do { } while (0)
 #endif
-template <int MM, int HI>
-__global__ __launch_bounds__(256, 6) void pool_step2_kernel(PoolStepParams p) {      // (six workgroups per CU: 1 536 slots)
-    extern __shared__ float lds[];
-    const PoolParams &f = p.f;
-    const PoolBwdParams &b = p.b;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int g = blockIdx.x, H = f.H, W = f.W, C = f.C;
-    const bool has_att = f.variant != PN_VARIANT_PAGG;
-    // per-member scalars (wave-uniform) live in LDS, [wave][MM] each: as register arrays they cost 40 VGPRs and two of the six
-    // workgroups a CU can hold
-    float *cf = lds + wave * MM;        // [4][MM] pooling coefficients
-    float *dsl = lds + 4 * MM + wave * MM;      // [4][MM] d score
-    float *sc = lds + 8 * MM;           // [4 MM] activated scores in member order (HETERO softmax)
-    float *part4 = sc + 4 * MM;         // [4][H]  waves' partial pooled sums; later [4][2H] attention-weight partials
-    float *l1s = part4 + 8 * H;         // [2H] classifier input
-    float *dp = l1s + 2 * H;            // [H]  d pooled / W
-    float *lg = dp + H;                 // [C] logits, then [C] their gradient
-    float *s_tot = lg + 2 * C;          // [4]
-    const float inv_w = 1.0f / (float)W;
-    const int64_t s0 = (int64_t)g * W;
-    PTRACE(0);
-
-    // ---- everything the node needs from memory, requested at once
-    float hn[MM][HI], e_r[HI], aw_h[HI], aw_e[HI];
-    const int e0 = has_att ? f.egoidx[s0] : 0;
-    // (the node's own row of Xh, its target and the attention weights are asked for here as well, with the rows: loaded where they
-    //  are used they were two more dependent round trips behind barriers)
-    const int sel_g = min(max(f.sel[g], 0), f.N - 1);
-    // (a target outside [0, C): NaN loss, zero gradient row; the index into lg[] is clamped -- selects, no branch, no address
-    //  formed from it.  Workgroup-uniform: scalar registers)
-    const int64_t tgt64 = p.target[g];
-    const bool tgt_ok = tgt64 >= 0 && tgt64 < (int64_t)C;
-    const int tgt = tgt_ok ? (int)tgt64 : 0;
-    int same = 1;
-    const float *hn_g = f.hn + s0 * H;          // (a scalar base + one 32-bit offset per load: twenty 64-bit addresses would not fit)
-    // Every load below is unconditional (clamped addresses) and its value always used -- rows past W / columns past H are zeroed by a
-    // MULTIPLICATION, the members' start rows compared whatever the variant (PAGG: a valid dummy).  As selects, hipcc moved each load
-    // into a branch of its own with a wait behind it: thirty dependent round trips, 18 of the kernel's 40 us (r06_glue.txt section 23).
-    const int32_t *ego_g = has_att ? f.egoidx + s0 : reinterpret_cast<const int32_t *>(hn_g);
-    int egv[MM];
-#pragma unroll
-    for (int k = 0; k < MM; k++) {
-        const uint32_t memc = (uint32_t)min(wave + 4 * k, W - 1);
-        egv[k] = ego_g[memc];
-#pragma unroll
-        for (int i = 0; i < HI; i++) hn[k][i] = hn_g[memc * (uint32_t)H + (uint32_t)min(lane + 64 * i, H - 1)];
-    }
-#pragma unroll
-    for (int k = 0; k < MM; k++) {
-        same &= (int)(egv[k] == e0) | (int)!has_att;
-#pragma unroll
-        for (int i = 0; i < HI; i++) hn[k][i] *= (wave + 4 * k < W && lane + 64 * i < H) ? 1.0f : 0.0f;
-    }
-#pragma unroll
-    for (int i = 0; i < HI; i++) {
-        const int j = lane + 64 * i, jc = min(j, H - 1);
-        aw_h[i] = (has_att && j < H) ? f.att_w[jc] : 0.0f;
-        aw_e[i] = (has_att && j < H) ? f.att_w[H + jc] : 0.0f;
-        e_r[i] = (has_att && j < H) ? f.ego_tab[(int64_t)e0 * H + jc] : 0.0f;
-    }
-    const float xh_own = f.Xh[(int64_t)sel_g * H + min(tid, H - 1)];
-    const bool one_row = __syncthreads_and(same) != 0;
-    PTRACE(1);
-    // ---- scores and pooling coefficients of this wave's members (raw scores -> cf[], LeakyReLU slopes -> bits of `neg`)
-    uint32_t neg = 0;       // bit k: member k's raw score <= 0
-    if (has_att) {
-        const float ab = f.att_b[0];
-        float edot = 0.0f;
-#pragma unroll
-        for (int i = 0; i < HI; i++) edot += e_r[i] * aw_e[i];
-        edot = wave_sum_u(edot);
-#pragma unroll
-        for (int k = 0; k < MM; k++) {
-            const int mem = wave + 4 * k;
-            float part = 0.0f;
-#pragma unroll
-            for (int i = 0; i < HI; i++) part += hn[k][i] * aw_h[i];
-            float ed = edot;
-            if (!one_row) {         // (rare: a member whose path starts elsewhere)
-                const int64_t er = (int64_t)f.egoidx[s0 + min(mem, W - 1)] * H;
-                float pe = 0.0f;
-#pragma unroll
-                for (int i = 0; i < HI; i++) {
-                    const int j = lane + 64 * i;
-                    if (j < H) pe += f.ego_tab[er + j] * aw_e[i];
-                }
-                ed = wave_sum_u(pe);
-            }
-            const float raw = wave_sum_u(part) + ed + ab;
-            if (!(raw > 0.0f)) neg |= 1u << k;
-            if (lane == 0) {
-                cf[k] = raw;
-                if (mem < W) f.rawsc[s0 + mem] = raw;
-            }
-        }
-    } else if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < MM; k++) {
-            cf[k] = 0.0f;
-            if (wave + 4 * k < W) f.rawsc[s0 + wave + 4 * k] = 0.0f;
-        }
-    }
-    if (f.variant == PN_VARIANT_HETERO) {       // softmax over the W members of LeakyReLU(score)
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < MM; k++) {
-                const int mem = wave + 4 * k;
-                const float r = cf[k];
-                if (mem < W) sc[mem] = r > 0.0f ? r : 0.01f * r;
-            }
-        }
-        __syncthreads();
-        const float v = lane < W ? sc[lane] : -3.4e38f;       // (W <= 4 MM <= 64)
-        const float mx = wave_max(v);
-        const float sum = wave_sum_u(lane < W ? expf(v - mx) : 0.0f);
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < MM; k++) {
-                const float r = cf[k];
-                cf[k] = expf((r > 0.0f ? r : 0.01f * r) - mx) / sum;
-            }
-        }
-    } else if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < MM; k++) cf[k] = f.variant == PN_VARIANT_HOMO ? 1.0f + cf[k] : 1.0f;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (cf[] of this wave: written by lane 0, read by the wave)
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < MM; k++)
-            if (wave + 4 * k < W) f.coef[s0 + wave + 4 * k] = cf[k];
-    }
-    // ---- pooled = mean_w coef_w h_w
-    PTRACE(2);
-#pragma unroll
-    for (int i = 0; i < HI; i++) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < MM; k++) acc += cf[k] * hn[k][i];       // (members past W hold zeros)
-        const int j = lane + 64 * i;
-        if (j < H) part4[wave * H + j] = acc;
-    }
-    __syncthreads();
-    PTRACE(3);
-    // ---- layer1 = dropout([Xh[sel[g]] ; pooled]); the masks stay in registers for the backward
-    float m_a = 1.0f, m_b = 1.0f;       // this thread's column tid (< H)
-    if (tid < H) {
-        const int j = tid;
-        const uint64_t gg = (uint64_t)(f.goff + g);
-        float a = xh_own, bq = (part4[j] + part4[H + j] + part4[2 * H + j] + part4[3 * H + j]) * inv_w;
-        if (f.mask) {
-            m_a = f.mask[gg * 2 * H + j];
-            m_b = f.mask[gg * 2 * H + H + j];
-        } else if (f.p_drop > 0.0f) {
-            const uint64_t seed = f.dyn ? f.dyn->seed : f.seed;
-            m_a = dropout1(seed, gg * 2 * H + j, 2u, f.p_drop);
-            m_b = dropout1(seed, gg * 2 * H + H + j, 2u, f.p_drop);
-        }
-        a *= m_a;
-        bq *= m_b;
-        float *l1 = f.layer1 + (int64_t)g * 2 * H;
-        l1[j] = a;
-        l1[H + j] = bq;
-        l1s[j] = a;
-        l1s[H + j] = bq;
-    }
-    __syncthreads();
-    PTRACE(4);
-    for (int c = wave; c < C; c += 4) {
-        // (a fixed trip count with clamped addresses: the row's loads leave together instead of one round trip per 64 columns)
-        const float *wrow = f.fc2_w + (int64_t)c * 2 * H;
-        float wv[2 * HI];
-#pragma unroll
-        for (int q = 0; q < 2 * HI; q++) wv[q] = wrow[min(lane + 64 * q, 2 * H - 1)];
-        float part = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 2 * HI; q++) {
-            const int j = lane + 64 * q;
-            if (j < 2 * H) part += l1s[j] * wv[q];
-        }
-        part = wave_sum_u(part);
-        if (lane == 0) {
-            const float v = part + f.fc2_b[c];
-            f.out[(int64_t)g * C + c] = v;
-            lg[c] = v;
-        }
-    }
-    __syncthreads();
-    PTRACE(5);
-    if (wave == 0) {        // the row's cross entropy as cross_entropy_kernel computes it, a lane per class (the sum in another order)
-        float m = -3.4e38f;
-        for (int c = lane; c < C; c += 64) m = fmaxf(m, lg[c]);
-        m = wave_max(m);
-        float sum = 0.0f;
-        for (int c = lane; c < C; c += 64) sum += expf(lg[c] - m);
-        const float ls = logf(wave_sum_u(sum));
-        const int t = tgt;
-        const float row = ls - (lg[t] - m);
-        if (lane == 0) p.lossg[g] = tgt_ok ? row : NAN;
-        float *go = p.gout + (int64_t)g * C;
-        for (int c = lane; c < C; c += 64) {
-            const float gv = (expf((lg[c] - m) - ls) - (c == t ? 1.0f : 0.0f)) * p.scale;
-            go[c] = tgt_ok ? gv : 0.0f;
-            lg[C + c] = tgt_ok ? gv : 0.0f;
-        }
-    }
-    __syncthreads();
-    PTRACE(6);
-    // ---- backward: d layer1 = g_out . fc2_w (masked): its ego half onto the node's row of d Xh, its pooled half / W = dp
-    if (tid < H) {
-        const int j = tid;
-        float a = 0.0f, bq = 0.0f;
-        for (int c0 = 0; c0 < C; c0 += 4) {     // four classes' loads in flight (clamped rows, masked sums)
-            float wa[4], wb[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float *wrow = f.fc2_w + (int64_t)min(c0 + q, C - 1) * 2 * H;
-                wa[q] = wrow[j];
-                wb[q] = wrow[H + j];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float go = c0 + q < C ? lg[C + c0 + q] : 0.0f;
-                a += go * wa[q];
-                bq += go * wb[q];
-            }
-        }
-        atomicAdd(&b.dXh[(int64_t)sel_g * H + j], a * m_a);
-        dp[j] = bq * m_b * inv_w;
-    }
-    __syncthreads();
-    PTRACE(7);
-    float dpr[HI];
-#pragma unroll
-    for (int i = 0; i < HI; i++) {
-        const int j = lane + 64 * i;
-        dpr[i] = j < H ? dp[j] : 0.0f;
-    }
-    {       // d coef of this wave's members -> dsl[]; HETERO: through the softmax
-        float tpart = 0.0f;
-#pragma unroll
-        for (int k = 0; k < MM; k++) {
-            float part = 0.0f;
-#pragma unroll
-            for (int i = 0; i < HI; i++) part += hn[k][i] * dpr[i];
-            const float dco = wave_sum_u(part);
-            if (wave + 4 * k < W) tpart += cf[k] * dco;
-            if (lane == 0) dsl[k] = dco;
-        }
-        if (f.variant == PN_VARIANT_HETERO) {
-            if (lane == 0) s_tot[wave] = tpart;
-            __syncthreads();
-            const float tot = (s_tot[0] + s_tot[1]) + (s_tot[2] + s_tot[3]);
-            if (lane == 0) {
-#pragma unroll
-                for (int k = 0; k < MM; k++) dsl[k] = cf[k] * (dsl[k] - tot) * ((neg >> k) & 1u ? 0.01f : 1.0f);
-            }
-        } else if (f.variant != PN_VARIANT_HOMO && lane == 0) {
-#pragma unroll
-            for (int k = 0; k < MM; k++) dsl[k] = 0.0f;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    PTRACE(8);
-    // ---- per member: d h_n; the attention-weight and attention-ego terms accumulate in registers
-    float gaw_h[HI], gaw_e[HI], ego_acc[HI], gab = 0.0f;
-#pragma unroll
-    for (int i = 0; i < HI; i++) gaw_h[i] = gaw_e[i] = ego_acc[i] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < MM; k++) {
-        const int mem = wave + 4 * k;
-        if (mem >= W) break;            // (wave-uniform)
-        const float ds = dsl[k], ck = cf[k];
-        const int64_t er = (has_att && !one_row) ? (int64_t)f.egoidx[s0 + mem] * H : 0;
-#pragma unroll
-        for (int i = 0; i < HI; i++) {
-            const int j = lane + 64 * i;
-            if (j < H) {
-                float dh = ck * dpr[i];
-                if (has_att) {
-                    dh += ds * aw_h[i];
-                    gaw_h[i] += ds * hn[k][i];
-                    const float eg = ds * aw_e[i];
-                    if (one_row) {
-                        gaw_e[i] += ds * e_r[i];
-                        ego_acc[i] += eg;
-                    } else {
-                        gaw_e[i] += ds * f.ego_tab[er + j];
-                        atomicAdd(&b.dego[er + j], eg);
-                    }
-                }
-                b.dhn[(s0 + mem) * H + j] = dh;
-            }
-        }
-        gab += ds;
-    }
-    PTRACE(9);
-    if (!has_att) return;       // block-uniform
-    float *red = part4;         // [4][2H]
-    if (one_row) {
-#pragma unroll
-        for (int i = 0; i < HI; i++) {
-            const int j = lane + 64 * i;
-            if (j < H) red[wave * H + j] = ego_acc[i];
-        }
-        __syncthreads();
-        if (tid < H) atomicAdd(&b.dego[(int64_t)e0 * H + tid], (red[tid] + red[H + tid]) + (red[2 * H + tid] + red[3 * H + tid]));
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < HI; i++) {
-        const int j = lane + 64 * i;
-        if (j < H) {
-            red[wave * 2 * H + j] = gaw_h[i];
-            red[wave * 2 * H + H + j] = gaw_e[i];
-        }
-    }
-    __syncthreads();
-    float *out = b.det_att + (int64_t)g * (2 * H + 4);
-    for (int j = tid; j < 2 * H; j += 256) out[j] = red[j] + red[2 * H + j] + red[4 * H + j] + red[6 * H + j];
-    if (lane == 0) out[2 * H + wave] = gab;
-    PTRACE(10);
-}
+// (the kernel's text: pn_pool_step2.inc, once as pool_step2_kernel, once with the loss options as pool_step2_loss_kernel)
+#include "pn_pool_step2.inc"
+#define PN_STEP2_LOSS_OPTS
+#include "pn_pool_step2.inc"
+#undef PN_STEP2_LOSS_OPTS
 inline size_t pool_step2_lds_bytes(int MM, int H, int C) { return (size_t)(12 * MM + 8 * H + 2 * H + H + 2 * C + 8) * sizeof(float); }
 
 // loss[0] (+)= scale * sum of the rows' terms, in cross_entropy_kernel's order (one workgroup of 1024 threads)
@@ -1188,6 +888,28 @@ __global__ __launch_bounds__(1024) void loss_sum_kernel(const float *__restrict_
             *loss = t * scale;
         else
             atomicAdd(loss, t * scale);
+    }
+}
+
+// the same with the options' k = grad_scale / D (mean) or grad_scale (sum), formed here from D in device memory
+__global__ __launch_bounds__(1024) void loss_sum_opts_kernel(const float *__restrict__ lossg, int rows, LossOpts o,
+                                                             float *__restrict__ loss, int store) {
+    __shared__ float part[16];
+    float mine = 0.0f;
+    for (int r = threadIdx.x; r < rows; r += 1024) mine += lossg[r];
+#pragma unroll
+    for (int of = 32; of > 0; of >>= 1) mine += __shfl_xor(mine, of, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float k_grad, k_loss;
+        loss_factors(o, k_grad, k_loss);
+        float t = 0.0f;
+        for (int w = 0; w < 16; w++) t += part[w];
+        if (store)
+            *loss = t * k_loss;
+        else
+            atomicAdd(loss, t * k_loss);
     }
 }
 
@@ -2178,13 +1900,18 @@ inline hipStream_t fork_if(const Call &c, bool fork) {
 // classifier of micro-batch b on `s`: g_fc2_w += g_out^T . layer1, g_fc2_b += colsum(g_out) -- nothing later reads them.
 // loss (behind the fused pooling step): first the fixed-order sum of the per-node loss terms into loss[0].
 // On the second stream the end is marked for the join.
-int run_fc2_grad(const Call &c, int b, JoinGuard &joiner, hipStream_t s, const float *g_out, float *loss, float grad_scale) {
+int run_fc2_grad(const Call &c, int b, JoinGuard &joiner, hipStream_t s, const float *g_out, float *loss, float grad_scale,
+                 const LossOpts *opts) {
     const Dims &d = c.d;
     const pn_pagg_args *a = c.a;
     const int H = d.H, Sb = c.groups(b);
     if (loss) {
-        hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, s, c.at<const float>(c.w.outb), Sb, grad_scale, loss,
-                           d.nb == 1 ? 1 : 0);
+        if (opts)
+            hipLaunchKernelGGL(loss_sum_opts_kernel, dim3(1), dim3(1024), 0, s, c.at<const float>(c.w.outb), Sb, *opts, loss,
+                               d.nb == 1 ? 1 : 0);
+        else
+            hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, s, c.at<const float>(c.w.outb), Sb, grad_scale, loss,
+                               d.nb == 1 ? 1 : 0);
         PN_CHECK_HIP(hipGetLastError());
     }
     if (g_out) {        // (no g_out: only the embedding is differentiated, g_fc2_* keep the backward's zero fill)
@@ -2248,7 +1975,7 @@ PoolBwdParams pool_bwd_params(const Call &c, int b, const float *g_out) {
 inline size_t pool_bwd_lds_bytes(const Dims &d) { return (size_t)(4 * (2 * d.W + d.H) + 8 * d.H + 8 * d.W) * sizeof(float); }
 
 // pn_pagg_train_step, default mode: pooling forward, loss and pooling backward of micro-batch b in one launch
-int run_pool_step(const Call &c, int b, const PoolBwdParams &pp, const int64_t *target, float grad_scale) {
+int run_pool_step(const Call &c, int b, const PoolBwdParams &pp, const int64_t *target, float grad_scale, const LossOpts *opts) {
     const Dims &d = c.d;
     const int H = d.H, Sb = pp.S, knob = knobs_of(c.ctx).pool_step;
     PoolStepParams ps{};
@@ -2265,7 +1992,18 @@ int run_pool_step(const Call &c, int b, const PoolBwdParams &pp, const int64_t *
     // make_dims does not bound: past 64 KiB (C > 7 424 at H = 128) the node goes to pool_step_kernel<4>, whose LDS does
     // not depend on C (64 W + 48 H bytes, within 64 KiB by make_dims)
     const size_t lds_step2 = pool_step2_lds_bytes(10, H, d.C);
-    if (d.W <= 40 && H <= 128 && H >= 32 && lds_step2 <= 64 * 1024 && knob >= 1 && knob != 2) {
+    const bool step2 = d.W <= 40 && H <= 128 && H >= 32 && lds_step2 <= 64 * 1024 && knob >= 1 && knob != 2;
+    if (opts) {         // pn_pagg_train_step_loss: the same three routes, their option-aware kernels
+        const PoolStepLossParams ql{ps, *opts};
+        if (step2) {
+            hipLaunchKernelGGL((pool_step2_loss_kernel<10, 2>), dim3(Sb), dim3(256), lds_step2, c.stream, ql);
+        } else if (H <= 256) {
+            hipLaunchKernelGGL(pool_step_loss_kernel<4>, dim3(Sb), dim3(256), lds_step, c.stream, ql);
+        } else {
+            if (int rc = ensure_dynamic_lds(c.ctx, reinterpret_cast<const void *>(pool_step_loss_kernel<16>), (int)lds_step)) return rc;
+            hipLaunchKernelGGL(pool_step_loss_kernel<16>, dim3(Sb), dim3(256), lds_step, c.stream, ql);
+        }
+    } else if (step2) {
         // the node's rows in registers (pool_step2_kernel); PN_POOL_STEP=2: the three bodies back to back
         hipLaunchKernelGGL((pool_step2_kernel<10, 2>), dim3(Sb), dim3(256), lds_step2, c.stream, ps);
     } else if (H <= 256) {
@@ -2653,7 +2391,8 @@ int pn_pagg_forward_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_spar
 // pn_pagg_backward, and -- with `target` -- pn_pagg_train_step: the forward of every micro-batch runs right before its
 // backward (saved tensors in place), the loss gradient of its rows is formed in between
 static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stream_, const int64_t *target, float grad_scale,
-                              float *loss, const pn_sparse_features *sp) {
+                              float *loss, const pn_sparse_features *sp, const LossOpts *opts = nullptr,
+                              float *denom_out = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     const bool fused = target != nullptr;
     Call c;
@@ -2664,6 +2403,9 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
             if (int rc = check_forward_args(c, "pn_pagg_train_step")) return rc;
         // (one micro-batch: the loss kernel overwrites -- launch_cross_entropy zero-fills only if it needs several workgroups)
         if (d.nb > 1 || d.S == 0) PN_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float), stream));
+        // (pn_pagg_train_step_loss) D of the call's whole S rows, once, ahead of the micro-batches that all divide by it
+        if (opts && denom_out && d.S > 0)
+            if (int rc = launch_loss_denominator(target, d.S, d.C, *opts, denom_out, stream)) return rc;
     }
     // (S == 0 -- a rank of a sharded batch without masked nodes: its index arrays and g_out are empty tensors, i.e. NULL;
     //  the call still zero-fills every gradient it was given)
@@ -2754,20 +2496,20 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
                 if (int rc = run_pool_fwd(c, b, out_b)) return rc;
                 if (fused)
                     if (int rc = launch_cross_entropy(out_b, target + (size_t)b * d.Sb, c.groups(b), d.C, grad_scale, loss,
-                                                      c.at<float>(c.w.gout), stream, d.nb == 1))
+                                                      c.at<float>(c.w.gout), stream, d.nb == 1, opts))
                         return rc;
             }
         }
         PoolBwdParams pp = pool_bwd_params(c, b, g_out);
         if (a->g_embed) pp.g_embed = a->g_embed + (size_t)b * d.Sb * 2 * H;     // (never with the pooling step: train_step refuses it)
         if (pool_step)
-            if (int rc = run_pool_step(c, b, pp, target, grad_scale)) return rc;
+            if (int rc = run_pool_step(c, b, pp, target, grad_scale, opts)) return rc;
         if (!small_behind_pool)
-            if (int rc = run_fc2_grad(c, b, joiner, fork_if(c, side_ok), g_out, loss_sum, grad_scale)) return rc;
+            if (int rc = run_fc2_grad(c, b, joiner, fork_if(c, side_ok), g_out, loss_sum, grad_scale, opts)) return rc;
         if (int rc = run_pool_bwd(c, pp, pool_step)) return rc;
         const hipStream_t small = fork_if(c, small_behind_pool);
         if (small_behind_pool)
-            if (int rc = run_fc2_grad(c, b, joiner, small, g_out, loss_sum, grad_scale)) return rc;
+            if (int rc = run_fc2_grad(c, b, joiner, small, g_out, loss_sum, grad_scale, opts)) return rc;
         if (int rc = run_att_reduce(c, joiner, small, pp)) return rc;
         if (d.det) {
             // (this micro-batch's orders were sorted on the second stream under its forward, when the backward re-ran it)
@@ -2812,6 +2554,24 @@ int pn_pagg_train_step_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_s
         return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp);
     }
     return pagg_backward_impl(ctx, a, stream, target, grad_scale, loss, sp);
+}
+
+int pn_pagg_train_step_loss(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const pn_loss_spec *spec,
+                            const int64_t *target, float *loss, void *stream) {
+    LossOpts o;
+    if (int rc = loss_opts_from_spec(spec, "pn_pagg_train_step_loss", &o)) return rc;
+    if (!a) PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step_loss: null args");
+    if (a->out_embed || a->out_path_weight || a->out_path_state || a->g_embed)
+        PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step_loss: out_embed / out_path_weight / out_path_state / g_embed are for "
+                            "pn_pagg_forward / pn_pagg_backward");
+    if (!loss || (a->shape.S > 0 && !target)) PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step_loss: null target / loss");
+    float *denom_out = spec->denominator_given ? nullptr : spec->denominator;
+    if (a->shape.S == 0) {          // nothing to aggregate: zero loss, zero gradients (and D = 0, when it is this call's to write)
+        PN_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float), (hipStream_t)stream));
+        if (denom_out) PN_CHECK_HIP(hipMemsetAsync(denom_out, 0, sizeof(float), (hipStream_t)stream));
+        return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp);
+    }
+    return pagg_backward_impl(ctx, a, stream, target, o.grad_scale, loss, sp, &o, denom_out);
 }
 
 }  // extern "C"

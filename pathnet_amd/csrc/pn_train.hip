@@ -10,6 +10,7 @@
 
 #include "../../include/pathnet_hip.h"
 #include "pn_internal.h"
+#include "pn_loss.h"
 
 namespace {
 
@@ -56,6 +57,60 @@ __global__ __launch_bounds__(1024) void cross_entropy_kernel(const float *__rest
             *loss = s * inv_rows;           // one workgroup computes the whole loss: no zero-fill launch ahead of it
         else
             atomicAdd(loss, s * inv_rows);  // (several workgroups, or a loss that accumulates over micro-batches)
+    }
+}
+
+// ---- the same with pn_loss_spec's options (class weights, ignore_index, label smoothing; pn_loss.h has the row) ----------
+// k = grad_scale / D or grad_scale is formed here from D in device memory: the launch carries no number that depends on
+// the targets.  Same launch shape, same summation order as cross_entropy_kernel.
+__global__ __launch_bounds__(1024) void cross_entropy_opts_kernel(const float *__restrict__ logits,
+                                                                  const int64_t *__restrict__ target, int rows, int classes,
+                                                                  pn::LossOpts o, float *__restrict__ loss,
+                                                                  float *__restrict__ g_logits, int store) {
+    __shared__ float part[16];
+    float k_grad, k_loss;
+    pn::loss_factors(o, k_grad, k_loss);
+    float mine = 0.0f;
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += gridDim.x * blockDim.x)
+        mine += pn::ce_row_opts(logits + (int64_t)r * classes, classes, target[r], o, k_grad,
+                                g_logits ? g_logits + (int64_t)r * classes : nullptr);
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) mine += __shfl_xor(mine, o2, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.0f;
+        for (int w = 0; w < (int)(blockDim.x >> 6); w++) s += part[w];
+        if (store)
+            *loss = s * k_loss;
+        else
+            atomicAdd(loss, s * k_loss);
+    }
+}
+
+// ---- D = sum over the kept rows of w[target]: one workgroup, thread i takes rows i, i + 1024, ... in order, then the
+// wavefronts' and the sixteen partial sums in a fixed order -- the same bits in every run at any row count.  A row is kept
+// when its target is a class and not the ignore value; the weight is read at a clamped index.
+__global__ __launch_bounds__(1024) void loss_denominator_kernel(const int64_t *__restrict__ target, int rows, int classes,
+                                                                pn::LossOpts o, float *__restrict__ denom) {
+    __shared__ float part[16];
+    float mine = 0.0f;
+#pragma unroll 4
+    for (int64_t r = threadIdx.x; r < rows; r += 1024) {
+        const int64_t t64 = target[r];
+        const bool kept = t64 >= 0 && t64 < (int64_t)classes && !(o.has_ignore && t64 == o.ignore);
+        const int t = kept ? (int)t64 : 0;
+        const float w = o.weight ? o.weight[t] : 1.0f;
+        mine += kept ? w : 0.0f;
+    }
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) mine += __shfl_xor(mine, o2, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.0f;
+        for (int w = 0; w < 16; w++) s += part[w];
+        *denom = s;
     }
 }
 
@@ -136,7 +191,7 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamList a) {
 namespace pn {
 // loss[0] += scale * sum over rows of (logsumexp - logit[target]);  g_logits = (softmax - onehot) * scale
 int launch_cross_entropy(const float *logits, const int64_t *target, int rows, int classes, float scale, float *loss,
-                         float *g_logits, void *stream_, bool overwrite) {
+                         float *g_logits, void *stream_, bool overwrite, const LossOpts *opts) {
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (rows < 1) return PN_OK;
     // Up to CE_ONE_BLOCK_ROWS rows one workgroup of 1024 threads walks them all (a few microseconds) and the loss is a
@@ -146,8 +201,32 @@ int launch_cross_entropy(const float *logits, const int64_t *target, int rows, i
     const int threads = rows <= CE_ONE_BLOCK_ROWS ? 1024 : 256;
     const int blocks = rows <= CE_ONE_BLOCK_ROWS ? 1 : ((rows + 255) / 256 < 256 ? (rows + 255) / 256 : 256);
     if (overwrite && blocks > 1) PN_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float), stream));
-    hipLaunchKernelGGL(cross_entropy_kernel, dim3(blocks), dim3(threads), 0, stream, logits, target, rows, classes, scale,
-                       loss, g_logits, overwrite && blocks == 1 ? 1 : 0);
+    if (opts)
+        hipLaunchKernelGGL(cross_entropy_opts_kernel, dim3(blocks), dim3(threads), 0, stream, logits, target, rows, classes,
+                           *opts, loss, g_logits, overwrite && blocks == 1 ? 1 : 0);
+    else
+        hipLaunchKernelGGL(cross_entropy_kernel, dim3(blocks), dim3(threads), 0, stream, logits, target, rows, classes, scale,
+                           loss, g_logits, overwrite && blocks == 1 ? 1 : 0);
+    PN_CHECK_HIP(hipGetLastError());
+    return PN_OK;
+}
+
+int loss_opts_from_spec(const pn_loss_spec *spec, const char *who, LossOpts *opts) {
+    if (!spec) PN_FAIL(PN_ERR_ARG, "%s: null loss spec", who);
+    if (!(spec->label_smoothing >= 0.0f && spec->label_smoothing <= 1.0f))
+        PN_FAIL(PN_ERR_ARG, "%s: label_smoothing %g outside [0, 1]", who, (double)spec->label_smoothing);
+    if (spec->reduction != PN_LOSS_MEAN && spec->reduction != PN_LOSS_SUM)
+        PN_FAIL(PN_ERR_ARG, "%s: reduction %d is neither PN_LOSS_MEAN nor PN_LOSS_SUM", who, (int)spec->reduction);
+    if (spec->reduction == PN_LOSS_MEAN && !spec->denominator)
+        PN_FAIL(PN_ERR_ARG, "%s: the mean reduction needs a denominator", who);
+    *opts = LossOpts{spec->weight, spec->denominator, spec->ignore_index, spec->has_ignore != 0 ? 1 : 0, spec->label_smoothing,
+                     spec->reduction == PN_LOSS_MEAN ? 1 : 0, spec->grad_scale};
+    return PN_OK;
+}
+
+int launch_loss_denominator(const int64_t *target, int rows, int classes, const LossOpts &opts, float *denom, void *stream_) {
+    hipLaunchKernelGGL(loss_denominator_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream_), target, rows,
+                       classes, opts, denom);
     PN_CHECK_HIP(hipGetLastError());
     return PN_OK;
 }
@@ -161,6 +240,25 @@ int pn_cross_entropy(const float *logits, const int64_t *target, int32_t rows, i
     if (rows < 1 || classes < 1) PN_FAIL(PN_ERR_ARG, "pn_cross_entropy: rows=%d classes=%d", rows, classes);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     return pn::launch_cross_entropy(logits, target, rows, classes, 1.0f / (float)rows, loss, g_logits, stream, true);
+}
+
+int pn_loss_denominator(const int64_t *target, int32_t rows, int32_t classes, const pn_loss_spec *spec, void *stream) {
+    pn::LossOpts o;
+    if (int rc = pn::loss_opts_from_spec(spec, "pn_loss_denominator", &o)) return rc;
+    if (!target || !spec->denominator) PN_FAIL(PN_ERR_ARG, "pn_loss_denominator: null target / denominator");
+    if (rows < 1 || classes < 1) PN_FAIL(PN_ERR_ARG, "pn_loss_denominator: rows=%d classes=%d", rows, classes);
+    return pn::launch_loss_denominator(target, rows, classes, o, spec->denominator, stream);
+}
+
+int pn_cross_entropy_ex(const float *logits, const int64_t *target, int32_t rows, int32_t classes, const pn_loss_spec *spec,
+                        float *loss, float *g_logits, void *stream) {
+    pn::LossOpts o;
+    if (int rc = pn::loss_opts_from_spec(spec, "pn_cross_entropy_ex", &o)) return rc;
+    if (!logits || !target || !loss) PN_FAIL(PN_ERR_ARG, "pn_cross_entropy_ex: null argument");
+    if (rows < 1 || classes < 1) PN_FAIL(PN_ERR_ARG, "pn_cross_entropy_ex: rows=%d classes=%d", rows, classes);
+    if (spec->denominator && !spec->denominator_given)
+        if (int rc = pn::launch_loss_denominator(target, rows, classes, o, spec->denominator, stream)) return rc;
+    return pn::launch_cross_entropy(logits, target, rows, classes, 0.0f, loss, g_logits, stream, true, &o);
 }
 
 static int adam_step_impl(const pn_adam_tensor *tensors, int32_t n_tensors, float lr, float beta1, float beta2, float eps,

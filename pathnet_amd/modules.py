@@ -86,12 +86,12 @@ class PaggCall:
                     "deterministic", "compact", "seq_math")
     __slots__ = SHAPE_FIELDS + ("p_seq", "p_cls", "seed", "mask_seq", "mask_cls", "step_state", "index_rows_local", "bank_w",
                                 "bank_b", "grad", "reuse_tables", "grad_scale", "path_state", "sparse_plan", "workspace",
-                                "features", "_shape", "_ws_bytes")
+                                "features", "loss", "_shape", "_ws_bytes")
 
     def __init__(self, variant, N, F, H, C, S, W, L, S_total=0, group_begin=0, batch_groups=0, cell=None, deterministic=False,
                  compact=None, seq_math=None, *, p_seq=0.0, p_cls=0.0, seed=0, mask_seq=None, mask_cls=None, step_state=None,
                  index_rows_local=False, bank_w=None, bank_b=None, grad=True, reuse_tables=0, grad_scale=1.0,
-                 path_state=False, sparse_plan=None, workspace=None, features=None):
+                 path_state=False, sparse_plan=None, workspace=None, features=None, loss=None):
         self.variant, self.N, self.F, self.H, self.C, self.S, self.W, self.L = variant, N, F, H, C, S, W, L
         self.S_total, self.group_begin, self.batch_groups, self.cell = S_total, group_begin, batch_groups, cell
         # decisions that shape the workspace are taken once per call and travel with its shape
@@ -105,6 +105,8 @@ class PaggCall:
         self.grad, self.reuse_tables, self.grad_scale, self.path_state = grad, reuse_tables, grad_scale, path_state
         self.sparse_plan, self.workspace = sparse_plan, workspace
         self.features = features        # PreparedFeatures of the call's X (fc0 over its non-zeros), or None: the dense kernels
+        # (optim.CrossEntropyLoss with options, grad_scale of the reduced loss) of forward_loss(loss=...), or None: the plain loss
+        self.loss = loss
         self._shape = self._ws_bytes = None
 
     def get(self, name, default=None):
@@ -429,7 +431,15 @@ class _PaggLossFunction(torch.autograd.Function):
             # the loss with one launch instead of one per tensor
             grads, gX, flat = call.grad_buffers(a, p, X if ctx.needs_input_grad[1] else None, flat=True)
             target = target.to(device=dev, dtype=torch.int64).contiguous()
-            if call.S > 0:
+            if call.S > 0 and call.loss is not None:
+                # (the spec's weight and denominator tensors live on the context until backward(); under capture they are the
+                #  graph's pool's, like every other tensor of the step)
+                loss_fn, scale = call.loss
+                spec, ctx.loss_keep = loss_fn.spec(dev, call.C, scale)
+                _lib.check(_lib.load().pn_pagg_train_step_loss(_lib.context(dev), ctypes.byref(a), call.features_ref(),
+                                                               ctypes.byref(spec), target.data_ptr(), loss.data_ptr(),
+                                                               _lib.stream_ptr(dev)))
+            elif call.S > 0:
                 _lib.check(_lib.load().pn_pagg_train_step_sparse(_lib.context(dev), ctypes.byref(a), call.features_ref(),
                                                                  target.data_ptr(), float(call.grad_scale), loss.data_ptr(),
                                                                  _lib.stream_ptr(dev)))
@@ -734,7 +744,8 @@ class _Aggregator(nn.Module):
                 self.fc2.weight, self.fc2.bias)
         return fw, fb, head + tuple(ws) + tuple(bs)
 
-    def forward_loss(self, X, neis, num_w, walk_len, indices, layer_type, target, indxx=None, grad_scale=None, fused=None):
+    def forward_loss(self, X, neis, num_w, walk_len, indices, layer_type, target, indxx=None, grad_scale=None, fused=None,
+                     loss=None):
         """(loss, logits) of a training step's forward + torch.nn.CrossEntropyLoss() (PathNet_run.py:343-346); loss.backward()
         yields the parameter gradients.  target: class index of every masked node, in the order of the logits' rows.
         grad_scale: weight of a row's loss (default 1 / rows = the mean).
@@ -742,8 +753,14 @@ class _Aggregator(nn.Module):
         call already computed) -- for a batch that runs in micro-batches this saves every micro-batch's second forward (the
         10 M-node configuration: 0.250 -> 0.222 s per step).  fused=False: the three calls, which is what a batch that fits
         the workspace is quicker with (measured 1.26 vs 1.29 ms per step at the headline shape).  None: fused exactly when
-        the batch needs micro-batches.  Same values either way."""
-        return self._run(X, neis, num_w, walk_len, indices, layer_type, target=target, grad_scale=grad_scale, fused=fused)
+        the batch needs micro-batches.  Same values either way.
+        loss: a pathnet_amd.CrossEntropyLoss with class weights, ignore_index, label smoothing or reduction="sum" (None, or one
+        with every option at its default: the plain mean, today's call and bits).  Every route above takes it -- fused or
+        not, micro-batches, sparse features, the deterministic mode -- and the weighted mean's denominator is formed on the
+        device over the whole batch, so a captured step follows targets whose ignored count changes.  With a loss, grad_scale
+        (default 1 / rows) times rows multiplies the reduced loss: the default is torch's value."""
+        return self._run(X, neis, num_w, walk_len, indices, layer_type, target=target, grad_scale=grad_scale, fused=fused,
+                         loss=loss)
 
     def forward(self, X, neis, num_w, walk_len, indices, layer_type, indxx=None, reuse_tables=False, group_slice=None):
         return self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=reuse_tables, group_slice=group_slice)
@@ -854,7 +871,7 @@ class _Aggregator(nn.Module):
                 seq_math_default() if self.seq_math is None else _SEQ_MATH[self.seq_math])
 
     def _run(self, X, neis, num_w, walk_len, indices, layer_type, reuse_tables=False, group_slice=None, target=None,
-             grad_scale=None, fused=None, batch_position=None, seed=None, _math=None, _encode=None):
+             grad_scale=None, fused=None, batch_position=None, seed=None, _math=None, _encode=None, loss=None):
         """reuse_tables (extension, inference only): X and the weights are those of the previous no-grad forward of this
         module -- the validation and the test forward of an epoch (PathNet_run.py:362, :378) -- so the projected
         feature matrix and the distance bank still sitting in the module's workspace are used again.
@@ -942,17 +959,22 @@ class _Aggregator(nn.Module):
                 raise ValueError("target holds %d classes, the batch has %d masked nodes" % (target.numel(), S))
             call.grad_scale = (1.0 / max(S, 1)) if grad_scale is None else float(grad_scale)
             target = target.reshape(-1)
+            from . import optim
+            if loss is not None and not isinstance(loss, optim.CrossEntropyLoss):
+                raise TypeError("forward_loss: loss must be a pathnet_amd.CrossEntropyLoss")
+            loss_fn = loss if loss is not None and loss.has_options else None       # (no option set: today's call)
+            if loss_fn is not None:     # the options' grad_scale multiplies the reduced loss
+                call.loss = (loss_fn, 1.0 if grad_scale is None else float(grad_scale) * max(S, 1))
             if fused is None:
                 fused = call.batch_groups > 0
             if fused:
                 res = _PaggLossFunction.apply(call, X, ids, codes, sel, target, *params)
             else:
-                from . import optim
                 out = _PaggFunction.apply(call, X, ids, codes, sel, *params)
-                loss = optim.CrossEntropyLoss()(out, target.to(device=dev, dtype=torch.int64))        # the mean over the S rows
-                if grad_scale is not None:
-                    loss = loss * (float(grad_scale) * max(S, 1))
-                res = (loss, out)
+                value = (loss_fn or optim.CrossEntropyLoss())(out, target.to(device=dev, dtype=torch.int64))
+                if grad_scale is not None:      # (the plain loss: the mean over the S rows)
+                    value = value * (float(grad_scale) * max(S, 1))
+                res = (value, out)
         elif _encode is not None:       # (encode(): _encode = whether the paths' final hidden states are wanted)
             res = _PaggEncodeFunction.apply(call, X, ids, codes, sel, *params)
         else:
@@ -965,7 +987,7 @@ class _Aggregator(nn.Module):
                 if first and self._range_wide:      # the very first result is not handed out on a range it cannot carry
                     return self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=False, group_slice=group_slice,
                                      target=target, grad_scale=grad_scale, fused=fused, batch_position=batch_position,
-                                     seed=seed, _math=_lib.SEQ_MATH_BF16X3, _encode=_encode)
+                                     seed=seed, _math=_lib.SEQ_MATH_BF16X3, _encode=_encode, loss=loss)
         return res
 
 

@@ -1,6 +1,8 @@
 """Loss and optimizer of the reference's training step (/root/reference/PathNet_run.py:295-297, :346-352) as single
 launches of the HIP library (``pn_cross_entropy``, ``pn_adam_step``): same arithmetic as ``torch.nn.CrossEntropyLoss()``
-and ``torch.optim.Adam(lr, betas, eps, weight_decay)``, ~10 us instead of ~100 us per step on the bench workload."""
+and ``torch.optim.Adam(lr, betas, eps, weight_decay)``, ~10 us instead of ~100 us per step on the bench workload.
+Class weights, ``ignore_index`` and label smoothing go through ``pn_cross_entropy_ex`` (one launch more: the weighted
+mean's denominator, formed on the device)."""
 import ctypes
 
 import torch
@@ -42,6 +44,38 @@ class _CrossEntropy(torch.autograd.Function):
         return ctx.g * grad_out, None
 
 
+class _CrossEntropyEx(torch.autograd.Function):
+    """pn_cross_entropy_ex: the loss with the options of `loss_fn` (a CrossEntropyLoss)"""
+
+    @staticmethod
+    def forward(ctx, logits, target, loss_fn):
+        if not logits.is_cuda:
+            raise RuntimeError("pathnet_amd.cross_entropy: logits must be on the GPU (there is no CPU fallback)")
+        lib = _lib.load()
+        x = logits.contiguous().float()
+        t = target.to(device=x.device, dtype=torch.int64).contiguous()
+        if x.dim() != 2 or t.shape != (x.shape[0],):
+            raise ValueError("cross_entropy: logits [rows, classes] and int targets [rows] expected")
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        g = torch.empty_like(x) if logits.requires_grad else None
+        with torch.cuda.device(x.device):
+            spec, keep = loss_fn.spec(x.device, x.shape[1], 1.0)
+            _lib.check(lib.pn_cross_entropy_ex(_lib.ptr(x), _lib.ptr(t), x.shape[0], x.shape[1], ctypes.byref(spec),
+                                               _lib.ptr(loss), _lib.ptr(g), _stream()))
+        ctx.g = g
+        ctx.keep = keep
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if ctx.g is None:
+            return None, None, None
+        one = _UNIT.get(grad_out.device)
+        if one is not None and grad_out.data_ptr() == one.data_ptr():
+            return ctx.g, None, None
+        return ctx.g * grad_out, None, None
+
+
 _UNIT = {}
 
 
@@ -63,20 +97,96 @@ def backward(loss):
     loss.backward(unit(loss.device))
 
 
-def cross_entropy(logits, target):
-    """Mean softmax cross entropy, = ``torch.nn.functional.cross_entropy(logits, target)``."""
-    return _CrossEntropy.apply(logits, target)
+def cross_entropy(logits, target, weight=None, ignore_index=None, label_smoothing=0.0, reduction="mean"):
+    """Softmax cross entropy, = ``torch.nn.functional.cross_entropy(logits, target, weight, ignore_index=...,
+    label_smoothing=..., reduction=...)`` -- see CrossEntropyLoss for the options and the two differences.  With every
+    option at its default this is the plain mean (pn_cross_entropy), as it always was."""
+    if weight is None and ignore_index is None and label_smoothing == 0.0 and reduction == "mean":
+        return _CrossEntropy.apply(logits, target)
+    return CrossEntropyLoss(weight, ignore_index, label_smoothing, reduction)(logits, target)
+
+
+def balanced_class_weight(target, num_classes, ignore_index=None):
+    """scikit-learn's "balanced" class weights of a target tensor: ``n_kept / (num_classes * count_c)``, where a row is
+    kept when its target is a class in ``[0, num_classes)`` and not ``ignore_index``; a class without a kept row gets
+    weight 0.  fp32 [num_classes] on the target's device; nothing is read back."""
+    t = torch.as_tensor(target).reshape(-1).to(torch.int64)
+    kept = (t >= 0) & (t < num_classes)
+    if ignore_index is not None:
+        kept = kept & (t != int(ignore_index))
+    count = torch.zeros(num_classes, dtype=torch.float32, device=t.device)
+    count.index_add_(0, torch.where(kept, t, torch.zeros_like(t)), kept.to(torch.float32))
+    w = count.sum() / (float(num_classes) * count)
+    return torch.where(count > 0, w, torch.zeros_like(w))
 
 
 class CrossEntropyLoss(torch.nn.Module):
-    """Drop-in for ``torch.nn.CrossEntropyLoss()`` as the reference constructs it (PathNet_run.py:297): the mean over all
-    rows, no class weights, no label smoothing and NO ``ignore_index``.  Every target must lie in ``[0, classes)``.  A row
-    whose target does not -- the ``-1`` of an unlabelled node, torch's default ``ignore_index = -100`` -- is not skipped:
-    it poisons the loss (NaN, so the mistake cannot go unnoticed) and gets a zero gradient row; the kernel never indexes
-    with it.  ``forward_loss(..., fused=True)`` of the modules behaves the same.  Select the labelled rows first."""
+    """``torch.nn.CrossEntropyLoss(weight, ignore_index=..., label_smoothing=..., reduction="mean" | "sum")`` for int64
+    class targets (include/pathnet_hip.h, pn_loss_spec, has the formulas).
+
+    ``ignore_index=None`` is the default and means NO ignore value -- pass ``-100`` for torch's default.  A bare
+    ``CrossEntropyLoss()`` is the reference's (PathNet_run.py:297): the plain mean through ``pn_cross_entropy``, and a
+    target outside ``[0, classes)`` -- the ``-1`` of an unlabelled node -- poisons the loss (NaN, so the mistake cannot go
+    unnoticed) and gets a zero gradient row.  With ``ignore_index=-1`` those rows are dropped instead: they add nothing to
+    the loss, to the weighted mean's denominator or to any gradient, and their logits are not looked at.
+
+    Two differences from torch, after this library's rule that every gradient stays finite: a target outside
+    ``[0, classes)`` that is NOT the ignore value still gives a NaN loss and a zero gradient row (torch raises or reads out
+    of bounds); and when the mean's denominator is zero -- every row ignored, or only zero-weight classes among the kept
+    rows -- the loss is NaN and every gradient is zero (torch: NaN gradients in the zero-weight case).
+
+    The denominator depends on the targets and is formed on the device; nothing is read back, so a captured step may be
+    replayed with targets whose ignored count differs.  ``forward_loss(..., loss=this)`` of the aggregators takes the same
+    options on every route.  Not covered: ``reduction="none"`` and probability targets."""
+
+    def __init__(self, weight=None, ignore_index=None, label_smoothing=0.0, reduction="mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise ValueError("CrossEntropyLoss: reduction %r (mean | sum)" % (reduction,))
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError("CrossEntropyLoss: label_smoothing %r outside [0, 1]" % (label_smoothing,))
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32).detach())
+        self.ignore_index = None if ignore_index is None else int(ignore_index)
+        self.label_smoothing = float(label_smoothing)
+        self.reduction = reduction
+        self._weight_on = None      # (device, source tensor, its version, contiguous fp32 copy on the device)
+
+    @property
+    def has_options(self):
+        return (self.weight is not None or self.ignore_index is not None or self.label_smoothing != 0.0 or
+                self.reduction != "mean")
+
+    def _device_weight(self, device):
+        w = self.weight
+        if w is None:
+            return None
+        if w.device == device and w.is_contiguous():
+            return w
+        hit = self._weight_on
+        if hit is None or hit[0] != device or hit[1] is not w or hit[2] != w._version:
+            hit = self._weight_on = (device, w, w._version, w.to(device).contiguous())
+        return hit[3]
+
+    def spec(self, device, classes, grad_scale=1.0):
+        """(pn_loss_spec, tensors it points to) for a call on `device` with `classes` classes: keep the second alive until
+        the call's kernels have run (under capture: allocate it inside the capture)."""
+        device = torch.device(device)
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        w = self._device_weight(device)
+        if w is not None and tuple(w.shape) != (classes,):
+            raise ValueError("CrossEntropyLoss: %d class weights for %d classes" % (w.numel(), classes))
+        mean = self.reduction == "mean"
+        denom = torch.empty(1, dtype=torch.float32, device=device) if mean else None
+        spec = _lib.LossSpec(_lib.ptr(w), self.ignore_index if self.ignore_index is not None else 0,
+                             0 if self.ignore_index is None else 1, self.label_smoothing,
+                             _lib.LOSS_MEAN if mean else _lib.LOSS_SUM, float(grad_scale), _lib.ptr(denom), 0)
+        return spec, (w, denom)
 
     def forward(self, logits, target):
-        return cross_entropy(logits, target)
+        if not self.has_options:
+            return _CrossEntropy.apply(logits, target)
+        return _CrossEntropyEx.apply(logits, target, self)
 
 
 class Adam(torch.optim.Optimizer):

@@ -54,13 +54,16 @@ def _index_tensor(mask_or_index, device):
 def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices, test_indices, num_w, hid_size,
                         walk_len, paths, round_i=0, *, epochs=1000, lr=0.005, weight_decay=0.0005, dropout=0.7,
                         device="cuda:0", save_dir="./saved_models", sampler_seed=0, model=None, verbose=False,
-                        fused_step=None):
+                        fused_step=None, loss=None):
     """paths: (ids, codes) tensors [epochs, N, W, L] (int32 / uint8, any device) or a MerwSampler.
     fused_step: True = forward, loss and backward of the training step in one library call (module.forward_loss ->
     pn_pagg_train_step), False = three calls, None = fused exactly when the batch needs micro-batches (then it saves every
     micro-batch's second forward).  Same values.
+    loss: a pathnet_amd.CrossEntropyLoss (class weights, ignore_index, label smoothing) handed to forward_loss; None = the
+    plain mean.  With ignore_index the training rows may hold unlabelled nodes (Y = the ignore value).
     Returns (test macro-F1, micro-F1, macro recall, macro precision, accuracy) at the best-validation epoch."""
     dev = torch.device(device)
+    loss_fn = loss          # (`loss` is the step's value below)
     X = torch.as_tensor(X).to(dev).float()
     Y = torch.as_tensor(Y).to(dev).long()
     tr, va, te = (_index_tensor(m, dev) for m in (train_indices, val_indices, test_indices))
@@ -90,7 +93,7 @@ def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices
     for epoch in range(epochs):
         model.train()
         ids_tr, codes_tr = paths_of(tr32, epoch, check=(epoch == 0))
-        loss, out = model.forward_loss(X, ids_tr, num_w, walk_len, tr32, codes_tr, Y[tr], fused=fused_step)
+        loss, out = model.forward_loss(X, ids_tr, num_w, walk_len, tr32, codes_tr, Y[tr], fused=fused_step, loss=loss_fn)
         opt.zero_grad(set_to_none=True)
         optim.backward(loss)        # = loss.backward(), minus the seed gradient's fill and multiply
         opt.step()
