@@ -86,7 +86,7 @@ struct StageTimer {
     void *stream;
 };
 
-// ---- every buffer a backward accumulates into (atomics / += / split-K), cleared by ONE launch (zero_kernel, pn_pagg.hip) ----
+// ---- every buffer a backward accumulates into (atomics / += / split-K), cleared by ONE launch (zero_kernel, pn_plan.hip) ----
 struct ZeroList {
     float *ptr[12];
     unsigned long long count[12];

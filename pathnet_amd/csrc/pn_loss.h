@@ -1,5 +1,5 @@
 // pn_loss.h -- the loss options (pn_loss_spec: class weights, ignore_index, label smoothing) as the kernels take them, and
-// the one row of the option-aware softmax cross entropy that pn_train.hip's stand-alone kernel and pn_pagg.hip's fused
+// the one row of the option-aware softmax cross entropy that pn_train.hip's stand-alone kernel and pn_pool.hip's fused
 // pooling step (pool_step_loss_kernel) share -- the same lines, hence the same bits on both routes.
 // The arithmetic is written out above pn_loss_spec in include/pathnet_hip.h.
 #pragma once

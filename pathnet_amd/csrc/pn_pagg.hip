@@ -6,26 +6,36 @@
 //   PAGG          /root/reference/baseline/GPRGNN/src/copy.py:327-359   (variant PAGG)
 // and the autograd backward the reference gets from loss.backward() (PathNet_run.py:351).
 //
-// How the reference's op sequence maps onto kernels (this file: the call's orchestration -- shapes, workspace, streams -- and
-// the kernels that are neither GEMMs nor the recurrence; pn_gemm.hip, pn_seqh.hip / pn_seq3.hip hold those)
+// This file is the call's orchestration and holds no kernel: shapes (Dims), the workspace layout (WsLayout), one resolved call
+// (Call), the stages run_* that fill the kernels' parameter structs from the workspace, choose streams and bracket the
+// per-stage profile, pagg_backward_impl and the entry points of the ABI.  The kernels and their launchers:
+//   pn_plan.hip   (pn_plan.h)   index plan, touched-row compaction, stand-alone gather (pn_pagg_gather), padded X, zero fill
+//   pn_gemm.hip   (pn_gemm.h)   node-level GEMMs: fc0, distance bank, classifier, their gradients
+//   pn_seqh.hip / pn_seq3.hip / pn_seq4.hip (pn_seq.h)   the fused recurrent kernels, fp16 x 2 and bf16 x 3 planes
+//   pn_seqgen.hip (pn_seq.h)    mean / sum encoders, the step-by-step recurrence for hidden sizes above 256
+//   pn_pool.hip   (pn_pool.h)   pooling forward / backward, the pooling step, loss sum, attention-weight reduce
+//   pn_det.hip    (pn_det.h)    deterministic scatter-add
+//   pn_rgrad.hip, pn_sparse.hip, pn_sort.hip, pn_train.hip   row-reduction weight gradients, sparse fc0, radix sort, loss
+//
+// How the reference's op sequence maps onto kernels
 //   fc0 (+ReLU)                      :175 / :242-243      -> gemm_kernel (pn_gemm.hip)            Xh[N,H]
 //   L Linear layers on P*L gathered rows, stack, select by distance code
 //                                    :185-191 / :249-255  -> ONE gemm over the N nodes:
 //        Z[v, d, :] = nets[d](Xh[v])  for every node v and code d  (N*L rows instead of P*L*L),
 //        after which "gather + select" is a single row gather  Z[node(q,t)*L + code(q,t)].
 //        Same dot products per emitted row, ~S*W*L/N times fewer FLOPs, no [P*L, L, H] temporary.
-//   X[neis] gather, flip / view quirks :179-184 / :246     -> plan_kernel (index plan only)
+//   X[neis] gather, flip / view quirks :179-184 / :246     -> plan_kernel (pn_plan.hip; index plan only)
 //   dropout, nn.LSTM / nn.RNN          :194-195 / :264-265 -> seq_fwdh_kernel (pn_seqh.hip, fp16 x 2 planes, the default) or
 //        seq_fwd3_kernel (pn_seq3.hip, bf16 x 3): coalesced row gather into an LDS path tile, MFMA for
 //        [x_t ; h_{t-1}] x [W_ih ; W_hh]^T, cell math in registers, h_t back to LDS, L steps without leaving the CU;
-//        hidden sizes above 256: the step-by-step recurrence gen_*_kernel below
+//        hidden sizes above 256: the step-by-step recurrence gen_*_kernel (pn_seqgen.hip)
 //   attention over the W paths, mean, concat ego, dropout, fc2
-//                                    :196-210 / :266-277  -> pool_fwd_kernel: one workgroup per node, wave shuffles for
-//        the per-path dot products and the reduction over W
+//                                    :196-210 / :266-277  -> pool_fwd_kernel (pn_pool.hip): one workgroup per node, wave shuffles
+//        for the per-path dot products and the reduction over W
 //   loss.backward()                    :351                -> pool_bwd_wg_kernel (pn_pagg_train_step: pool_step_kernel = pooling
 //        forward + cross entropy + pooling backward of a node in one launch), seq_bwdh / seq_bwd3 (BPTT + atomic scatter of the
 //        gather backward), wgradh / wgrad3 / wgrad4 (dG^T . [x|h]), gemm_kernel for the bank / fc0 gradients; deterministic
-//        mode: det_scatter_kernel and fixed-order finishes instead of the atomics
+//        mode: det_scatter_kernel (pn_det.hip) and fixed-order finishes instead of the atomics
 //
 // Precision: inputs, outputs, accumulation and all element-wise math are fp32.  The node-level GEMMs use the fp32-input MFMA
 // (an exact FMA chain) or bf16 x 3 planes on large graphs; the three recurrent GEMMs evaluate every fp32 product on the 16-bit
@@ -36,12 +46,12 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
-
+#include "pn_det.h"
 #include "pn_gemm.h"
 #include "pn_internal.h"
-#include "pn_kernels.h"
 #include "pn_loss.h"
+#include "pn_plan.h"
+#include "pn_pool.h"
 #include "pn_seq.h"
 #include "pn_sparse.h"
 
@@ -52,1064 +62,6 @@ using namespace pn;
 // block per wave in the forward (two: 0.411 vs 0.308 ms), no s_setprio around the MFMA phases, the independent small launches on the
 // context's second stream.
 namespace {
-
-// ================================================================================================
-// index plan (the reference's view/flip/transposes collapsed into index arithmetic)
-//   slot' = group * W + member is the order every later kernel uses (pooling groups contiguous).
-//   original sequence slot q:  HOMO/PAGG q = slot'            (group = q / W)
-//                              HETERO    q = member * S + group  (h_n.view(W, S, H), PathNet_run.py:196-197)
-//   step t of slot q reads   HOMO/PAGG node ids[q, t]
-//                            HETERO    r = q*L + t, node ids[r % P, L-1 - r / P]  (flip + reshape, :182-183)
-//   and always the code codes[q, t] (:184 / :248).
-// ================================================================================================
-// A call may cover a slice of the batch (pn_pagg_shape: S_total, group_begin): `slot` below is the position in the WHOLE
-// batch's slot' order, (group_begin + local group) * W + member; ids / codes are the whole batch's arrays.
-struct PlanDims {
-    int S_total, W, L, N;
-    int64_t P_total;          // S_total * W
-    int64_t row_base;         // batch position of row 0 of ids / codes (non-zero: the arrays hold a slice; HOMO / PAGG)
-};
-__device__ __forceinline__ void plan_entry(int variant, const int32_t *ids, const uint8_t *codes, const PlanDims &d,
-                                           int64_t slot, int t, int64_t &q, int &node, int &code) {
-    if (variant == PN_VARIANT_HETERO) {
-        const int64_t g = slot / d.W, mem = slot - g * d.W;
-        q = mem * d.S_total + g;
-        const int64_t r = q * d.L + t;
-        node = ids[(r % d.P_total) * d.L + (d.L - 1 - (int)(r / d.P_total))];
-    } else {
-        q = slot;
-        node = ids[(q - d.row_base) * d.L + t];
-    }
-    code = codes[(q - d.row_base) * d.L + t];
-}
-
-// slots [slot_begin, slot_begin + count) of the batch -> rowidx / egoidx / slotof of the local slots 0 .. count-1
-// rank: null (row of the full table: node * L + code) or the compact row of (code, node) -- compact_rows below
-__global__ void plan_kernel(int variant, const int32_t *__restrict__ ids, const uint8_t *__restrict__ codes, PlanDims d,
-                            int64_t slot_begin, int64_t count, const int32_t *__restrict__ rank, int32_t *__restrict__ rowidx,
-                            int32_t *__restrict__ egoidx, int32_t *__restrict__ slotof) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count * d.L) return;
-    const int64_t ls = i / d.L;
-    const int t = (int)(i - ls * d.L);
-    int64_t q;
-    int node, code;
-    plan_entry(variant, ids, codes, d, slot_begin + ls, t, q, node, code);
-    node = min(max(node, 0), d.N - 1);
-    code = min(code, d.L - 1);
-    const int32_t row = rank ? rank[(int64_t)code * d.N + node] : node * d.L + code;
-    rowidx[i] = row;
-    if (t == 0) {
-        slotof[ls] = (int32_t)q;      // position in the whole batch: what the dropout counters / explicit masks index
-        // attention ego: HOMO uses the transformed row of (q, step 0) (ego_full, :259-260);
-        // HETERO uses the untransformed Xh row of path q's first node (neis[0], :199)
-        egoidx[ls] = variant == PN_VARIANT_HETERO ? min(max(ids[(q - d.row_base) * d.L], 0), d.N - 1) : row;
-    }
-}
-
-// ---- touched-row compaction ---------------------------------------------------------------------------------------------
-// The distance bank is applied to (node, code) rows, N * L of them, whatever the batch reads (bank-before-gather, DESIGN.md
-// section 4).  When the batch's path steps cannot touch half of them (a 10 M-node graph with 100 000 masked nodes: 24 M path
-// steps, 60 M rows) the bank, its backward and the tables Z / dZ themselves shrink to the rows that ARE touched:
-//   flags[code * N + node] = 1 for every path step (mark_rows_kernel), exclusive scan -> rank, the compact row of every
-//   touched (code, node); list[compact row] = node; seg[c] = first compact row of code c (the rows are code-major, so each
-//   code's rows are one contiguous GEMM against that code's weights); the index plan writes compact rows.
-__global__ void mark_rows_kernel(int variant, const int32_t *__restrict__ ids, const uint8_t *__restrict__ codes, PlanDims d,
-                                 int64_t slot_begin, int64_t count, uint8_t *__restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count * d.L) return;
-    const int64_t ls = i / d.L;
-    int64_t q;
-    int node, code;
-    plan_entry(variant, ids, codes, d, slot_begin + ls, (int)(i - ls * d.L), q, node, code);
-    flags[(int64_t)min(code, d.L - 1) * d.N + min(max(node, 0), d.N - 1)] = 1;
-}
-constexpr int SCAN_BLOCK = 256 * 16;        // flags per workgroup
-__global__ __launch_bounds__(256) void scan_count_kernel(const uint8_t *__restrict__ flags, int64_t n, int32_t *__restrict__ bsum) {
-    __shared__ int red[4];
-    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + threadIdx.x * 16;
-    int c = 0;
-    if (base + 16 <= n) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(flags + base);
-        c = __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);        // (flags are 0 / 1 bytes)
-    } else {
-        for (int k = 0; k < 16; k++) c += base + k < n ? flags[base + k] : 0;
-    }
-    c = (int)wave_sum((float)c);        // <= 1024 per wave: exact in fp32
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-// exclusive scan of the block counts in place (one workgroup walks them: <= 15 k blocks for 60 M rows); total -> seg[L]
-__global__ __launch_bounds__(1024) void scan_blocks_kernel(int32_t *__restrict__ bsum, int nb, int32_t *__restrict__ total) {
-    __shared__ int part[1024];
-    const int per = (nb + 1023) / 1024, lo = threadIdx.x * per, hi = min(nb, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; i++) s += bsum[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int i = 0; i < 1024; i++) {
-            const int v = part[i];
-            part[i] = run;
-            run += v;
-        }
-        *total = run;
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int i = lo; i < hi; i++) {
-        const int v = bsum[i];
-        bsum[i] = run;
-        run += v;
-    }
-}
-__global__ __launch_bounds__(256) void scan_rank_kernel(const uint8_t *__restrict__ flags, int64_t n, int N, int L,
-                                                        const int32_t *__restrict__ bsum, int32_t *__restrict__ rank,
-                                                        int32_t *__restrict__ list, int32_t *__restrict__ seg) {
-    __shared__ int wsum[4];
-    const int64_t base = (int64_t)blockIdx.x * SCAN_BLOCK + threadIdx.x * 16;
-    uint8_t f[16];
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        f[k] = base + k < n ? flags[base + k] : 0;
-        c += f[k];
-    }
-    // exclusive scan of the 256 per-thread counts: inside the wave by shuffles, across the four waves through LDS
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int run = bsum[blockIdx.x] + inc - c;
-    for (int w = 0; w < wave; w++) run += wsum[w];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const int64_t i = base + k;
-        if (i < n) {
-            rank[i] = run;
-            const int code = (int)(i / N), node = (int)(i - (int64_t)code * N);
-            if (node == 0) seg[code] = run;         // first row of a code (rows are code-major)
-            if (f[k]) list[run] = node;
-            run += f[k];
-        }
-    }
-}
-
-// rows[slot', t, :] = table[rowidx, :]   (stand-alone gather, also the HBM-roofline microbenchmark)
-template <int VEC>
-__global__ __launch_bounds__(256) void gather_kernel(int variant, const float *__restrict__ table,
-                                                     const int32_t *__restrict__ ids,
-                                                     const uint8_t *__restrict__ codes, PlanDims d, int64_t slot_begin,
-                                                     int64_t count, int H, float *__restrict__ rows) {
-    const int hv = H / VEC;
-    const int64_t total = count * d.L * hv;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t row = i / hv;
-        const int c = (int)(i - row * hv);
-        const int64_t ls = row / d.L;
-        const int t = (int)(row - ls * d.L);
-        int64_t q;
-        int node, code;
-        plan_entry(variant, ids, codes, d, slot_begin + ls, t, q, node, code);
-        node = min(max(node, 0), d.N - 1);
-        code = min(code, d.L - 1);
-        const int64_t src = ((int64_t)node * d.L + code) * hv + c;
-        if (VEC == 4)
-            reinterpret_cast<float4 *>(rows)[i] = reinterpret_cast<const float4 *>(table)[src];
-        else
-            rows[i] = table[src];
-    }
-}
-
-// ---- order-agnostic path encoders of the ablation ("mean" / "sum" instead of the recurrent cell): h_n of a path is the
-//      mean (sum) over its L steps of the dropped-out rows the recurrent kernels would consume.  One thread per (path,
-//      4 columns); the backward scatters scale * mask * d h_n back onto the L table rows.
-struct SeqReduceParams {
-    const float *Z;          // [N*L, H]
-    const int32_t *rowidx;   // [P, L]
-    const int32_t *slotof;   // [P]
-    float *hn;               // [P, H]   forward output
-    const float *dhn;        // [P, H]   backward input
-    float *dZ;               // [N*L, H] backward output (atomic scatter)
-    int P, L, H;
-    int64_t Pmask;
-    float scale;             // 1/L (mean) or 1 (sum)
-    float p_drop;
-    uint64_t seed;
-    const pn_step_state *dyn;
-    const float *mask;       // [L, Pmask, H] or null
-};
-
-template <bool BACKWARD>
-__global__ __launch_bounds__(256) void seq_reduce_kernel(SeqReduceParams p) {
-    const int hv = p.H / 4;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)p.P * hv) return;
-    const int q = (int)(i / hv), c4 = (int)(i - (int64_t)q * hv);
-    const uint64_t seed = p.dyn ? p.dyn->seed : p.seed;
-    const int64_t slot = p.slotof[q];
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (BACKWARD) {
-        g = reinterpret_cast<const float4 *>(p.dhn)[i];
-        g.x *= p.scale; g.y *= p.scale; g.z *= p.scale; g.w *= p.scale;
-    }
-    for (int t = 0; t < p.L; t++) {
-        float4 m = make_float4(1.f, 1.f, 1.f, 1.f);
-        if (p.mask)
-            m = reinterpret_cast<const float4 *>(p.mask)[((int64_t)t * p.Pmask + slot) * hv + c4];
-        else if (p.p_drop > 0.0f)
-            m = dropout4(seed, ((uint64_t)t * p.Pmask + slot) * hv + c4, 1u, p.p_drop);     // the recurrent kernels' counters
-        const size_t row = (size_t)(uint32_t)p.rowidx[(int64_t)q * p.L + t];
-        if (BACKWARD) {
-            float *d = p.dZ + row * p.H + 4 * c4;
-            atomicAdd(d + 0, g.x * m.x); atomicAdd(d + 1, g.y * m.y); atomicAdd(d + 2, g.z * m.z); atomicAdd(d + 3, g.w * m.w);
-        } else {
-            const float4 v = reinterpret_cast<const float4 *>(p.Z)[row * hv + c4];
-            acc.x += v.x * m.x; acc.y += v.y * m.y; acc.z += v.z * m.z; acc.w += v.w * m.w;
-        }
-    }
-    if (!BACKWARD) {
-        acc.x *= p.scale; acc.y *= p.scale; acc.z *= p.scale; acc.w *= p.scale;
-        reinterpret_cast<float4 *>(p.hn)[i] = acc;
-    }
-}
-
-
-// ================================================================================================
-// Generic recurrence for hidden sizes the fused kernels do not cover (256 < H <= 1024, e.g. the reference's -hid=1024
-// runs, results/result_for_Nba.txt): step by step -- gather + dropout kernel, one fp32 MFMA GEMM for the gate
-// pre-activations, an element-wise cell kernel; backward the same way round plus one GEMM for the weight gradients.
-// Same tensors and layouts as the fused path (saved [P,L,SV,H], xh [P,L,2H], dG [P,L,GH]), same dropout counters, so
-// pooling, micro-batches, slices and the caller see no difference.  A functional path, ~10 launches per step.
-// ================================================================================================
-struct GenParams {
-    const float *Z;            // [N*L, H]
-    const int32_t *rowidx;     // [P, L]
-    const int32_t *slotof;     // [P]
-    float *xh;                 // [P, L, 2H]
-    float *pre;                // [P, L, GH]  forward: gate pre-activations of step t; backward: dG
-    float *saved;              // [P, L, SV, H] or null
-    float *state;              // [P, H] running cell / hidden state (forward), d c / the GRU's direct term (backward)
-    float *hn;                 // [P, H]
-    float *dh;                 // [P, H] backward: d loss / d h_t, updated in place
-    const float *gx;           // [P, 2H] backward: [dx_t | dh_{t-1}] of the step's GEMM
-    float *dZ;
-    const float *biasc;
-    int P, L, H, G, cell, t;
-    int64_t Pmask;
-    float p_drop;
-    uint64_t seed;
-    const pn_step_state *dyn;
-    const float *mask;
-};
-
-__device__ __forceinline__ float4 gen_mask(const GenParams &p, uint64_t seed, int t, int64_t slot, int c4) {
-    const int hv = p.H / 4;
-    if (p.mask) return reinterpret_cast<const float4 *>(p.mask)[((int64_t)t * p.Pmask + slot) * hv + c4];
-    if (p.p_drop > 0.0f) return dropout4(seed, ((uint64_t)t * p.Pmask + slot) * hv + c4, 1u, p.p_drop);
-    return make_float4(1.f, 1.f, 1.f, 1.f);
-}
-
-// xh[q, t, 0:H] = mask * Z[row(q, t)];  t = 0 also clears the h half
-__global__ __launch_bounds__(256) void gen_x_kernel(GenParams p) {
-    const int hv = p.H / 4;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)p.P * hv) return;
-    const int q = (int)(i / hv), c4 = (int)(i - (int64_t)q * hv);
-    const uint64_t seed = p.dyn ? p.dyn->seed : p.seed;
-    const float4 m = gen_mask(p, seed, p.t, p.slotof[q], c4);
-    const size_t row = (size_t)(uint32_t)p.rowidx[(int64_t)q * p.L + p.t];
-    float4 v = reinterpret_cast<const float4 *>(p.Z)[row * hv + c4];
-    v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
-    float4 *dst = reinterpret_cast<float4 *>(p.xh) + ((size_t)q * p.L + p.t) * (2 * hv) + c4;
-    dst[0] = v;
-    if (p.t == 0) dst[hv] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// one element (path q, hidden unit j) of the cell update of step t
-__global__ __launch_bounds__(256) void gen_cell_fwd_kernel(GenParams p) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)p.P * p.H) return;
-    const int H = p.H, q = (int)(i / H), j = (int)(i - (int64_t)q * H);
-    const float *pre = p.pre + ((size_t)q * p.L + p.t) * ((size_t)p.G * H) + j;
-    const int SV = p.G == 4 ? 5 : 1;
-    float *sv = p.saved ? p.saved + (((size_t)q * p.L + p.t) * SV) * H + j : nullptr;
-    float h;
-    if (p.cell == 3) {                     // GRU on the four slots r, z, nx, nh
-        const float rg = sigmoidf_(pre[0]), zg = sigmoidf_(pre[H]), nh = pre[3 * (size_t)H];
-        const float ng = tanhf_(pre[2 * (size_t)H] + rg * nh);
-        const float hp = p.t > 0 ? p.state[i] : 0.0f;
-        h = (1.0f - zg) * ng + zg * hp;
-        p.state[i] = h;
-        if (sv) { sv[0] = rg; sv[H] = zg; sv[2 * (size_t)H] = ng; sv[3 * (size_t)H] = nh; sv[4 * (size_t)H] = hp; }
-    } else if (p.G == 4) {                 // LSTM
-        const float ig = sigmoidf_(pre[0]), fg = sigmoidf_(pre[H]), gg = tanhf_(pre[2 * (size_t)H]), og = sigmoidf_(pre[3 * (size_t)H]);
-        const float c = fg * (p.t > 0 ? p.state[i] : 0.0f) + ig * gg;
-        p.state[i] = c;
-        h = og * tanhf_(c);
-        if (sv) { sv[0] = ig; sv[H] = fg; sv[2 * (size_t)H] = gg; sv[3 * (size_t)H] = og; sv[4 * (size_t)H] = c; }
-    } else {                                // tanh RNN
-        h = tanhf_(pre[0]);
-        if (sv) sv[0] = h;
-    }
-    if (p.t == p.L - 1)
-        p.hn[i] = h;
-    else
-        p.xh[((size_t)q * p.L + p.t + 1) * (2 * (size_t)H) + H + j] = h;
-}
-
-// cell backward of step t: dh (in place buffer) and the carried state -> the gate-slot gradients dG[q, t, :]
-__global__ __launch_bounds__(256) void gen_cell_bwd_kernel(GenParams p) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)p.P * p.H) return;
-    const int H = p.H, q = (int)(i / H), j = (int)(i - (int64_t)q * H);
-    const int SV = p.G == 4 ? 5 : 1;
-    const float *sv = p.saved + (((size_t)q * p.L + p.t) * SV) * H + j;
-    float *d = p.pre + ((size_t)q * p.L + p.t) * ((size_t)p.G * H) + j;
-    const float dhv = p.dh[i];
-    if (p.cell == 3) {
-        const float rg = sv[0], zg = sv[H], ng = sv[2 * (size_t)H], nh = sv[3 * (size_t)H], hp = sv[4 * (size_t)H];
-        const float dnp = dhv * (1.0f - zg) * (1.0f - ng * ng);
-        d[0] = dnp * nh * rg * (1.0f - rg);
-        d[H] = dhv * (hp - ng) * zg * (1.0f - zg);
-        d[2 * (size_t)H] = dnp;
-        d[3 * (size_t)H] = dnp * rg;
-        p.state[i] = dhv * zg;              // the direct path d h_t / d h_{t-1}
-    } else if (p.G == 4) {
-        const float ig = sv[0], fg = sv[H], gg = sv[2 * (size_t)H], og = sv[3 * (size_t)H], c = sv[4 * (size_t)H];
-        const float cprev = p.t > 0 ? sv[-(ptrdiff_t)H] : 0.0f;       // slot 4 of step t-1
-        const float tc = tanhf_(c);
-        const float dct = (p.t < p.L - 1 ? p.state[i] : 0.0f) + dhv * og * (1.0f - tc * tc);
-        d[0] = dct * gg * ig * (1.0f - ig);
-        d[H] = dct * cprev * fg * (1.0f - fg);
-        d[2 * (size_t)H] = dct * ig * (1.0f - gg * gg);
-        d[3 * (size_t)H] = dhv * tc * og * (1.0f - og);
-        p.state[i] = dct * fg;
-    } else {
-        const float h = sv[0];
-        d[0] = dhv * (1.0f - h * h);
-    }
-}
-
-// after the step's GEMM gx = dG_t . [W_ih | W_hh]: scatter mask * dx into dZ, dh_{t-1} into the dh buffer
-__global__ __launch_bounds__(256) void gen_scatter_kernel(GenParams p) {
-    const int hv = p.H / 4;
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)p.P * hv) return;
-    const int q = (int)(i / hv), c4 = (int)(i - (int64_t)q * hv);
-    const uint64_t seed = p.dyn ? p.dyn->seed : p.seed;
-    const float4 m = gen_mask(p, seed, p.t, p.slotof[q], c4);
-    const float4 *g = reinterpret_cast<const float4 *>(p.gx) + (size_t)q * (2 * hv) + c4;
-    const float4 dx = g[0];
-    const size_t row = (size_t)(uint32_t)p.rowidx[(int64_t)q * p.L + p.t];
-    float *dz = p.dZ + row * p.H + 4 * c4;
-    atomicAdd(dz + 0, dx.x * m.x); atomicAdd(dz + 1, dx.y * m.y); atomicAdd(dz + 2, dx.z * m.z); atomicAdd(dz + 3, dx.w * m.w);
-    if (p.t > 0) {
-        float4 dh = g[hv];
-        if (p.cell == 3) {
-            const float4 direct = reinterpret_cast<const float4 *>(p.state)[i];
-            dh.x += direct.x; dh.y += direct.y; dh.z += direct.z; dh.w += direct.w;
-        }
-        reinterpret_cast<float4 *>(p.dh)[i] = dh;
-    }
-}
-
-// Wcat [GH, 2H] = [W_ih | W_hh] in fp32 (GRU: the four slots with their zero halves) and its transpose, biasc as in
-// pack_fwd3_kernel
-__global__ void gen_pack_kernel(const float *__restrict__ w_ih, const float *__restrict__ w_hh,
-                                const float *__restrict__ b_ih, const float *__restrict__ b_hh, int H, int G, int gru,
-                                float *__restrict__ Wcat, float *__restrict__ WcatT, float *__restrict__ biasc) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (int64_t)G * H) {
-        if (!gru) {
-            biasc[i] = b_ih[i] + b_hh[i];
-        } else {
-            const int slot = (int)(i / H), j = (int)(i - (int64_t)slot * H), wr = gru_weight_row(slot, j, H);
-            biasc[i] = slot < 2 ? b_ih[wr] + b_hh[wr] : slot == 2 ? b_ih[wr] : b_hh[wr];
-        }
-    }
-    if (i >= (int64_t)G * H * 2 * H) return;
-    const int m = (int)(i / (2 * H)), k = (int)(i - (int64_t)m * 2 * H), slot = m / H, j = m - slot * H;
-    const int row = gru ? gru_weight_row(slot, j, H) : m;
-    float v = k < H ? w_ih[(int64_t)row * H + k] : w_hh[(int64_t)row * H + (k - H)];
-    if (gru && ((slot == 2 && k >= H) || (slot == 3 && k < H))) v = 0.0f;
-    Wcat[i] = v;
-    if (WcatT) WcatT[(int64_t)k * G * H + m] = v;      // [2H, GH]: the BPTT's GEMM wants its B operand K-contiguous too
-}
-
-// (SeqFwdParams: pn_seq.h)
-
-// ================================================================================================
-// pool_fwd_kernel: one workgroup (4 waves) per pooling group (= output node).
-// ================================================================================================
-struct PoolParams {
-    int variant, S, W, H, C, N;      // N: rows of Xh (sel is clamped to it, like ids in plan_kernel)
-    int64_t goff;           // position of local group 0 in the whole batch (dropout counters / explicit mask rows)
-    const float *hn;        // [P, H] in slot' order
-    const float *ego_tab;   // Z (HOMO) or Xh (HETERO)
-    const int32_t *egoidx;  // [P] row of ego_tab
-    const float *Xh;        // [N, H]
-    const int32_t *sel;     // [S]
-    const float *att_w, *att_b, *fc2_w, *fc2_b;
-    float p_drop;
-    uint64_t seed;
-    const pn_step_state *dyn;
-    const float *mask;      // [S, 2H] or null
-    float *coef;            // [P] pooling coefficient per slot' (1+att | softmax | 1)
-    float *rawsc;           // [P] raw attention score (pre LeakyReLU) per slot'
-    float *layer1;          // [S, 2H] classifier input after dropout
-    float *out;             // [S, C]
-    // optional outputs (pn_pagg_args.out_*), rows of this launch's groups; null: not written (kernel arguments: the tests
-    // below are uniform over the grid -- the pooling steps, which never set them, run the same code as before)
-    float *embed;           // [S, 2H] classifier input before the dropout
-    float *path_weight;     // [S, W]  coef in member order
-    float *path_state;      // [S, W, H] hn in member order
-};
-
-__device__ __forceinline__ void pool_fwd_body(const PoolParams &p, float *lds) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int g = blockIdx.x, H = p.H, W = p.W;
-    float *sc = lds;                                            // [W] scores, then coefficients
-    int *s_erow = reinterpret_cast<int *>(sc + W);              // [W] ego rows of the group's members
-    float *part4 = reinterpret_cast<float *>(s_erow + W);       // [4][H] the waves' partial pooled sums
-    float *l1s = part4 + 4 * H;                                 // [2H] classifier input
-    const float inv_w = 1.0f / (float)W;
-
-    if (p.variant != PN_VARIANT_PAGG) {
-        // the ego rows, fetched up front: the score loop then has no index -> row dependent load pair
-        for (int mem = tid; mem < W; mem += 256) s_erow[mem] = p.egoidx[(int64_t)g * W + mem];
-        __syncthreads();
-        // attention scores, 8 members per wave at a time: lane = (member lane>>3, eighth of H lane&7); the eight partial
-        // dot products of a member are summed with three xor-shuffles
-        const float ab = p.att_b[0];
-        const int m8 = lane >> 3, part = lane & 7, jw = H / 8;
-        for (int m0 = 8 * wave; m0 < W; m0 += 32) {
-            const int mem = m0 + m8;
-            const int memc = min(mem, W - 1);
-            const int64_t s = (int64_t)g * W + memc;
-            const float4 *h4 = reinterpret_cast<const float4 *>(p.hn + s * H + part * jw);
-            const float4 *e4 = reinterpret_cast<const float4 *>(p.ego_tab + (int64_t)s_erow[memc] * H + part * jw);
-            const float4 *a4 = reinterpret_cast<const float4 *>(p.att_w + part * jw);
-            const float4 *b4 = reinterpret_cast<const float4 *>(p.att_w + H + part * jw);
-            float acc = 0.0f;
-            for (int j = 0; j < jw / 4; j++) {
-                const float4 hv = h4[j], ev = e4[j], av = a4[j], bv = b4[j];
-                acc += hv.x * av.x + hv.y * av.y + hv.z * av.z + hv.w * av.w;
-                acc += ev.x * bv.x + ev.y * bv.y + ev.z * bv.z + ev.w * bv.w;
-            }
-            acc += __shfl_xor(acc, 1, 64);
-            acc += __shfl_xor(acc, 2, 64);
-            acc += __shfl_xor(acc, 4, 64);
-            if (part == 0 && mem < W) {
-                sc[mem] = acc + ab;
-                p.rawsc[(int64_t)g * W + mem] = acc + ab;
-            }
-        }
-        __syncthreads();
-    }
-    if (p.variant == PN_VARIANT_HETERO) {
-        // softmax over the W members of LeakyReLU(score) (F.softmax implicit dim 0 of [W,S,1]); every wave reduces
-        // all W scores (same order, same result), then each thread rewrites its own entries
-        float mx = -3.4e38f;
-        for (int mem = lane; mem < W; mem += 64) {
-            float v = sc[mem];
-            v = v > 0.0f ? v : 0.01f * v;
-            mx = fmaxf(mx, v);
-        }
-        mx = wave_max(mx);
-        float sum = 0.0f;
-        for (int mem = lane; mem < W; mem += 64) {
-            float v = sc[mem];
-            v = v > 0.0f ? v : 0.01f * v;
-            sum += expf(v - mx);
-        }
-        sum = wave_sum(sum);
-        __syncthreads();
-        for (int mem = tid; mem < W; mem += 256) {
-            float v = sc[mem];
-            v = v > 0.0f ? v : 0.01f * v;
-            sc[mem] = expf(v - mx) / sum;
-        }
-    } else if (p.variant == PN_VARIANT_HOMO) {
-        for (int mem = tid; mem < W; mem += 256) sc[mem] = 1.0f + sc[mem];
-    } else {
-        for (int mem = tid; mem < W; mem += 256) sc[mem] = 1.0f;
-    }
-    __syncthreads();
-    for (int mem = tid; mem < W; mem += 256) p.coef[(int64_t)g * W + mem] = sc[mem];
-    if (p.path_weight)
-        for (int mem = tid; mem < W; mem += 256) p.path_weight[(int64_t)g * W + mem] = sc[mem];
-    if (p.path_state) {     // the group's W rows of hn are already in member order: one contiguous copy (H % 32 == 0)
-        const float4 *src = reinterpret_cast<const float4 *>(p.hn + (int64_t)g * W * H);
-        float4 *dst = reinterpret_cast<float4 *>(p.path_state + (int64_t)g * W * H);
-        for (int i = tid; i < W * H / 4; i += 256) dst[i] = src[i];
-    }
-
-    // pooled = mean_w coef_w * h_w: each wave sums its quarter of the members, the quarters meet in LDS (fixed order)
-    {
-        const int per = (W + 3) / 4, mem_end = min(W, (wave + 1) * per);
-        for (int j = lane; j < H; j += 64) {
-            float acc = 0.0f;
-#pragma unroll 8
-            for (int mem = wave * per; mem < mem_end; mem++) acc += sc[mem] * p.hn[((int64_t)g * W + mem) * H + j];
-            part4[wave * H + j] = acc;
-        }
-    }
-    __syncthreads();
-    // layer1 = dropout([Xh[sel[g]] ; pooled])
-    float *l1 = p.layer1 + (int64_t)g * 2 * H;
-    const float *ego = p.Xh + (int64_t)min(max(p.sel[g], 0), p.N - 1) * H;
-    for (int j = tid; j < H; j += 256) {
-        float a = ego[j], b = (part4[j] + part4[H + j] + part4[2 * H + j] + part4[3 * H + j]) * inv_w;
-        if (p.embed) {
-            p.embed[(int64_t)g * 2 * H + j] = a;
-            p.embed[(int64_t)g * 2 * H + H + j] = b;
-        }
-        const uint64_t gg = (uint64_t)(p.goff + g);
-        if (p.mask) {
-            a *= p.mask[gg * 2 * H + j];
-            b *= p.mask[gg * 2 * H + H + j];
-        } else if (p.p_drop > 0.0f) {
-            const uint64_t seed = p.dyn ? p.dyn->seed : p.seed;
-            const float4 m0 = dropout4(seed, (gg * 2 * H + j) >> 2, 2u, p.p_drop);
-            const float4 m1 = dropout4(seed, (gg * 2 * H + H + j) >> 2, 2u, p.p_drop);
-            const int e0 = j & 3;
-            a *= e0 == 0 ? m0.x : e0 == 1 ? m0.y : e0 == 2 ? m0.z : m0.w;
-            b *= e0 == 0 ? m1.x : e0 == 1 ? m1.y : e0 == 2 ? m1.z : m1.w;
-        }
-        l1[j] = a;
-        l1[H + j] = b;
-        l1s[j] = a;
-        l1s[H + j] = b;
-    }
-    __syncthreads();
-    for (int c = wave; c < p.C; c += 4) {
-        float part = 0.0f;
-        for (int j = lane; j < 2 * H; j += 64) part += l1s[j] * p.fc2_w[(int64_t)c * 2 * H + j];
-        part = wave_sum(part);
-        if (lane == 0) p.out[(int64_t)g * p.C + c] = part + p.fc2_b[c];
-    }
-}
-__global__ __launch_bounds__(256) void pool_fwd_kernel(PoolParams p) {
-    extern __shared__ float lds[];
-    pool_fwd_body(p, lds);
-}
-
-
-// ================================================================================================
-// BACKWARD
-// ================================================================================================
-// ---- pooling / attention / classifier backward: the parameters of pool_bwd_wg_kernel and of the pooling step ------------
-struct PoolBwdParams {
-    int variant, S, W, H, C, N;
-    int64_t goff;
-    const float *hn, *ego_tab;
-    const int32_t *egoidx, *sel;
-    const float *att_w, *fc2_w, *g_out, *coef, *rawsc;
-    float p_drop;
-    uint64_t seed;
-    const pn_step_state *dyn;
-    const float *mask;
-    float *dhn;        // [P, H]
-    float *dXh;        // [N, H]  (+= ego of the classifier input; HETERO: += attention ego)
-    float *dego;       // table the attention-ego gradient goes to: dZ (HOMO) or dXh (HETERO)
-    float *g_att_w, *g_att_b;
-    // instead of atomics the kernel stores the attention-weight terms per workgroup (always) and, in deterministic mode
-    // (else null), the ego half of d layer1 per group and d score per path; det_att_reduce_kernel / det_scatter_kernel add
-    float *det_sel;    // [S, H]
-    float *det_ds;     // [P]
-    float *det_att;    // [workgroups][2H + 4]
-    // pn_pagg_args.g_embed: d loss / d (classifier input before the dropout) [S, 2H] of this launch's groups, or null.  g_out
-    // may be null when it is set (the classifier's term is then absent)
-    const float *g_embed;
-};
-
-// A workgroup per group: the W members of a group split over the four waves.  (A wavefront per group ran its ~50 dependent
-// memory round trips alone on its SIMD -- 1 299 waves on 1 024 SIMDs at the headline shape; four times the waves hide them:
-// 0.052 -> 0.031 ms.  Round 2 had rejected this layout for quadrupling the atomics on the 2H + 1 attention-weight
-// addresses; those go through per-workgroup partials, det_att: [groups][2H + 4].)
-// HI: 64-column chunks of H a lane walks (4 covers H <= 256, the fused kernels' range; 16 covers the generic path's H <= 1024)
-template <int HI>
-__device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *lds) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int H = p.H, W = p.W;
-    float *dco = lds;                        // [W] d coef
-    float *dsc = dco + W;                    // [W] d score
-    float *dp = dsc + W;                     // [H] d pooled / W
-    float *red = dp + H;                     // [4][2H] per-wave attention-weight partials; before that [4][H] ego partials
-    int *s_erow = reinterpret_cast<int *>(red + 8 * H);    // [W] ego rows of the group
-    float *s_coef = reinterpret_cast<float *>(s_erow + W);  // [W]
-    float *s_tot = s_coef + W;               // [4] hetero: partial sums of coef * d coef
-    const int g = blockIdx.x;
-    const float inv_w = 1.0f / (float)W;
-    for (int mem = tid; mem < W; mem += 256) {
-        const int64_t s = (int64_t)g * W + mem;
-        s_erow[mem] = p.variant == PN_VARIANT_PAGG ? 0 : p.egoidx[s];
-        s_coef[mem] = p.coef[s];
-    }
-    for (int j = tid; j < H; j += 256) {
-        float a = 0.0f, b = 0.0f;
-        if (p.g_out)
-            for (int c = 0; c < p.C; c++) {
-                const float go = p.g_out[(int64_t)g * p.C + c];
-                a += go * p.fc2_w[(int64_t)c * 2 * H + j];
-                b += go * p.fc2_w[(int64_t)c * 2 * H + H + j];
-            }
-        const uint64_t gg = (uint64_t)(p.goff + g);
-        if (p.mask) {
-            a *= p.mask[gg * 2 * H + j];
-            b *= p.mask[gg * 2 * H + H + j];
-        } else if (p.p_drop > 0.0f) {
-            const uint64_t seed = p.dyn ? p.dyn->seed : p.seed;
-            a *= dropout1(seed, gg * 2 * H + j, 2u, p.p_drop);
-            b *= dropout1(seed, gg * 2 * H + H + j, 2u, p.p_drop);
-        }
-        if (p.g_embed) {    // the embedding is read before the dropout: its gradient joins behind the mask
-            a += p.g_embed[(int64_t)g * 2 * H + j];
-            b += p.g_embed[(int64_t)g * 2 * H + H + j];
-        }
-        if (p.det_sel)
-            p.det_sel[(int64_t)g * H + j] = a;
-        else
-            atomicAdd(&p.dXh[(int64_t)min(max(p.sel[g], 0), p.N - 1) * H + j], a);
-        dp[j] = b * inv_w;
-    }
-    __syncthreads();
-    {       // d coef[mem] = hn[mem] . d pooled / W: eight lanes per member, 32 members per pass
-        const int m32 = tid >> 3, part = tid & 7, jw = H / 8;
-        for (int m0 = 0; m0 < W; m0 += 32) {
-            const int mem = m0 + m32;
-            const float4 *h4 = reinterpret_cast<const float4 *>(p.hn + ((int64_t)g * W + min(mem, W - 1)) * H + part * jw);
-            float acc = 0.0f;
-            for (int j = 0; j < jw / 4; j++) {
-                const float4 hv = h4[j];
-                const float *d = dp + part * jw + 4 * j;
-                acc += hv.x * d[0] + hv.y * d[1] + hv.z * d[2] + hv.w * d[3];
-            }
-            acc += __shfl_xor(acc, 1, 64);
-            acc += __shfl_xor(acc, 2, 64);
-            acc += __shfl_xor(acc, 4, 64);
-            if (part == 0 && mem < W) dco[mem] = acc;
-        }
-    }
-    __syncthreads();
-    if (p.variant == PN_VARIANT_HETERO) {
-        float tot = 0.0f;
-        for (int mem = tid; mem < W; mem += 256) tot += s_coef[mem] * dco[mem];
-        tot = wave_sum(tot);
-        if (lane == 0) s_tot[wave] = tot;
-        __syncthreads();
-        tot = (s_tot[0] + s_tot[1]) + (s_tot[2] + s_tot[3]);
-        for (int mem = tid; mem < W; mem += 256) {
-            const int64_t s = (int64_t)g * W + mem;
-            dsc[mem] = s_coef[mem] * (dco[mem] - tot) * (p.rawsc[s] > 0.0f ? 1.0f : 0.01f);
-        }
-    } else {
-        for (int mem = tid; mem < W; mem += 256) dsc[mem] = p.variant == PN_VARIANT_HOMO ? dco[mem] : 0.0f;
-    }
-    __syncthreads();
-    // per member: d h_n, the attention-weight terms and the attention-ego term; wave w takes members w, w + 4, ...
-    float gaw_h[HI], gaw_e[HI], ego_acc[HI], gab = 0.0f;
-#pragma unroll
-    for (int i = 0; i < HI; i++) gaw_h[i] = gaw_e[i] = ego_acc[i] = 0.0f;
-    const bool has_att = p.variant != PN_VARIANT_PAGG;
-    // the members' ego rows: usually one row for the whole group (HOMO: all W paths of a node start at the node) -- then the
-    // waves' sums meet in LDS and the group flushes once; otherwise (HETERO, or paths that start elsewhere) a row per
-    // member, flushed as it comes
-    int same = 1;
-    for (int mem = tid; mem < W; mem += 256) same &= s_erow[mem] == s_erow[0];
-    const bool one_row = __syncthreads_and(same) != 0;
-#pragma unroll 2
-    for (int mem = wave; mem < W; mem += 4) {
-        const int64_t s = (int64_t)g * W + mem;
-        const float ds = dsc[mem], cf = s_coef[mem];
-        const int64_t erow = (int64_t)s_erow[mem] * H;
-#pragma unroll
-        for (int i = 0; i < HI; i++) {
-            const int j = lane + 64 * i;
-            if (j < H) {
-                float dh = cf * dp[j];
-                if (has_att) {
-                    dh += ds * p.att_w[j];
-                    gaw_h[i] += ds * p.hn[s * H + j];
-                    gaw_e[i] += ds * p.ego_tab[erow + j];
-                    const float eg = ds * p.att_w[H + j];
-                    if (one_row)
-                        ego_acc[i] += eg;
-                    else if (!p.det_ds)
-                        atomicAdd(&p.dego[erow + j], eg);
-                }
-                p.dhn[s * H + j] = dh;
-            }
-        }
-        gab += ds;
-        if (p.det_ds && lane == 0) p.det_ds[s] = ds;
-    }
-    if (!has_att) return;       // block-uniform
-    if (one_row && !p.det_ds) {
-#pragma unroll
-        for (int i = 0; i < HI; i++) {
-            const int j = lane + 64 * i;
-            if (j < H) red[wave * H + j] = ego_acc[i];
-        }
-        __syncthreads();
-        const int64_t erow = (int64_t)s_erow[0] * H;
-        for (int j = tid; j < H; j += 256)
-            atomicAdd(&p.dego[erow + j], (red[j] + red[H + j]) + (red[2 * H + j] + red[3 * H + j]));
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < HI; i++) {
-        const int j = lane + 64 * i;
-        if (j < H) {
-            red[wave * 2 * H + j] = gaw_h[i];
-            red[wave * 2 * H + H + j] = gaw_e[i];
-        }
-    }
-    __syncthreads();
-    float *out = p.det_att + (int64_t)blockIdx.x * (2 * H + 4);
-    for (int j = tid; j < 2 * H; j += 256) out[j] = red[j] + red[2 * H + j] + red[4 * H + j] + red[6 * H + j];
-    if (lane == 0) out[2 * H + wave] = gab;
-}
-template <int HI>
-__global__ __launch_bounds__(256) void pool_bwd_wg_kernel(PoolBwdParams p) {
-    extern __shared__ float lds[];
-    pool_bwd_wg_body<HI>(p, lds);
-}
-
-// ---- pooling forward, loss and pooling backward of a group in ONE launch (pn_pagg_train_step, default mode) -----------------
-// Between the recurrence and the BPTT a training step has, per masked node and independent of every other node: attention +
-// pooling + classifier (pool_fwd_kernel), softmax cross entropy of its C logits (cross_entropy_kernel) and the pooling /
-// attention backward (pool_bwd_wg_kernel) -- three dependent launches of ~20 us each for work that touches 40 KB per node.
-// One workgroup per node runs the three bodies back to back: the node's h_n and ego rows are re-read from the CU's own
-// caches, the logits and their gradient never leave the workgroup's sight.  The same code as the three kernels (the
-// bodies ARE those kernels'), so logits, g_out, d h_n and every gradient term are bit-identical to the three launches;
-// the loss is the fixed-order sum of the per-node terms (loss_sum_kernel, off the critical path).
-// Replaces /root/reference/PathNet_run.py:196-210 / :266-277 (forward), :346 (loss) and autograd's backward of both.
-struct PoolStepParams {
-    PoolParams f;
-    PoolBwdParams b;
-    const int64_t *target;  // [S] class of each group
-    float scale;            // d loss / d (row loss): grad_scale / rows of the whole batch
-    float *gout;            // [S, C] d loss / d logits (read by the classifier's weight-gradient GEMM)
-    float *lossg;           // [S] logsumexp - logit[target] per group
-};
-template <int HI>
-__global__ __launch_bounds__(256) void pool_step_kernel(PoolStepParams p) {
-    extern __shared__ float lds[];
-    pool_fwd_body(p.f, lds);
-    __syncthreads();            // (workgroup-scope fence: out[g, :] written above is visible below; LDS is free again)
-    if (threadIdx.x == 0) {     // the row's cross entropy exactly as cross_entropy_kernel computes it
-        const int g = blockIdx.x, classes = p.f.C;
-        const float *x = p.f.out + (int64_t)g * classes;
-        float m = x[0];
-        for (int c = 1; c < classes; c++) m = fmaxf(m, x[c]);
-        float sum = 0.0f;
-        for (int c = 0; c < classes; c++) sum += expf(x[c] - m);
-        const float ls = logf(sum);
-        const int64_t t64 = p.target[g];        // out of range: NaN loss, zero gradient row, no address formed from it
-        const bool ok = t64 >= 0 && t64 < (int64_t)classes;
-        const int t = ok ? (int)t64 : 0;
-        const float row = ls - (x[t] - m);
-        p.lossg[g] = ok ? row : NAN;
-        float *go = p.gout + (int64_t)g * classes;
-        for (int c = 0; c < classes; c++) {
-            const float gv = (expf((x[c] - m) - ls) - (c == t ? 1.0f : 0.0f)) * p.scale;
-            go[c] = ok ? gv : 0.0f;
-        }
-    }
-    __syncthreads();
-    pool_bwd_wg_body<HI>(p.b, lds);
-}
-// ---- the step with pn_loss_spec's options (pn_pagg_train_step_loss): the row is pn_loss.h's, as cross_entropy_opts_kernel
-// walks it; k = grad_scale / D comes from D in device memory.  A kernel of its own: pool_step_kernel is as it was.
-struct PoolStepLossParams {
-    PoolStepParams s;       // (s.scale is not read: the options carry grad_scale)
-    LossOpts o;
-};
-template <int HI>
-__global__ __launch_bounds__(256) void pool_step_loss_kernel(PoolStepLossParams q) {
-    extern __shared__ float lds[];
-    const PoolStepParams &p = q.s;
-    pool_fwd_body(p.f, lds);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int g = blockIdx.x, classes = p.f.C;
-        float k_grad, k_loss;
-        loss_factors(q.o, k_grad, k_loss);
-        p.lossg[g] = ce_row_opts(p.f.out + (int64_t)g * classes, classes, p.target[g], q.o, k_grad, p.gout + (int64_t)g * classes);
-    }
-    __syncthreads();
-    pool_bwd_wg_body<HI>(p.b, lds);
-}
-// ---- the same step with the node's rows held in REGISTERS (round 6).  pool_step_kernel's bodies change the thread layout from
-// phase to phase (eight lanes per member for the dot products, a lane per column for the sums) and therefore read the node's
-// W x H final hidden states four times from memory, behind one another: ~15 dependent round trips per node, 47 us for 1 299
-// nodes and 0.27 / 1.3 ms at Pubmed / BGP size, where the launch is bound by that cache traffic.  Here wave w owns members
-// w, w + 4, ... (MM of them) and a lane columns lane + 64 i (HI of them) throughout: the rows are loaded ONCE, all at once
-// (MM x HI registers), dot products over H are wave sums, sums over W are lane-local plus one exchange through LDS -- five
-// round trips and eight barriers per node.  Same arithmetic, other summation orders than the three kernels (which the
-// deterministic mode keeps: pn_pagg_train_step's bitwise tests run there); W <= 4 MM, H <= 64 HI.
-#ifdef PN_POOL_TRACE
-__device__ long long g_pool_trace[2048 * 12];
-#define PTRACE(n) do { if (threadIdx.x == 0 && blockIdx.x < 2048) g_pool_trace[blockIdx.x * 12 + (n)] = wall_clock64(); } while (0)
-#else
-#define PTRACE(n) do { } while (0)
-#endif
-// (the kernel's text: pn_pool_step2.inc, once as pool_step2_kernel, once with the loss options as pool_step2_loss_kernel)
-#include "pn_pool_step2.inc"
-#define PN_STEP2_LOSS_OPTS
-#include "pn_pool_step2.inc"
-#undef PN_STEP2_LOSS_OPTS
-inline size_t pool_step2_lds_bytes(int MM, int H, int C) { return (size_t)(12 * MM + 8 * H + 2 * H + H + 2 * C + 8) * sizeof(float); }
-
-// loss[0] (+)= scale * sum of the rows' terms, in cross_entropy_kernel's order (one workgroup of 1024 threads)
-__global__ __launch_bounds__(1024) void loss_sum_kernel(const float *__restrict__ lossg, int rows, float scale,
-                                                        float *__restrict__ loss, int store) {
-    __shared__ float part[16];
-    float mine = 0.0f;
-    for (int r = threadIdx.x; r < rows; r += 1024) mine += lossg[r];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.0f;
-        for (int w = 0; w < 16; w++) t += part[w];
-        if (store)
-            *loss = t * scale;
-        else
-            atomicAdd(loss, t * scale);
-    }
-}
-
-// the same with the options' k = grad_scale / D (mean) or grad_scale (sum), formed here from D in device memory
-__global__ __launch_bounds__(1024) void loss_sum_opts_kernel(const float *__restrict__ lossg, int rows, LossOpts o,
-                                                             float *__restrict__ loss, int store) {
-    __shared__ float part[16];
-    float mine = 0.0f;
-    for (int r = threadIdx.x; r < rows; r += 1024) mine += lossg[r];
-#pragma unroll
-    for (int of = 32; of > 0; of >>= 1) mine += __shfl_xor(mine, of, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float k_grad, k_loss;
-        loss_factors(o, k_grad, k_loss);
-        float t = 0.0f;
-        for (int w = 0; w < 16; w++) t += part[w];
-        if (store)
-            *loss = t * k_loss;
-        else
-            atomicAdd(loss, t * k_loss);
-    }
-}
-
-// ================================================================================================
-// Deterministic scatter-add (pn_pagg_shape.deterministic): dst[key[i]] += contribution i, added in the order of i.
-// The default backward scatters with fp32 atomics, whose order -- and with it the last bits of every gradient -- changes
-// from run to run (the reference inherits the same from torch's index_add / embedding backward).
-// Here the (key, i) pairs are sorted by key (stable radix sort, pn_sort.hip), the sorted array is cut into chunks of
-// DET_CHUNK positions, and one group of H/4 lanes walks a chunk in order:
-//   pass 1  a run of equal keys that lies inside the chunk is added to dst by its one owner; a run that crosses a chunk
-//           boundary leaves its piece in cpart[chunk][lead | trail];
-//   pass 2  the chunk holding the head of a crossing run adds the pieces up in chunk order and adds the sum to dst.
-// Every dst row has exactly one writer per pass and a fixed order of additions: bitwise reproducible.
-// A contribution is a row of `rows` ([K, H]) or scal[i] * vec[0..H) (the attention-ego term of the pooling backward).
-// The BPTT kernels need no second version for this: in deterministic mode they are handed the identity as their row
-// index and the zero-filled contribution buffer as their table -- every atomic then lands on an address of its own,
-// i.e. is a store -- and the scatter proper happens here.
-// ================================================================================================
-constexpr int DET_CHUNK = 32;
-struct DetScatterParams {
-    const int32_t *skey, *ssrc;     // sorted keys (with the scatter's segment number above `kmask`); the unsorted position of every one
-    int32_t kmask;
-    int64_t K, chunk0;              // positions; first chunk of this scatter's region of cpart
-    const float *rows;              // [K, H] or null
-    const float *scal, *vec;        // [K], [H]
-    float *dst;                     // [., H]
-    float *cpart;                   // [chunks][2][H]
-    int H;
-};
-
-struct DetScatterPair {          // blockIdx.y picks the scatter: the pooling backward's two run in one launch
-    DetScatterParams s[2];
-};
-
-template <int PASS>
-__global__ __launch_bounds__(256) void det_scatter_kernel(DetScatterPair pp) {
-    const DetScatterParams &p = pp.s[blockIdx.y];
-    const int hv = p.H / 4, gpb = 256 / hv;
-    const int grp = threadIdx.x / hv, ln = threadIdx.x - grp * hv;
-    if (grp >= gpb) return;
-    const int64_t c = (int64_t)blockIdx.x * gpb + grp, b = c * DET_CHUNK;
-    if (b >= p.K) return;
-    const int64_t e = min(p.K, b + (int64_t)DET_CHUNK);
-    float4 *dst = reinterpret_cast<float4 *>(p.dst);
-    float4 *cpart = reinterpret_cast<float4 *>(p.cpart) + p.chunk0 * 2 * hv;
-    const int32_t km = p.kmask;
-    auto add_to = [&](float4 *d, const float4 &a) {
-        float4 v = *d;
-        v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-        *d = v;
-    };
-    if (PASS == 1) {
-        const float4 vec = p.rows ? make_float4(0.f, 0.f, 0.f, 0.f) : reinterpret_cast<const float4 *>(p.vec)[ln];
-        int key = p.skey[b] & km;
-        bool lead = b > 0 && (p.skey[b - 1] & km) == key;      // the chunk opens inside a run
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        // four positions per trip: their contributions are requested together (the walk was one dependent 512-byte row load
-        // per position -- latency, 85 us for the 208 k rows of the headline shape) and added in the order of the positions
-        constexpr int DU = 4;
-        for (int64_t i0 = b; i0 < e; i0 += DU) {
-            int kk[DU];
-            float4 vv[DU];
-#pragma unroll
-            for (int j = 0; j < DU; j++) {
-                const int64_t i = min(i0 + j, e - 1);   // (past the end: a harmless re-load of the last position)
-                kk[j] = p.skey[i] & km;
-                const int64_t src = p.ssrc[i];
-                if (p.rows) {
-                    vv[j] = reinterpret_cast<const float4 *>(p.rows)[src * hv + ln];
-                } else {
-                    const float sc = p.scal[src];
-                    vv[j] = make_float4(sc * vec.x, sc * vec.y, sc * vec.z, sc * vec.w);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < DU; j++) {
-                if (i0 + j >= e) break;
-                const int k = kk[j];
-                if (k != key) {                          // the run of `key` ends inside the chunk
-                    if (lead)
-                        cpart[(c * 2 + 0) * hv + ln] = acc;
-                    else
-                        add_to(dst + (int64_t)key * hv + ln, acc);
-                    lead = false;
-                    key = k;
-                    acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-                acc.x += vv[j].x; acc.y += vv[j].y; acc.z += vv[j].z; acc.w += vv[j].w;
-            }
-        }
-        const bool cont = e < p.K && (p.skey[e] & km) == key;   // the last run goes on in the next chunk
-        if (lead)
-            cpart[(c * 2 + 0) * hv + ln] = acc;
-        else if (cont)
-            cpart[(c * 2 + 1) * hv + ln] = acc;
-        else
-            add_to(dst + (int64_t)key * hv + ln, acc);
-    } else {
-        const int key = p.skey[e - 1] & km;
-        if (!(e < p.K && (p.skey[e] & km) == key)) return;                      // nothing crosses this chunk's end
-        if ((p.skey[b] & km) == key && b > 0 && (p.skey[b - 1] & km) == key) return;   // a middle chunk of the run: its head's chunk adds
-        float4 acc = cpart[(c * 2 + 1) * hv + ln];
-        for (int64_t c2 = c + 1;; c2++) {
-            const int64_t e2 = min(p.K, (c2 + 1) * (int64_t)DET_CHUNK);
-            const float4 v = cpart[(c2 * 2 + 0) * hv + ln];
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-            if ((p.skey[e2 - 1] & km) != key || !(e2 < p.K && (p.skey[e2] & km) == key)) break;
-        }
-        add_to(dst + (int64_t)key * hv + ln, acc);
-    }
-}
-
-// keys of a scatter, clamped to [0, hi], beside the identity permutation the sort carries along
-struct DetKeys3 {
-    const int32_t *keys[3];
-    int64_t n[3];
-    int32_t hi[3];
-    int shift;
-};
-__global__ __launch_bounds__(256) void det_keys3_kernel(DetKeys3 q, int32_t *__restrict__ keys, int32_t *__restrict__ pos) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t at = i;
-    int seg = 0;
-    while (seg < 3 && i >= q.n[seg]) i -= q.n[seg], seg++;
-    if (seg >= 3) return;
-    keys[at] = min(max(q.keys[seg][i], 0), q.hi[seg]) | (seg << q.shift);
-    pos[at] = (int32_t)i;
-}
-
-__global__ __launch_bounds__(256) void det_iota_kernel(int32_t *__restrict__ iota, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) iota[i] = (int32_t)i;
-}
-
-// the pooling backward's per-workgroup attention terms ([nblk][2H + 4]: g_att_w partials, then one g_att_b term per
-// wave) added up in a fixed order.  A workgroup owns 64 consecutive outputs: sixteen row groups of 64 lanes walk the
-// partials' rows 16 apart -- every load a 256-byte run of one row -- and meet in LDS (round 6; a workgroup per output read
-// the [nblk][260] array column-wise, one cache line per element: 19 us for 1.3 MB at the headline shape)
-__global__ __launch_bounds__(1024) void det_att_reduce_kernel(const float *__restrict__ part, int nblk, int H,
-                                                              float *__restrict__ g_att_w, float *__restrict__ g_att_b) {
-    __shared__ float red[16][64];
-    const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6, stride = 2 * H + 4;
-    const int col = blockIdx.x * 64 + lane;
-    float v = 0.0f;
-    if (col < stride) {
-        const float *src = part + col;
-#pragma unroll 8
-        for (int b = rg; b < nblk; b += 16) v += src[(int64_t)b * stride];
-    }
-    red[rg][lane] = v;
-    __syncthreads();
-    if (rg != 0) return;
-    float t = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; r++) t += red[r][lane];
-    if (col < 2 * H) {
-        g_att_w[col] += t;
-    } else if (col < stride) {      // the four per-wave bias terms sit in one workgroup (4 | 2H): lanes c .. c + 3
-        red[0][lane] = t;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (col == 2 * H) *g_att_b += (red[0][lane] + red[0][lane + 1]) + (red[0][lane + 2] + red[0][lane + 3]);
-    }
-}
-
-// out [R][F4] = in [R][F] with zeros in columns F .. F4 - 1 (F4 = F rounded up to 4): 16-byte stores, dword loads
-__global__ __launch_bounds__(256) void pad_rows_kernel(const float *__restrict__ in, int64_t R, int F, int F4, float *__restrict__ out) {
-    const int q4 = F4 / 4;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= R * q4) return;
-    const int64_t r = i / q4;
-    const int c = (int)(i - r * q4) * 4;
-    const float *src = in + r * F + c;
-    float4 v;
-    v.x = src[0];                       // (c < F always)
-    v.y = c + 1 < F ? src[1] : 0.0f;
-    v.z = c + 2 < F ? src[2] : 0.0f;
-    v.w = c + 3 < F ? src[3] : 0.0f;
-    reinterpret_cast<float4 *>(out)[i] = v;
-}
-
-// zero-fill of up to 12 buffers in one launch (the accumulated gradients of a backward; ZeroList / ZeroFill: pn_internal.h)
-__global__ __launch_bounds__(256) void zero_kernel(ZeroList z) {
-    for (int b = 0; b < z.n; b++) {
-        float *p = z.ptr[b];
-        const unsigned long long cnt = z.count[b];
-        // 16-byte stores on the aligned body, scalars on the ragged ends
-        const unsigned long long head = min(cnt, (unsigned long long)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) / 4);
-        const unsigned long long body4 = (cnt - head) / 4;
-        float4 *p4 = reinterpret_cast<float4 *>(p + head);
-        for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < body4;
-             i += (unsigned long long)gridDim.x * blockDim.x)
-            p4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (blockIdx.x == 0) {
-            for (unsigned long long i = threadIdx.x; i < head; i += blockDim.x) p[i] = 0.0f;
-            for (unsigned long long i = head + body4 * 4 + threadIdx.x; i < cnt; i += blockDim.x) p[i] = 0.0f;
-        }
-    }
-}
 
 // ================================================================================================
 // shape bookkeeping and workspace layout
@@ -1136,10 +88,13 @@ int make_dims(const pn_pagg_shape &s, Dims &d) {
         PN_FAIL(PN_ERR_ARG, "hidden size %d not supported (multiples of 32 up to 1024; fused kernels up to 256)", s.H);
     if (s.N < 1 || s.F < 1 || s.C < 1 || s.S < 0 || s.W < 1 || s.L < 1 || s.L > 64)
         PN_FAIL(PN_ERR_ARG, "bad aggregator shape N=%d F=%d C=%d S=%d W=%d L=%d", s.N, s.F, s.C, s.S, s.W, s.L);
-    // the pooling kernels keep per-walk scores, coefficients, ego rows and a few rows of H floats in LDS
-    if (64 * (int64_t)s.W + 48 * s.H > 64 * 1024)
+    // the pooling kernels keep per-walk scores, coefficients, ego rows and a few rows of H floats in LDS (pool_lds_bytes, pn_pool.hip:
+    // linear in W, which gives the largest W the message names)
+    if (pool_lds_bytes(s.W, s.H) > 64 * 1024) {
+        const size_t at0 = pool_lds_bytes(0, s.H), per_walk = pool_lds_bytes(1, s.H) - at0;
         PN_FAIL(PN_ERR_ARG, "W=%d walks per node exceed the pooling kernels' LDS budget (W <= %d at H=%d)", s.W,
-                (64 * 1024 - 48 * s.H) / 64, s.H);
+                (int)((64 * 1024 - at0) / per_walk), s.H);
+    }
     if (s.variant == PN_VARIANT_PAGG && s.L != 4)
         PN_FAIL(PN_ERR_ARG, "PAGG has exactly four distance layers nei0..nei3 (copy.py:310-313); L=%d", s.L);
     if (s.cell < 0 || s.cell > CELL_SUM) PN_FAIL(PN_ERR_ARG, "unknown cell %d", s.cell);
@@ -1276,7 +231,7 @@ WsLayout ws_layout(const Dims &d) {
     w.rank = take(d.compact ? N * L * 4 : 0);
     w.list = take(d.compact ? (size_t)d.ZR * 4 : 0);
     w.seg = take(d.compact ? (L + 2) * 4 : 0);
-    w.bsum = take(d.compact ? ((N * L + SCAN_BLOCK - 1) / SCAN_BLOCK + 1) * 4 : 0);
+    w.bsum = take(d.compact ? (scan_block_count((int64_t)(N * L)) + 1) * 4 : 0);
     if (d.det) {
         // contributions of the gather backward ([Pb * L, H] rows), their (destination row, position) pairs before and
         // after the sort, the sort's temporary storage, the sums of the segments that cross a chunk boundary; the
@@ -1367,41 +322,28 @@ int resolve_call(Call &c, pn_context *ctx, const pn_pagg_args *a, hipStream_t st
     return PN_OK;
 }
 
-inline PlanDims plan_dims(const Call &c) {
+// the path steps of the batch's slots [slot_begin, slot_begin + count), as the index kernels walk them
+inline PlanSteps plan_steps(const Call &c, int64_t slot_begin, int64_t count) {
     const Dims &d = c.d;
-    return PlanDims{d.S_total, d.W, d.L, d.N, d.P_total, c.a->index_rows_local ? (int64_t)d.group_begin * d.W : 0};
+    const PlanDims pd{d.S_total, d.W, d.L, d.N, d.P_total, c.a->index_rows_local ? (int64_t)d.group_begin * d.W : 0};
+    return PlanSteps{d.variant, c.a->ids, c.a->codes, pd, slot_begin, count};
 }
 
 int run_plan(const Call &c, hipStream_t s, int b) {
     const Dims &d = c.d;
-    const int64_t count = (int64_t)c.groups(b) * d.W, n = count * d.L;
-    const PlanDims pd = plan_dims(c);
-    hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d.variant, c.a->ids, c.a->codes,
-                       pd, c.group0(b) * d.W, count, d.compact ? c.at<const int32_t>(c.w.rank) : nullptr,
-                       c.at<int32_t>(c.w.rowidx), c.at<int32_t>(c.w.egoidx), c.at<int32_t>(c.w.slotof));
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
+    return launch_plan(s, plan_steps(c, c.group0(b) * d.W, (int64_t)c.groups(b) * d.W),
+                       d.compact ? c.at<const int32_t>(c.w.rank) : nullptr, c.at<int32_t>(c.w.rowidx), c.at<int32_t>(c.w.egoidx),
+                       c.at<int32_t>(c.w.slotof));
 }
 
 // flags -> rank / list / seg for the (node, code) rows this call's paths touch (the hetero class: the whole batch's)
 int run_compact_rows(const Call &c, hipStream_t s) {
     const Dims &d = c.d;
     const bool het = d.variant == PN_VARIANT_HETERO;
-    const int64_t slot0 = het ? 0 : (int64_t)d.group_begin * d.W, count = (int64_t)(het ? d.S_total : d.S) * d.W, n = count * d.L;
-    const int64_t rows = (int64_t)d.N * d.L;
-    const PlanDims pd = plan_dims(c);
-    uint8_t *flags = c.at<uint8_t>(c.w.flags);
-    PN_CHECK_HIP(hipMemsetAsync(flags, 0, (size_t)rows, s));
-    hipLaunchKernelGGL(mark_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d.variant, c.a->ids, c.a->codes, pd,
-                       slot0, count, flags);
-    const int nb = (int)((rows + SCAN_BLOCK - 1) / SCAN_BLOCK);
-    int32_t *seg = c.at<int32_t>(c.w.seg), *bsum = c.at<int32_t>(c.w.bsum);
-    hipLaunchKernelGGL(scan_count_kernel, dim3(nb), dim3(256), 0, s, flags, rows, bsum);
-    hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(1024), 0, s, bsum, nb, seg + d.L);
-    hipLaunchKernelGGL(scan_rank_kernel, dim3(nb), dim3(256), 0, s, flags, rows, d.N, d.L, bsum, c.at<int32_t>(c.w.rank),
-                       c.at<int32_t>(c.w.list), seg);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
+    const int64_t slot0 = het ? 0 : (int64_t)d.group_begin * d.W, count = (int64_t)(het ? d.S_total : d.S) * d.W;
+    return launch_compact_rows(s, plan_steps(c, slot0, count),
+                               CompactRows{c.at<uint8_t>(c.w.flags), c.at<int32_t>(c.w.bsum), c.at<int32_t>(c.w.rank),
+                                           c.at<int32_t>(c.w.list), c.at<int32_t>(c.w.seg)});
 }
 
 // ---- the generic recurrence (H > 256): step-by-step kernels + the fp32 GEMM ------------------------------------------
@@ -1438,19 +380,16 @@ int run_seq_fwd_generic(const Call &c, int b, bool save) {
     gp.state = c.at<float>(c.w.dhn);            // (a backward-only buffer: the running cell / hidden state lives there)
     const int H = d.H, GH = d.G * H, P = gp.P;
     const float *Wcat = c.at<const float>(c.w.Wp);
-    const unsigned bx = (unsigned)(((int64_t)P * (H / 4) + 255) / 256), be = (unsigned)(((int64_t)P * H + 255) / 256);
     StageTimer tm(c.ctx, ST_SEQ_FWD, c.stream);
     for (int t = 0; t < d.L; t++) {
         gp.t = t;
-        hipLaunchKernelGGL(gen_x_kernel, dim3(bx), dim3(256), 0, c.stream, gp);
-        PN_CHECK_HIP(hipGetLastError());
+        if (int rc = launch_gen_x(c.stream, gp)) return rc;
         // pre[q, :] = [x_t | h_{t-1}] . Wcat^T + b      (step 0: h_{-1} = 0, the x half of K suffices)
         GemmParams g = gemm_linear_fwd(gp.xh + (size_t)t * 2 * H, (int64_t)d.L * 2 * H, Wcat, 2 * H, gp.pre + (size_t)t * GH,
                                        (int64_t)d.L * GH, P, t == 0 ? H : 2 * H, GH);
         g.bias = gp.biasc;
         if (int rc = launch_gemm3(c.stream, gemm3_of(g))) return rc;
-        hipLaunchKernelGGL(gen_cell_fwd_kernel, dim3(be), dim3(256), 0, c.stream, gp);
-        PN_CHECK_HIP(hipGetLastError());
+        if (int rc = launch_gen_cell_fwd(c.stream, gp)) return rc;
     }
     return PN_OK;
 }
@@ -1466,20 +405,17 @@ int run_seq_bwd_generic(const Call &c, int b) {
     const int H = d.H, GH = d.G * H, P = gp.P;
     const float *WcatT = c.at<const float>(c.w.WpT);
     float *gx = c.at<float>(c.w.gx);
-    const unsigned bx = (unsigned)(((int64_t)P * (H / 4) + 255) / 256), be = (unsigned)(((int64_t)P * H + 255) / 256);
     {
         StageTimer tm(c.ctx, ST_SEQ_BWD, c.stream);
         for (int t = d.L - 1; t >= 0; t--) {
             gp.t = t;
-            hipLaunchKernelGGL(gen_cell_bwd_kernel, dim3(be), dim3(256), 0, c.stream, gp);
-            PN_CHECK_HIP(hipGetLastError());
+            if (int rc = launch_gen_cell_bwd(c.stream, gp)) return rc;
             // [dx_t | dh_{t-1}] = dG_t . [W_ih | W_hh]      (step 0: the dx half suffices)
             // (a forward through the transposed weights WcatT [2 H, G H])
             const GemmParams g = gemm_linear_fwd(gp.pre + (size_t)t * GH, (int64_t)d.L * GH, WcatT, GH, gx, 2 * H, P, GH,
                                                  t == 0 ? H : 2 * H);
             if (int rc = launch_gemm3(c.stream, gemm3_of(g))) return rc;
-            hipLaunchKernelGGL(gen_scatter_kernel, dim3(bx), dim3(256), 0, c.stream, gp);
-            PN_CHECK_HIP(hipGetLastError());
+            if (int rc = launch_gen_scatter(c.stream, gp)) return rc;
         }
     }
     return PN_OK;
@@ -1499,14 +435,9 @@ inline bool bank_epilogue_range(const Call &c) {
 int run_pack_fwd(const Call &c, hipStream_t s) {
     const Dims &d = c.d;
     if (d.G == 0) return PN_OK;         // mean / sum: nothing to pack
-    if (d.generic) {
-        const int64_t n = (int64_t)d.G * d.H * 2 * d.H;
-        hipLaunchKernelGGL(gen_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c.a->w_ih, c.a->w_hh,
-                           c.a->b_ih, c.a->b_hh, d.H, d.G, d.gru, c.at<float>(c.w.Wp),
-                           c.at<float>(c.w.WpT), c.at<float>(c.w.biasc));
-        PN_CHECK_HIP(hipGetLastError());
-        return PN_OK;
-    }
+    if (d.generic)
+        return launch_gen_pack(s, c.a->w_ih, c.a->w_hh, c.a->b_ih, c.a->b_hh, d.H, d.G, d.gru, c.at<float>(c.w.Wp),
+                               c.at<float>(c.w.WpT), c.at<float>(c.w.biasc));
     if (d.math == PN_SEQ_MATH_F16X2) {      // two fp16 planes, scaled by the weights' own maxima (pn_seqh.hip)
         SeqRange *rg = c.at<SeqRange>(c.w.range);
         // (it also clears the slots this call's atomicMax launches add to; a reused dense bank keeps its range.x.)  A training
@@ -1541,14 +472,8 @@ int run_seq_reduce(const Call &c, int b, bool backward) {
     rp.dyn = a->step_state;
     rp.mask = a->mask_seq;
     if (backward && d.det) rp.rowidx = c.at<int32_t>(c.w.iota), rp.dZ = c.at<float>(c.w.dx);     // (see det_scatter_kernel)
-    const int64_t n = (int64_t)rp.P * (d.H / 4);
     StageTimer tm(c.ctx, backward ? ST_SEQ_BWD : ST_SEQ_FWD, c.stream);
-    if (backward)
-        hipLaunchKernelGGL(seq_reduce_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.stream, rp);
-    else
-        hipLaunchKernelGGL(seq_reduce_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.stream, rp);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
+    return launch_seq_reduce(c.stream, rp, backward);
 }
 
 // Inference without dropout on the fp16 kernels: the input half of the gates is applied to the rows of the bank once
@@ -1636,7 +561,6 @@ PoolParams pool_fwd_params(const Call &c, int b, float *out) {
     pp.out = out;
     return pp;
 }
-inline size_t pool_fwd_lds_bytes(const Dims &d) { return (size_t)(2 * d.W + 6 * d.H) * sizeof(float); }
 // outputs: pn_pagg_forward's own pass writes the caller's optional outputs (out_*: rows of micro-batch b); the backward's
 // re-runs do not
 int run_pool_fwd(const Call &c, int b, float *out, bool outputs = false) {
@@ -1649,9 +573,7 @@ int run_pool_fwd(const Call &c, int b, float *out, bool outputs = false) {
         if (a->out_path_state) pp.path_state = a->out_path_state + r0 * c.d.W * c.d.H;
     }
     StageTimer tm(c.ctx, ST_POOL_FWD, c.stream);
-    hipLaunchKernelGGL(pool_fwd_kernel, dim3(pp.S), dim3(256), pool_fwd_lds_bytes(c.d), c.stream, pp);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
+    return launch_pool_fwd(c.stream, pp);
 }
 
 int check_forward_args(const Call &c, const char *who) {
@@ -1764,11 +686,9 @@ int run_tables(const Call &c, JoinGuard &joiner, ZeroFill *zero_fill = nullptr) 
         // weights, the table in the slot of the saved gates -- neither is used by an inference forward
         StageTimer tm(ctx, ST_BANK, stream);
         const int GH = d.G * H;
-        const int64_t n = (int64_t)GH * 2 * H;
         float *Wcat = c.at<float>(c.w.WpT);
-        hipLaunchKernelGGL(gen_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a->w_ih, a->w_hh, a->b_ih,
-                           a->b_hh, H, d.G, d.gru, Wcat, (float *)nullptr, c.at<float>(c.w.biasc));
-        PN_CHECK_HIP(hipGetLastError());
+        if (int rc = launch_gen_pack(stream, a->w_ih, a->w_hh, a->b_ih, a->b_hh, H, d.G, d.gru, Wcat, nullptr, c.at<float>(c.w.biasc)))
+            return rc;
         const int M = (int)d.ZR;
         const bool g3 = H % G3_KT == 0 && (int64_t)((M + G3_BM - 1) / G3_BM) * ((GH + G3_BN - 1) / G3_BN) >= 256;
         GemmParams g = gemm_linear_fwd(c.Z, H, Wcat, 2 * H, c.at<float>(c.w.saved), GH, M, H, GH);
@@ -1839,8 +759,7 @@ int prepare_det_orders(const Call &c, hipStream_t s, int b) {
     }
     q.shift = g.bits;
     int32_t *ck = c.at<int32_t>(c.w.keys), *pos = c.at<int32_t>(c.w.skey);
-    hipLaunchKernelGGL(det_keys3_kernel, dim3((unsigned)((g.total + 255) / 256)), dim3(256), 0, s, q, ck, pos);
-    PN_CHECK_HIP(hipGetLastError());
+    if (int rc = launch_det_keys3(s, q, g.total, ck, pos)) return rc;
     // (okey / osrc are the heads of the two contiguous output blocks; an empty EGO segment leaves its slot unused: the
     //  segments that follow start where the sort puts them only if the layout matches -- so the outputs are addressed by the
     //  running sum of the ACTUAL counts, which equals the layout's whenever a segment is present)
@@ -1866,24 +785,9 @@ DetScatterParams det_params(const Call &c, int which, int b, const float *rows, 
                             g.n[which], off / DET_CHUNK + which, rows, scal, vec, dst, c.at<float>(c.w.cpart), c.d.H};
 }
 
-// one or two scatters (the pooling backward's pair) per launch: pass 1, then pass 2
-int run_det_scatters(const Call &c, const DetScatterParams *list, int count) {
-    DetScatterPair pp{};
-    int64_t kmax = 0;
-    for (int i = 0; i < count; i++) pp.s[i] = list[i], kmax = std::max(kmax, list[i].K);
-    if (kmax <= 0) return PN_OK;
-    const int gpb = 256 / (c.d.H / 4);
-    const int64_t chunks = (kmax + DET_CHUNK - 1) / DET_CHUNK;
-    const dim3 grid((unsigned)((chunks + gpb - 1) / gpb), (unsigned)count);
-    hipLaunchKernelGGL(det_scatter_kernel<1>, grid, dim3(256), 0, c.stream, pp);
-    hipLaunchKernelGGL(det_scatter_kernel<2>, grid, dim3(256), 0, c.stream, pp);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
-}
-
 int run_det_scatter(const Call &c, int which, int b, const float *rows, const float *scal, const float *vec, float *dst) {
     const DetScatterParams p = det_params(c, which, b, rows, scal, vec, dst);
-    return run_det_scatters(c, &p, 1);
+    return launch_det_scatters(c.stream, &p, 1);
 }
 
 // ---- the backward's stages (pagg_backward_impl) ---------------------------------------------------------------------------
@@ -1905,15 +809,8 @@ int run_fc2_grad(const Call &c, int b, JoinGuard &joiner, hipStream_t s, const f
     const Dims &d = c.d;
     const pn_pagg_args *a = c.a;
     const int H = d.H, Sb = c.groups(b);
-    if (loss) {
-        if (opts)
-            hipLaunchKernelGGL(loss_sum_opts_kernel, dim3(1), dim3(1024), 0, s, c.at<const float>(c.w.outb), Sb, *opts, loss,
-                               d.nb == 1 ? 1 : 0);
-        else
-            hipLaunchKernelGGL(loss_sum_kernel, dim3(1), dim3(1024), 0, s, c.at<const float>(c.w.outb), Sb, grad_scale, loss,
-                               d.nb == 1 ? 1 : 0);
-        PN_CHECK_HIP(hipGetLastError());
-    }
+    if (loss)
+        if (int rc = launch_loss_sum(s, c.at<const float>(c.w.outb), Sb, grad_scale, opts, loss, d.nb == 1)) return rc;
     if (g_out) {        // (no g_out: only the embedding is differentiated, g_fc2_* keep the backward's zero fill)
         StageTimer tm(c.ctx, ST_FC2_GRAD, s);
         GemmParams g = gemm_weight_grad(g_out, d.C, c.at<float>(c.w.layer1), 2 * H, a->g_fc2_w, 2 * H, Sb, 2 * H, d.C);
@@ -1972,12 +869,11 @@ PoolBwdParams pool_bwd_params(const Call &c, int b, const float *g_out) {
     }
     return pp;
 }
-inline size_t pool_bwd_lds_bytes(const Dims &d) { return (size_t)(4 * (2 * d.W + d.H) + 8 * d.H + 8 * d.W) * sizeof(float); }
 
-// pn_pagg_train_step, default mode: pooling forward, loss and pooling backward of micro-batch b in one launch
+// pn_pagg_train_step, default mode: pooling forward, loss and pooling backward of micro-batch b in one launch (which kernel:
+// launch_pool_step, pn_pool.hip)
 int run_pool_step(const Call &c, int b, const PoolBwdParams &pp, const int64_t *target, float grad_scale, const LossOpts *opts) {
     const Dims &d = c.d;
-    const int H = d.H, Sb = pp.S, knob = knobs_of(c.ctx).pool_step;
     PoolStepParams ps{};
     ps.f = pool_fwd_params(c, b, c.a->out + (size_t)b * d.Sb * d.C);
     ps.b = pp;
@@ -1986,59 +882,22 @@ int run_pool_step(const Call &c, int b, const PoolBwdParams &pp, const int64_t *
     ps.gout = c.at<float>(c.w.gout);
     ps.b.g_out = ps.gout;
     ps.lossg = c.at<float>(c.w.outb);       // (the fused step's logits go to the caller: the slot is free)
-    const size_t lds_step = std::max(pool_bwd_lds_bytes(d), pool_fwd_lds_bytes(d));
     StageTimer tm(c.ctx, ST_POOL_FWD, c.stream);
-    // pool_step2_kernel holds the logits and their gradient in LDS (2 C floats; 6 144 + 8 C bytes at H = 128), which
-    // make_dims does not bound: past 64 KiB (C > 7 424 at H = 128) the node goes to pool_step_kernel<4>, whose LDS does
-    // not depend on C (64 W + 48 H bytes, within 64 KiB by make_dims)
-    const size_t lds_step2 = pool_step2_lds_bytes(10, H, d.C);
-    const bool step2 = d.W <= 40 && H <= 128 && H >= 32 && lds_step2 <= 64 * 1024 && knob >= 1 && knob != 2;
-    if (opts) {         // pn_pagg_train_step_loss: the same three routes, their option-aware kernels
-        const PoolStepLossParams ql{ps, *opts};
-        if (step2) {
-            hipLaunchKernelGGL((pool_step2_loss_kernel<10, 2>), dim3(Sb), dim3(256), lds_step2, c.stream, ql);
-        } else if (H <= 256) {
-            hipLaunchKernelGGL(pool_step_loss_kernel<4>, dim3(Sb), dim3(256), lds_step, c.stream, ql);
-        } else {
-            if (int rc = ensure_dynamic_lds(c.ctx, reinterpret_cast<const void *>(pool_step_loss_kernel<16>), (int)lds_step)) return rc;
-            hipLaunchKernelGGL(pool_step_loss_kernel<16>, dim3(Sb), dim3(256), lds_step, c.stream, ql);
-        }
-    } else if (step2) {
-        // the node's rows in registers (pool_step2_kernel); PN_POOL_STEP=2: the three bodies back to back
-        hipLaunchKernelGGL((pool_step2_kernel<10, 2>), dim3(Sb), dim3(256), lds_step2, c.stream, ps);
-    } else if (H <= 256) {
-        hipLaunchKernelGGL(pool_step_kernel<4>, dim3(Sb), dim3(256), lds_step, c.stream, ps);
-    } else {
-        if (int rc = ensure_dynamic_lds(c.ctx, reinterpret_cast<const void *>(pool_step_kernel<16>), (int)lds_step)) return rc;
-        hipLaunchKernelGGL(pool_step_kernel<16>, dim3(Sb), dim3(256), lds_step, c.stream, ps);
-    }
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
+    return launch_pool_step(c.ctx, c.stream, ps, opts, knobs_of(c.ctx).pool_step);
 }
 
 // the pooling backward (pool_bwd_wg_kernel) in its stage bracket -- an empty bracket behind the pooling step, which did it
 int run_pool_bwd(const Call &c, const PoolBwdParams &pp, bool pool_step) {
     StageTimer tm(c.ctx, ST_POOL_BWD, c.stream);
     if (pool_step) return PN_OK;
-    const size_t lds_bytes = pool_bwd_lds_bytes(c.d);
-    if (pp.H <= 256) {
-        hipLaunchKernelGGL(pool_bwd_wg_kernel<4>, dim3(pp.S), dim3(256), lds_bytes, c.stream, pp);
-    } else {
-        if (int rc = ensure_dynamic_lds(c.ctx, reinterpret_cast<const void *>(pool_bwd_wg_kernel<16>), (int)lds_bytes)) return rc;
-        hipLaunchKernelGGL(pool_bwd_wg_kernel<16>, dim3(pp.S), dim3(256), lds_bytes, c.stream, pp);
-    }
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
+    return launch_pool_bwd(c.ctx, c.stream, pp);
 }
 
 // the attention weights' terms in workgroup order (a partial per workgroup of the pooling backward) on `s`; on the second
 // stream the end is marked for the join
 int run_att_reduce(const Call &c, JoinGuard &joiner, hipStream_t s, const PoolBwdParams &pp) {
-    if (c.d.variant != PN_VARIANT_PAGG) {
-        hipLaunchKernelGGL(det_att_reduce_kernel, dim3((2 * pp.H + 4 + 63) / 64), dim3(1024), 0, s, pp.det_att, pp.S, pp.H,
-                           pp.g_att_w, pp.g_att_b);
-        PN_CHECK_HIP(hipGetLastError());
-    }
+    if (c.d.variant != PN_VARIANT_PAGG)
+        if (int rc = launch_att_reduce(s, pp.det_att, pp.S, pp.H, pp.g_att_w, pp.g_att_b)) return rc;
     return s != c.stream ? joiner.mark() : PN_OK;
 }
 
@@ -2049,9 +908,9 @@ int run_pool_scatters(const Call &c, int b, const PoolBwdParams &pp) {
     const bool has_att = c.d.variant != PN_VARIANT_PAGG;
     const DetScatterParams two[2] = {det_params(c, DET_SEL, b, pp.det_sel, nullptr, nullptr, pp.dXh),
                                      det_params(c, DET_EGO, b, nullptr, pp.det_ds, c.a->att_w + c.d.H, pp.dego)};
-    if (has_att && pp.dego != pp.dXh) return run_det_scatters(c, two, 2);
-    if (int rc = run_det_scatters(c, two, 1)) return rc;
-    return has_att ? run_det_scatters(c, two + 1, 1) : PN_OK;
+    if (has_att && pp.dego != pp.dXh) return launch_det_scatters(c.stream, two, 2);
+    if (int rc = launch_det_scatters(c.stream, two, 1)) return rc;
+    return has_att ? launch_det_scatters(c.stream, two + 1, 1) : PN_OK;
 }
 
 // BPTT of micro-batch b and the gather-backward scatter (mean / sum encoders: the scatter alone) -- run_seq_fwd's counterpart
@@ -2252,9 +1111,7 @@ int run_fc0_bwd(const Call &c, const float *dXh) {
         // rows of X padded to 16 bytes first (see xpad_floats); the padding columns are zeros, and outputs past F are not stored
         const int F4 = (d.F + 3) / 4 * 4;
         float *Xp = c.at<float>(c.w.xpad);
-        const int64_t n4 = (int64_t)d.N * (F4 / 4);
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, a->X, (int64_t)d.N, d.F, F4, Xp);
-        PN_CHECK_HIP(hipGetLastError());
+        if (int rc = launch_pad_rows(stream, a->X, (int64_t)d.N, d.F, F4, Xp)) return rc;
         const RgradParams rp{dXh, xgate, Xp, H, F4, d.N, H, d.F, a->g_fc0_w, d.F, a->g_fc0_b, nullptr, nullptr};
         if (int rc = launch_rgrad(ctx, stream, rp)) return rc;
     } else if (a->g_fc0_w) {
@@ -2271,15 +1128,6 @@ int run_fc0_bwd(const Call &c, const float *dXh) {
 }
 
 }  // namespace
-
-int pn::ZeroFill::flush(void *stream, bool timed) {
-    if (!zl.n) return PN_OK;
-    StageTimer tm(timed ? ctx : nullptr, ST_ZERO_FILL, stream);       // (d Z and d Xh are the bulk: rows of the graph, not paths)
-    hipLaunchKernelGGL(zero_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, zl);
-    PN_CHECK_HIP(hipGetLastError());
-    zl.n = 0;
-    return PN_OK;
-}
 
 extern "C" {
 
@@ -2331,33 +1179,6 @@ int pn_pagg_debug_offsets(const pn_pagg_shape *shape, int64_t out[4]) {
     out[1] = (int64_t)w.Z;
     out[2] = (int64_t)w.hn;
     out[3] = (int64_t)w.layer1;
-    return PN_OK;
-}
-
-int pn_pagg_gather(pn_context *ctx, const pn_pagg_shape *shape, const float *table, const int32_t *ids,
-                   const uint8_t *codes, float *rows, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!shape || !table || !ids || !codes || !rows) PN_FAIL(PN_ERR_ARG, "pn_pagg_gather: null");
-    if (int rc = context_check_device(ctx)) return rc;
-    const pn_pagg_shape &s = *shape;
-    if (s.S < 0 || s.W < 1 || s.L < 1 || s.H < 1 || s.N < 1) PN_FAIL(PN_ERR_ARG, "pn_pagg_gather: bad shape");
-    const int S_total = s.S_total > 0 ? s.S_total : s.S;
-    if (s.group_begin < 0 || (int64_t)s.group_begin + s.S > S_total) PN_FAIL(PN_ERR_ARG, "pn_pagg_gather: bad slice");
-    const int64_t count = (int64_t)s.S * s.W, rowsn = count * s.L;
-    if (rowsn == 0) return PN_OK;
-    const bool vec = (s.H % 4 == 0) && ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(rows)) % 16 == 0);
-    const int64_t work = rowsn * (vec ? s.H / 4 : s.H);
-    const int blocks = (int)std::min<int64_t>((work + 255) / 256, 256 * 32);
-    const PlanDims pd{S_total, s.W, s.L, s.N, (int64_t)S_total * s.W, 0};
-    const int64_t slot_begin = (int64_t)s.group_begin * s.W;
-    StageTimer tm(ctx, ST_GATHER, stream);
-    if (vec)
-        hipLaunchKernelGGL(gather_kernel<4>, dim3(blocks), dim3(256), 0, stream, s.variant, table, ids, codes, pd,
-                           slot_begin, count, s.H, rows);
-    else
-        hipLaunchKernelGGL(gather_kernel<1>, dim3(blocks), dim3(256), 0, stream, s.variant, table, ids, codes, pd,
-                           slot_begin, count, s.H, rows);
-    PN_CHECK_HIP(hipGetLastError());
     return PN_OK;
 }
 
@@ -2458,8 +1279,7 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
     const bool pool_step = fused && !d.det && knobs_of(ctx).pool_step != 0;
     if (d.det) {        // the identity the BPTT kernels index the contribution buffer with
         const int64_t n = std::max<int64_t>((int64_t)d.Sb * d.W * L, d.Sb);
-        hipLaunchKernelGGL(det_iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c.at<int32_t>(c.w.iota), n);
-        PN_CHECK_HIP(hipGetLastError());
+        if (int rc = launch_det_iota(stream, c.at<int32_t>(c.w.iota), n)) return rc;
     }
     if (d.G > 0 && !d.generic) {
         StageTimer tm(ctx, ST_PLAN_PACK, stream);      // (its own bracket: ST_SEQ_BWD times the BPTT kernel alone)
@@ -2529,6 +1349,15 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
     return run_fc0_bwd(c, dXh);
 }
 
+// what every training-step entry point asks of its arguments before it looks at the shape
+static int check_train_step_args(const pn_pagg_args *a, const int64_t *target, const float *loss, const char *who) {
+    if (!a) PN_FAIL(PN_ERR_ARG, "%s: null args", who);
+    if (a->out_embed || a->out_path_weight || a->out_path_state || a->g_embed)
+        PN_FAIL(PN_ERR_ARG, "%s: out_embed / out_path_weight / out_path_state / g_embed are for pn_pagg_forward / pn_pagg_backward", who);
+    if (!loss || (a->shape.S > 0 && !target)) PN_FAIL(PN_ERR_ARG, "%s: null target / loss", who);
+    return PN_OK;
+}
+
 int pn_pagg_backward(pn_context *ctx, const pn_pagg_args *a, void *stream) {
     return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, nullptr);
 }
@@ -2544,11 +1373,7 @@ int pn_pagg_train_step(pn_context *ctx, const pn_pagg_args *a, const int64_t *ta
 
 int pn_pagg_train_step_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const int64_t *target,
                               float grad_scale, float *loss, void *stream) {
-    if (!a) PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step: null args");
-    if (a->out_embed || a->out_path_weight || a->out_path_state || a->g_embed)
-        PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step: out_embed / out_path_weight / out_path_state / g_embed are for pn_pagg_forward / "
-                            "pn_pagg_backward");
-    if (!loss || (a->shape.S > 0 && !target)) PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step: null target / loss");
+    if (int rc = check_train_step_args(a, target, loss, "pn_pagg_train_step")) return rc;
     if (a->shape.S == 0) {          // nothing to aggregate: zero loss, zero gradients
         PN_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float), (hipStream_t)stream));
         return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp);
@@ -2560,11 +1385,7 @@ int pn_pagg_train_step_loss(pn_context *ctx, const pn_pagg_args *a, const pn_spa
                             const int64_t *target, float *loss, void *stream) {
     LossOpts o;
     if (int rc = loss_opts_from_spec(spec, "pn_pagg_train_step_loss", &o)) return rc;
-    if (!a) PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step_loss: null args");
-    if (a->out_embed || a->out_path_weight || a->out_path_state || a->g_embed)
-        PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step_loss: out_embed / out_path_weight / out_path_state / g_embed are for "
-                            "pn_pagg_forward / pn_pagg_backward");
-    if (!loss || (a->shape.S > 0 && !target)) PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step_loss: null target / loss");
+    if (int rc = check_train_step_args(a, target, loss, "pn_pagg_train_step_loss")) return rc;
     float *denom_out = spec->denominator_given ? nullptr : spec->denominator;
     if (a->shape.S == 0) {          // nothing to aggregate: zero loss, zero gradients (and D = 0, when it is this call's to write)
         PN_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float), (hipStream_t)stream));
@@ -2576,8 +1397,3 @@ int pn_pagg_train_step_loss(pn_context *ctx, const pn_pagg_args *a, const pn_spa
 
 }  // extern "C"
 
-#ifdef PN_POOL_TRACE
-extern "C" int pn_debug_pool_trace(long long *host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_pool_trace), sizeof(long long) * 2048 * 12) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -1,4 +1,4 @@
-// pn_pool_step2.inc -- pool_step2_kernel, the fused pooling step with the node's rows in registers (pn_pagg.hip includes this
+// pn_pool_step2.inc -- pool_step2_kernel, the fused pooling step with the node's rows in registers (pn_pool.hip includes this
 // text twice).  Plain, it is pool_step2_kernel exactly as it stood in pn_pagg.hip; with PN_STEP2_LOSS_OPTS defined it is
 // pool_step2_loss_kernel, the same kernel with pn_loss_spec's options in its cross-entropy block.  The preprocessor and not
 // a template parameter: the plain kernel's text is then token for token what it was, and so is its code (as a template

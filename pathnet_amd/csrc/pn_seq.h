@@ -1,6 +1,7 @@
 // pn_seq.h -- launch parameters of the three recurrent kernels (forward recurrence, BPTT, weight gradient), shared by
-// pn_pagg.hip (the bf16 x 3 kernels for every hidden size up to 256), pn_seqh.hip (the fp16 x 2 kernels, the default) and
-// pn_seq4.hip (the bf16 x 3 weight-gradient GEMM of the headline shape).  Not part of the ABI.
+// pn_pagg.hip (which fills them), pn_seqh.hip (the fp16 x 2 kernels, the default), pn_seq3.hip (the bf16 x 3 kernels for every
+// hidden size up to 256), pn_seq4.hip (the bf16 x 3 weight-gradient GEMM of the headline shape) and pn_seqgen.hip (the mean /
+// sum encoders and the step-by-step recurrence above 256).  Not part of the ABI.
 #pragma once
 #include <cstdint>
 
@@ -131,5 +132,55 @@ int launch_seq_fwdh(pn_context *ctx, void *stream, int H, int gc, const SeqFwdPa
 int launch_seq_fwdzw(pn_context *ctx, void *stream, int H, int gc, const SeqFwdParams &sp);
 int launch_seq_bwdh(pn_context *ctx, void *stream, int H, int gc, const SeqBwdParams &sp);
 int launch_wgradh(pn_context *ctx, void *stream, const WgradParams &wp, int H, int nsplit);
+
+// ---- pn_seqgen.hip: what stands in for the fused recurrent kernels -- the mean / sum encoders and the hidden sizes above 256 ----
+// ---- order-agnostic path encoders of the ablation ("mean" / "sum" instead of the recurrent cell): h_n of a path is the
+//      mean (sum) over its L steps of the dropped-out rows the recurrent kernels would consume.  One thread per (path,
+//      4 columns); the backward scatters scale * mask * d h_n back onto the L table rows.
+struct SeqReduceParams {
+    const float *Z;          // [N*L, H]
+    const int32_t *rowidx;   // [P, L]
+    const int32_t *slotof;   // [P]
+    float *hn;               // [P, H]   forward output
+    const float *dhn;        // [P, H]   backward input
+    float *dZ;               // [N*L, H] backward output (atomic scatter)
+    int P, L, H;
+    int64_t Pmask;
+    float scale;             // 1/L (mean) or 1 (sum)
+    float p_drop;
+    uint64_t seed;
+    const pn_step_state *dyn;
+    const float *mask;       // [L, Pmask, H] or null
+};
+int launch_seq_reduce(void *stream, const SeqReduceParams &p, bool backward);
+
+// the step-by-step recurrence (256 < H <= 1024): the element-wise kernels of step p.t; the caller runs the step's GEMM between them
+struct GenParams {
+    const float *Z;            // [N*L, H]
+    const int32_t *rowidx;     // [P, L]
+    const int32_t *slotof;     // [P]
+    float *xh;                 // [P, L, 2H]
+    float *pre;                // [P, L, GH]  forward: gate pre-activations of step t; backward: dG
+    float *saved;              // [P, L, SV, H] or null
+    float *state;              // [P, H] running cell / hidden state (forward), d c / the GRU's direct term (backward)
+    float *hn;                 // [P, H]
+    float *dh;                 // [P, H] backward: d loss / d h_t, updated in place
+    const float *gx;           // [P, 2H] backward: [dx_t | dh_{t-1}] of the step's GEMM
+    float *dZ;
+    const float *biasc;
+    int P, L, H, G, cell, t;
+    int64_t Pmask;
+    float p_drop;
+    uint64_t seed;
+    const pn_step_state *dyn;
+    const float *mask;
+};
+int launch_gen_x(void *stream, const GenParams &p);             // xh[q, t, 0:H] = mask * Z[row(q, t)];  t = 0 also clears the h half
+int launch_gen_cell_fwd(void *stream, const GenParams &p);      // pre[q, t, :] -> h_t (into xh of step t + 1, or hn), state, saved
+int launch_gen_cell_bwd(void *stream, const GenParams &p);      // dh, state, saved -> dG[q, t, :] (in pre)
+int launch_gen_scatter(void *stream, const GenParams &p);       // gx = [dx_t | dh_{t-1}]: mask * dx into dZ (atomics), dh_{t-1} into dh
+// Wcat [GH, 2H] = [W_ih | W_hh] in fp32 (GRU: the four slots with their zero halves), its transpose (WcatT, or null) and biasc
+int launch_gen_pack(void *stream, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, int H, int G, int gru,
+                    float *Wcat, float *WcatT, float *biasc);
 
 }  // namespace pn

@@ -21,7 +21,7 @@ constexpr int H4 = 128, G4 = 4;      // hidden size and gate slots this file is 
 
 // =====================================================================================================================
 // weight gradient:  [g_W_ih | g_W_hh] [G*H, 2H] = dG^T [G*H, R] . XH [R, 2H]   (R = P*L rows; colsum(dG) = bias gradient)
-//   Same decomposition as wgrad3_kernel (pn_pagg.hip): 256 x 256 output tile per workgroup (8 waves, 64 x 128 each),
+//   Same decomposition as wgrad3_kernel (pn_seq3.hip): 256 x 256 output tile per workgroup (8 waves, 64 x 128 each),
 //   the R rows split over blockIdx.z in strided K tiles, partial tiles to part_w / part_b for wgrad_reduce_kernel.
 //   What changes is the pipeline: K tiles of 16 rows, TWO LDS stages, and the loads of tile i+2 issued behind the
 //   products of tile i, in flight across the barrier -- wgrad3 alternates "stage 32 rows" and "96 MFMAs per wave" in

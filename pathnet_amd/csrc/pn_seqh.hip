@@ -2,7 +2,7 @@
 // /root/reference/PathNet_run.py:164,195,265 and baseline/GPRGNN/src/copy.py:308,349 (forward), the autograd backward
 // of PathNet_run.py:351 through them (BPTT and weight gradient), for every hidden size up to 256.
 //
-// Same decomposition as the bf16 kernels of pn_pagg.hip (32-path tile per workgroup, wave w owns hidden units 32w..32w+31
+// Same decomposition as the bf16 kernels of pn_seq3.hip (32-path tile per workgroup, wave w owns hidden units 32w..32w+31
 // of all gates, [x_t | h_{t-1}] in LDS, weight fragments streamed L2 -> VGPR by asm loads) with the arithmetic of
 // pn_kernels.h "two planes, three MFMAs": half the matrix instructions per product, 2/3 of the weight stream and of the
 // LDS tile.  What that buys structurally:
@@ -181,7 +181,7 @@ __device__ __forceinline__ int gru_weight_row(int slot, int j, int H) { return (
 //     Wp[(((w*KS + s)*2 + plane)*G + g)*64 + lane] (16 bytes) =
 //         plane of 2^e Wcat[g*H + 32w + (lane & 31)][16 s + 8 (lane >> 5) .. +7],   KS = 2H/16 k-steps, e = e_ih | e_hh
 //   A operand: LDS holds the two planes of the tile [32][x_t | h_{t-1}], row pitch 4H + 16 bytes.
-//   GRU on the LSTM's four gate slots as in pn_pagg.hip (pack_fwd3_kernel).
+//   GRU on the LSTM's four gate slots as in pn_seq3.hip (pack_fwd3_kernel).
 // =====================================================================================================================
 __device__ __forceinline__ void pack_fwdh_body(int idx, const float *__restrict__ w_ih, const float *__restrict__ w_hh,
                                                const float *__restrict__ b_ih, const float *__restrict__ b_hh, int H, int G, int gru,

@@ -1,5 +1,5 @@
 // pn_sort.hip -- the one place the library leans on a ROCm primitive: a stable LSD radix sort of (int32 key, int32 value)
-// pairs (hipCUB / rocPRIM DeviceRadixSort), used by the deterministic backward of the aggregator (pn_pagg.hip,
+// pairs (hipCUB / rocPRIM DeviceRadixSort), used by the deterministic backward of the aggregator (pn_pagg.hip / pn_det.hip,
 // pn_set_deterministic): the gather backward's contributions are ordered by destination row, ties in the order of the
 // path steps, and then summed in that order; and by the sampler's table builders (pn_tables.hip: edge rows bucketed by
 // source in file order, CSR pairs).  Its own translation unit because the rocPRIM headers take ten seconds to compile.

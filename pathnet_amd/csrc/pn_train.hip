@@ -32,7 +32,7 @@ __global__ __launch_bounds__(1024) void cross_entropy_kernel(const float *__rest
         // at the magnitude of the largest logit and every probability would carry ulp(max |x|) / 2 of relative error.
         const float ls = logf(s);
         // A target outside [0, classes) poisons the loss (NaN) and leaves a zero gradient row; no address is formed from
-        // it: a clamped index and selects, no branch around a load (pool_step2_kernel, pn_pagg.hip, has the same lines)
+        // it: a clamped index and selects, no branch around a load (pool_step2_kernel, pn_pool_step2.inc, has the same lines)
         const int64_t t64 = target[r];
         const bool ok = t64 >= 0 && t64 < (int64_t)classes;
         const int t = ok ? (int)t64 : 0;

@@ -301,7 +301,9 @@ def test_no_kernel_spills_registers():
     """The recurrent kernels prefetch weight fragments with asm loads whose destination registers the compiler must
     not spill between the load and its wait (cdna_hip_programming.md §5.7): require zero scratch in every kernel of every
     source file under csrc/ -- the asm-load kernels live in pn_seqh / pn_seq3 / pn_seq4 / pn_gemm / pn_rgrad since the
-    round-6 split, and a glob keeps the next split covered.  (Eleven hipcc compiles: a minute or two of the CPU suite.)
+    round-6 split, and a glob keeps the next split covered.  (One hipcc compile per file: a minute or two of the CPU suite.)
+    A file may report no kernel only if it holds none: pn_pagg.hip is the aggregator's orchestration, all host code, since
+    its kernels moved to pn_plan / pn_seqgen / pn_pool / pn_det.
     The rocPRIM radix sort that pn_sort.hip instantiates is the library's code, not ours: its onesweep kernels keep 80
     bytes per lane of scratch (ROCm 7.2) and are left out of the check."""
     import glob
@@ -317,7 +319,11 @@ def test_no_kernel_spills_registers():
         assert r.returncode == 0, r.stderr[-500:]
         # (every kernel's remarks: its name, then its resources)
         kernels = re.findall(r"Function Name: (\S+) .*?ScratchSize \[bytes/lane\]: (\d+)", r.stderr, re.S)
-        assert kernels, f
+        if not kernels:     # nothing reported: then there is nothing to report, or the remarks were not understood
+            with open(os.path.join(src, f)) as fh:
+                assert "__global__" not in fh.read(), f
+            assert f == "pn_pagg.hip", f
+            continue
         spills = [(name, int(n)) for name, n in kernels if int(n) != 0 and "rocprim" not in name]
         assert not spills, (f, spills)
 

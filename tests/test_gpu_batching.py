@@ -692,7 +692,7 @@ def test_indices_outside_the_graph_are_refused_or_clamped():
 
 
 # ------------------------------------------------------------------------------------------------
-# touched-row compaction of the distance bank (pn_pagg.hip: run_compact_rows)
+# touched-row compaction of the distance bank (pn_pagg.hip: run_compact_rows; the kernels: pn_plan.hip)
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant,cell", [("homo", None), ("hetero", None), ("pagg", None), ("homo", "gru"), ("hetero", "mean")])
 def test_compact_rows_forced_on_small_shapes_match_the_dense_bank(variant, cell, monkeypatch):

@@ -16,7 +16,7 @@ step-major tables.  What that must survive:
 
 References: without dropout and with explicit masks the CPU oracle (oracle/pagg_oracle.py) in fp32 under the suite's
 contract (logits within 1e-5, gradients by tests/gradcheck.py).  The built-in masks are drawn inside the kernels from a
-seed the oracle cannot see: there the reference is the bf16 x 3 kernels of pn_pagg.hip on the same module, inputs and
+seed the oracle cannot see: there the reference is the bf16 x 3 kernels of pn_seq3.hip on the same module, inputs and
 seed (they draw the same masks and are themselves held to the oracle by tests/test_gpu_seqh.py), under that file's
 bounds for the pair (logits 2e-6, gradients rel 1e-5)."""
 import numpy as np

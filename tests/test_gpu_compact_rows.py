@@ -1,5 +1,5 @@
 """The touched-row ("compact") distance bank against the fp64 oracle (pn_pagg.hip: run_compact_rows, the compact branches of
-run_tables and run_bank_bwd).  make_dims switches to it when 2 * S * W * L < N * L -- every ordinary mini-batch of a large
+run_tables and run_bank_bwd; the flag / scan kernels: pn_plan.hip).  make_dims switches to it when 2 * S * W * L < N * L -- every ordinary mini-batch of a large
 graph -- and PN_COMPACT=1 forces it.  Its row counts exist in device memory only (seg[code], seg[L]) while its launches are
 sized by the host-side bound mmax = min(N, ZR), so the cases are built by construction at the edges where such kernels go
 wrong: a code no path touches, per-code segments of 63 / 64 / 65 / 127 / 128 / 129 rows (the 64 x 64 GEMM tile, the

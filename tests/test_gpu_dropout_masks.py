@@ -9,7 +9,7 @@ at every position; there is no tolerance.  What draws, and what reads it here:
   seq_reduce_kernel (mean / sum), gen_mask (256 < H <= 1024)                                           states of encode()
   seq_bwdh_kernel / seq_bwd3_kernel and the generic / reducing backward (saved keep bytes, or drawn
   again when a micro-batch is re-run)                                                                   X.grad, row by row
-  the pooling kernels of pn_pagg.hip (stream 2), forward, backward and the fused step's                fc2.weight.grad, X.grad
+  the pooling kernels of pn_pool.hip (stream 2), forward, backward and the fused step's                fc2.weight.grad, X.grad
 
 over P = S W in {1, 33, 65}, L in {1, 4}, p in {0.1, 0.5, 0.9}, the seeds 0, one drawn through torch.manual_seed and
 2^62 - 1, H in {32, 96, 128, 256} in both seq_math modes, H = 100 (the counters run on the padded 128), H = 288, every

@@ -1,6 +1,6 @@
 """The training step's pooling launch (pn_pagg_train_step, default mode: attention + pooling + classifier, softmax cross
 entropy and the pooling backward of a node in one workgroup) against the fp64 oracle, at the edges of its dispatch rule
-(run_pool_step in pn_pagg.hip; Hk = the hidden size padded to a multiple of 32):
+(launch_pool_step in pn_pool.hip; Hk = the hidden size padded to a multiple of 32):
 
     PN_POOL_STEP = 1, W <= 40, 32 <= Hk <= 128, pool_step2_lds_bytes(10, Hk, C) <= 64 KiB   -> pool_step2_kernel<10, 2>
     otherwise, Hk <= 256                                                                     -> pool_step_kernel<4>
@@ -191,7 +191,7 @@ def test_pool_step_matches_the_fp64_oracle(name):
 
 
 def test_largest_walk_count_runs_and_the_next_is_refused():
-    """make_dims budgets the pooling kernels' LDS at 64 W + 48 H bytes <= 64 KiB: W = 928 at H = 128 is the largest W it
+    """make_dims budgets the pooling kernels' LDS (pool_lds_bytes, pn_pool.hip: 64 W + 48 H bytes) at 64 KiB: W = 928 at H = 128 is the largest W it
     accepts (step<4>, 64 KiB of LDS, in every mode) and matches the oracle; W = 929 is refused with PN_ERR_ARG."""
     from pathnet_amd import _lib
     run_all(Case("homo", S=3, W=928, H=128, C=5))

@@ -1,5 +1,5 @@
 """The two-stage weight-gradient GEMM of the bf16 x 3 arithmetic at hidden size 128 (pn_seq4.hip, context knob PN_SEQ4 bit 2,
-on by default in that mode) against the generic one (wgrad3_kernel, pn_pagg.hip) on the same module, inputs and dropout seed,
+on by default in that mode) against the generic one (wgrad3_kernel, pn_seq3.hip) on the same module, inputs and dropout seed,
 and against the CPU oracle.  It replaces autograd's weight gradient of nn.LSTM (/root/reference/PathNet_run.py:164,195,265,351):
 logits within 1e-5, gradients within 3e-5 of each tensor's largest element (tests/gradcheck.py).  (The 128-path forward and
 BPTT that shared the file were experiments that measured slower; removed in round 6, profiles/HISTORY_r1_r4.md.)"""

@@ -1,6 +1,6 @@
 """The recurrent kernels on the fp16 matrix pipe (pathnet_amd/csrc/pn_seqh.hip: three fp16 MFMAs over scaled two-plane
 splits per fp32 product; pn_pagg_shape.seq_math, the default) against
-  * the bf16 x 3 kernels of rounds 1-3 (pn_pagg.hip, seq_math = bf16x3) on the same module, inputs and dropout seed,
+  * the bf16 x 3 kernels of rounds 1-3 (pn_seq3.hip, seq_math = bf16x3) on the same module, inputs and dropout seed,
   * the CPU oracle (oracle/pagg_oracle.py, pinned against the reference classes) in fp32 and fp64,
 over every hidden size and cell the fused path has, and at the edges of fp16's range: recurrent weights of 1e-14 (the
 magnitudes weight decay leaves in saved_models/cornell.pth), gathered rows up to 1e4, upstream gradients scaled by 1e-8

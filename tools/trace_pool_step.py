@@ -1,6 +1,6 @@
 """Phase times inside pool_step2_kernel (the fused pooling step of a node), from a library built with -DPN_POOL_TRACE
-(pn_pagg.hip stamps wall_clock64 at eleven points of workgroup g's thread 0 into a device array, pn_debug_pool_trace copies it out):
-    hipcc ... -DPN_POOL_TRACE -c pn_pagg.hip ; link as pathnet_amd/csrc/_variants/lib_trace.so
+(pn_pool.hip stamps wall_clock64 at eleven points of workgroup g's thread 0 into a device array, pn_debug_pool_trace copies it out):
+    hipcc ... -DPN_POOL_TRACE -c pn_pool.hip ; link as pathnet_amd/csrc/_variants/lib_trace.so
     PN_LIB_PATH=pathnet_amd/csrc/_variants/lib_trace.so python tools/trace_pool_step.py [workload]
 Prints, over the launch's workgroups: the median / p90 duration of every phase (100 MHz ticks -> us), the median start offset of
 a workgroup from the launch's first stamp, and the launch's span."""
