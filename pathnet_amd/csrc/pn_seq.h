@@ -1,7 +1,8 @@
-// pn_seq.h -- launch parameters of the three recurrent kernels (forward recurrence, BPTT, weight gradient), shared by
-// pn_pagg.hip (which fills them), pn_seqh.hip (the fp16 x 2 kernels, the default), pn_seq3.hip (the bf16 x 3 kernels for every
-// hidden size up to 256), pn_seq4.hip (the bf16 x 3 weight-gradient GEMM of the headline shape) and pn_seqgen.hip (the mean /
-// sum encoders and the step-by-step recurrence above 256).  Not part of the ABI.
+// pn_seq.h -- launch parameters and launchers of the three recurrent kernels (forward recurrence, BPTT, weight gradient): the
+// interface between pn_pagg.hip (which fills the parameters) and pn_seqh.hip (the fp16 x 2 kernels, the default), pn_seq3.hip
+// (the bf16 x 3 kernels for every hidden size up to 256), pn_seq4.hip (the bf16 x 3 weight-gradient GEMM of the headline shape)
+// and pn_seqgen.hip (the mean / sum encoders and the step-by-step recurrence above 256).  What those kernel files share on the
+// device side -- cell functions, packing sources, tile description -- and their launch glue: pn_seq_core.h.  Not part of the ABI.
 #pragma once
 #include <cstdint>
 

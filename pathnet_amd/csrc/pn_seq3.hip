@@ -6,7 +6,8 @@
 //   seq_bwd3_kernel   BPTT + the gather backward's atomic scatter        (autograd through the above, :348-351)
 //   wgrad3_kernel     [g_W_ih | g_W_hh] = dG^T . [x | h], K-split partials;  wgrad_reduce_kernel adds the partials of either
 //                     arithmetic in split order and hands out the caller's gate layout
-// Split out of pn_pagg.hip in round 6; the kernels are unchanged.  gfx950 only.
+// The cell functions, the packings' source half, the dropout pieces, the tile description (LDS layout) and the launch glue
+// are pn_seq_core.h's, shared with pn_seqh.hip and pn_seqgen.hip.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include "pn_internal.h"
 #include "pn_kernels.h"
 #include "pn_seq.h"
+#include "pn_seq_core.h"
 
 using namespace pn;
 
@@ -41,42 +43,23 @@ namespace {
 //   A operand: LDS holds the three planes of the tile [32][x_t | h_{t-1}] as bf16, row pitch 4H + 16 bytes
 //     (conflict-free ds_read_b128).  x is split when the gathered rows are committed, h in the cell update.
 // ================================================================================================
-// GRU (torch gate order r, z, n; n = tanh(W_in x + b_in + r * (W_hn h + b_hn))) rides on the four gate slots of the
-// LSTM kernels: slot 0 = r, 1 = z over [x | h] as usual, slot 2 = "nx" = W_in x + b_in (its h half of the weights is
-// zero), slot 3 = "nh" = W_hn h + b_hn (its x half is zero).  A quarter of the products multiplies zeros; in return
-// the recurrence, its BPTT and the weight-gradient GEMM are the LSTM's kernels with another cell function.
+// GRU rides on the four gate slots of the LSTM kernels (pn_seq_core.h: gru_fwd).
 
 __global__ void pack_fwd3_kernel(const float *__restrict__ w_ih, const float *__restrict__ w_hh,
                                  const float *__restrict__ b_ih, const float *__restrict__ b_hh, int H, int G, int gru,
                                  u32x4 *__restrict__ Wp, float *__restrict__ biasc) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < G * H) {
-        if (!gru) {
-            biasc[idx] = b_ih[idx] + b_hh[idx];
-        } else {
-            const int slot = idx / H, j = idx - slot * H, wr = gru_weight_row(slot, j, H);
-            biasc[idx] = slot < 2 ? b_ih[wr] + b_hh[wr] : slot == 2 ? b_ih[wr] : b_hh[wr];
-        }
-    }
-    const int KS = H / 8, NW = H / 32;
-    if (idx >= NW * KS * G * 64) return;
-    const int lane = idx & 63;
-    int rest = idx >> 6;
-    const int g = rest % G;
-    rest /= G;
-    const int s = rest % KS, w = rest / KS;
-    const int j = 32 * w + (lane & 31), k = 16 * s + 8 * (lane >> 5);
-    const int row = gru ? gru_weight_row(g, j, H) : g * H + j;
-    const float *src = k < H ? w_ih + (int64_t)row * H + k : w_hh + (int64_t)row * H + (k - H);
-    float4 v0 = reinterpret_cast<const float4 *>(src)[0], v1 = reinterpret_cast<const float4 *>(src)[1];
-    if (gru && ((g == 2 && k >= H) || (g == 3 && k < H))) v0 = v1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (idx < G * H) biasc[idx] = packed_bias(b_ih, b_hh, idx, H, gru);
+    if (idx >= pack_fwd_count(H, G)) return;
+    const PackFwdSrc f = pack_fwd_src(idx, w_ih, w_hh, H, G, gru);
+    const float4 v0 = f.v0, v1 = f.v1;
     u32x4 q0, q1, q2;
     uint32_t x0, x1, x2;
     split3(v0.x, v0.y, x0, x1, x2); q0[0] = x0; q1[0] = x1; q2[0] = x2;
     split3(v0.z, v0.w, x0, x1, x2); q0[1] = x0; q1[1] = x1; q2[1] = x2;
     split3(v1.x, v1.y, x0, x1, x2); q0[2] = x0; q1[2] = x1; q2[2] = x2;
     split3(v1.z, v1.w, x0, x1, x2); q0[3] = x0; q1[3] = x1; q2[3] = x2;
-    u32x4 *dst = Wp + ((int64_t)(w * KS + s) * 3 * G + g) * 64 + lane;
+    u32x4 *dst = Wp + ((int64_t)f.unit * 3 * G + f.g) * 64 + f.lane;
     dst[0] = q0;
     dst[G * 64] = q1;
     dst[2 * G * 64] = q2;
@@ -87,23 +70,21 @@ __global__ void pack_fwd3_kernel(const float *__restrict__ w_ih, const float *__
 template <int H>
 constexpr int fwd_waves() { return H == 32 ? 1 : H > 128 ? 2 : PN_FWD_WAVES; }
 
-// GC: 4 = LSTM, 1 = tanh RNN, 3 = GRU (on the LSTM's four gate slots, see pack_fwd3_kernel)
+// GC: 4 = LSTM, 1 = tanh RNN, 3 = GRU (on the LSTM's four gate slots, pn_seq_core.h)
 template <int H, int GC>
 __global__ __launch_bounds__(H / 32 * 64, (fwd_waves<H>())) void seq_fwd3_kernel(SeqFwdParams p) {
-    constexpr int G = GC == 3 ? 4 : GC;
-    constexpr bool GRU = GC == 3;
-    constexpr int MT = 32;
-    constexpr int NW = H / 32, NT = NW * 64, SV = (G == 4 ? 5 : 1);
+    using T = SeqTile<H, GC, 3>;
+    constexpr int G = T::G, MT = T::MT, NW = T::NW, NT = T::NT, SV = T::SV;
+    constexpr bool GRU = T::GRU;
     constexpr int KS = H / 8, KX = KS / 2;    // k-steps of 16 over [x | h]; the first KX walk x
-    constexpr int PB = 4 * H + 16;            // row pitch of a plane of the tile [x | h], bytes: conflict-free ds_read_b128
-    constexpr int PLANE = MT * PB;
+    constexpr int PB = T::FWD_PB, PLANE = T::FWD_PLANE;     // row pitch of a plane of the tile [x | h] / plane size, bytes
     // three workgroups per CU (168 registers): no register room for the x_{t+1} rows or a second plane-0 fragment set,
     // the third workgroup covers those latencies instead
     constexpr bool PREFETCH_X = fwd_waves<H>() < 3, PING_PONG = PREFETCH_X;
     // LDS: three bf16 planes of the tile [MT][x_t | h_{t-1}] | row indices
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
-    int *s_rowidx = reinterpret_cast<int *>(ldsb + 3 * PLANE);  // [MT][L] gather rows of this tile
-    int *s_slotof = s_rowidx + MT * p.L;                        // [MT]
+    int *s_rowidx = T::fwd_rowidx(ldsb);                        // [MT][L] gather rows of this tile
+    int *s_slotof = T::fwd_slotof(ldsb, p.L);                   // [MT]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31;
     // column slice / first tile row of this wave.  A workgroup is NW waves, so ws == wave and r0 == 0 at run time; the compiler
     // does not bound threadIdx by the launch bounds and computes both.  Folding them by hand changes the generated code of every
@@ -157,8 +138,7 @@ __global__ __launch_bounds__(H / 32 * 64, (fwd_waves<H>())) void seq_fwd3_kernel
                 const int idx = tid_g + NT * i;
                 const int row = idx / (H / 4), c4 = idx - row * (H / 4);
                 const float4 m = dropout4(seed, ((uint64_t)t * p.Pmask + s_slotof[row]) * (H / 4) + c4, 1u, p.p_drop);
-                bits |= ((m.x != 0.f ? 1u : 0u) | (m.y != 0.f ? 2u : 0u) | (m.z != 0.f ? 4u : 0u) |
-                         (m.w != 0.f ? 8u : 0u)) << (4 * i);
+                bits |= keep_nibble(m) << (4 * i);
             }
         }
         asm volatile("" : "+v"(bits));      // drawn here, not sunk to the commit
@@ -180,6 +160,7 @@ __global__ __launch_bounds__(H / 32 * 64, (fwd_waves<H>())) void seq_fwd3_kernel
                     v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
                 }
             } else if (builtin_drop) {
+                // (written out here and in the other arithmetic's forward, not shared: profiles/seq_core.txt)
                 const uint32_t b = keepbits >> (4 * i);
                 v.x = b & 1u ? v.x * keep_scale : 0.0f;
                 v.y = b & 2u ? v.y * keep_scale : 0.0f;
@@ -296,33 +277,25 @@ __global__ __launch_bounds__(H / 32 * 64, (fwd_waves<H>())) void seq_fwd3_kernel
             const int q = q0 + row;
             float h;
             if (GRU) {
-                // saved: r, z, n, the pre-activation W_hn h + b_hn, h_{t-1}
-                const float rg = sigmoidf_(acc[0][r]);
-                const float zg = sigmoidf_(acc[G > 1 ? 1 : 0][r]);
-                const float nh = acc[G > 3 ? 3 : 0][r];
-                const float ng = tanhf_(acc[G > 2 ? 2 : 0][r] + rg * nh);
                 const float hp = cst[r];
-                h = (1.0f - zg) * ng + zg * hp;
+                const GruFwd c = gru_fwd(acc[0][r], acc[G > 1 ? 1 : 0][r], acc[G > 2 ? 2 : 0][r], acc[G > 3 ? 3 : 0][r], hp);
+                h = c.h;
                 cst[r] = h;
                 if (saved_t && q < p.P) {
                     float *sv = &at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)(SV * H) + col) * 4u);
-                    sv[0] = rg; sv[H] = zg; sv[2 * H] = ng; sv[3 * H] = nh; sv[4 * H] = hp;
+                    sv[0] = c.rg; sv[H] = c.zg; sv[2 * H] = c.ng; sv[3 * H] = c.nh; sv[4 * H] = hp;
                 }
             } else if (G == 4) {
-                const float ig = sigmoidf_(acc[0][r]);
-                const float fg = sigmoidf_(acc[G > 1 ? 1 : 0][r]);
-                const float gg = tanhf_(acc[G > 2 ? 2 : 0][r]);
-                const float og = sigmoidf_(acc[G > 3 ? 3 : 0][r]);
-                const float c = fg * cst[r] + ig * gg;
-                cst[r] = c;
-                h = og * tanhf_(c);
+                const LstmFwd c = lstm_fwd(acc[0][r], acc[G > 1 ? 1 : 0][r], acc[G > 2 ? 2 : 0][r], acc[G > 3 ? 3 : 0][r], cst[r]);
+                cst[r] = c.c;
+                h = c.h;
                 if (saved_t && q < p.P) {
                     // (constant displacements on top of base + zext(offset) fold into the instructions' immediates)
                     float *sv = &at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)(SV * H) + col) * 4u);
-                    sv[0] = ig; sv[H] = fg; sv[2 * H] = gg; sv[3 * H] = og; sv[4 * H] = c;
+                    sv[0] = c.ig; sv[H] = c.fg; sv[2 * H] = c.gg; sv[3 * H] = c.og; sv[4 * H] = c.c;
                 }
             } else {
-                h = tanhf_(acc[0][r]);
+                h = rnn_fwd(acc[0][r]);
                 if (saved_t && q < p.P) at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)H + col) * 4u) = h;
             }
             hv[r] = h;
@@ -379,17 +352,7 @@ __global__ void pack_bwd3_kernel(const float *__restrict__ w_ih, const float *__
     const int kk = f >> 1, nt = f & 1;
     const int k = 32 * u + 16 * kk + 8 * (lane >> 5), n = 32 * w + (lane & 31);
     float v[8];
-    if (!gru) {
-        const float *src = (nt == 0 ? w_ih : w_hh) + (int64_t)k * H + n;
-#pragma unroll
-        for (int e = 0; e < 8; e++) v[e] = src[(int64_t)e * H];
-    } else {        // k .. k+7 lie inside one gate slot (8 | H)
-        const int slot = k / H, j = k - slot * H;
-        const bool zero = (slot == 2 && nt == 1) || (slot == 3 && nt == 0);
-        const float *src = (nt == 0 ? w_ih : w_hh) + (int64_t)gru_weight_row(slot, j, H) * H + n;
-#pragma unroll
-        for (int e = 0; e < 8; e++) v[e] = zero ? 0.0f : src[(int64_t)e * H];
-    }
+    pack_bwd_src(k, n, nt, w_ih, w_hh, H, gru, v);
     u32x4 q0, q1, q2;
 #pragma unroll
     for (int h = 0; h < 4; h++) {
@@ -405,19 +368,18 @@ __global__ void pack_bwd3_kernel(const float *__restrict__ w_ih, const float *__
 
 template <int H, int GC>
 __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWD_WAVES) void seq_bwd3_kernel(SeqBwdParams p) {
-    constexpr int G = GC == 3 ? 4 : GC;         // GC: 4 = LSTM, 1 = tanh RNN, 3 = GRU on the LSTM's four gate slots
-    constexpr bool GRU = GC == 3;
-    constexpr int MT = 32, NW = H / 32;
-    constexpr int NT = NW * 64, GH = G * H, SV = (G == 4 ? 5 : 1);
-    constexpr int NPASS = G == 4 ? 2 : 1, KP = GH / NPASS;      // K extent of one pass (one gate pair)
-    constexpr int PB = 2 * KP + 16, PLANE = MT * PB;            // plane row pitch / plane size, bytes
+    using T = SeqTile<H, GC, 3>;                // GC: 4 = LSTM, 1 = tanh RNN, 3 = GRU on the LSTM's four gate slots
+    constexpr int G = T::G, MT = T::MT, NW = T::NW, NT = T::NT, GH = T::GH, SV = T::SV;
+    constexpr bool GRU = T::GRU;
+    constexpr int NPASS = T::NPASS;                             // passes of the k loop, one gate pair each
+    constexpr int PB = T::BWD_PB, PLANE = T::BWD_PLANE;         // plane row pitch / plane size, bytes
     constexpr int NU = GH / 32, NUP = NU / NPASS;               // units of two k-steps, total / per pass
     constexpr int NB = 16;              // accumulator elements per batch of saved-gate loads: all 16, one memory round trip per step
     constexpr bool CARRY_C = false;     // true: c_t stays in registers from one step to the next (16 registers the kernel does not have)
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
-    int *s_rowidx = reinterpret_cast<int *>(ldsb + 3 * PLANE);   // [MT][L] gather rows of this tile
-    int *s_slotof = s_rowidx + MT * p.L;                         // [MT]
-    uint8_t *s_keep = reinterpret_cast<uint8_t *>(s_slotof + MT); // [2][MT][H/4] dropout keep bits of step t (t & 1)
+    int *s_rowidx = T::bwd_rowidx(ldsb);                        // [MT][L] gather rows of this tile
+    int *s_slotof = T::bwd_slotof(ldsb, p.L);                   // [MT]
+    uint8_t *s_keep = T::bwd_keep(ldsb, p.L);                   // [2][MT][H/4] dropout keep bits of step t (t & 1)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31;
     const int ws = wave % NW, r0 = 32 * (wave / NW);             // column slice / first tile row of this wave (== wave, 0: seq_fwd3_kernel)
     // tiles in descending order -- the forward wrote the saved tensors of the last tiles last, they are the ones still in
@@ -510,41 +472,24 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWD_WAVES) void seq_b
                 const bool ok = row < rows_here;
                 float *d = &at_bytes(dG_t, (((uint32_t)min(row, rows_here - 1) * (uint32_t)p.L + t) * (uint32_t)GH + col) * 4u);
                 if (GRU) {
-                    // h = (1 - z) n + z h_prev,  n = tanh(nx + r nh):  gradients of the four slots r, z, nx, nh; the direct
-                    // path d h_t / d h_{t-1} = z is carried in dc[] across the GEMM and added to its dh output
-                    const float rg = vi[e], zg = vf[e], ng = vg[e], nh = vo[e], hp = vc[e];
-                    const float dhv = dh[r];
-                    const float dnp = dhv * (1.0f - zg) * (1.0f - ng * ng);
-                    float a_r = dnp * nh * rg * (1.0f - rg);
-                    float a_z = dhv * (hp - ng) * zg * (1.0f - zg);
-                    float a_nx = dnp;
-                    float a_nh = dnp * rg;
-                    if (!ok) a_r = a_z = a_nx = a_nh = 0.0f;
-                    dc[r] = ok ? dhv * zg : 0.0f;
-                    ai[e] = a_r; af[e] = a_z; ag[r] = a_nx; ao[r] = a_nh;
+                    // the direct path d h_t / d h_{t-1} = z is carried in dc[] across the GEMM and added to its dh output
+                    const CellGrad c = gru_bwd(vi[e], vf[e], vg[e], vo[e], vc[e], dh[r], ok);
+                    dc[r] = c.carry;
+                    ai[e] = c.a0; af[e] = c.a1; ag[r] = c.a2; ao[r] = c.a3;
                     if (ok) {
-                        d[0] = a_r; d[H] = a_z; d[2 * (G > 1 ? H : 0)] = a_nx; d[3 * (G > 1 ? H : 0)] = a_nh;
+                        d[0] = c.a0; d[H] = c.a1; d[2 * (G > 1 ? H : 0)] = c.a2; d[3 * (G > 1 ? H : 0)] = c.a3;
                     }
                 } else if (G == 4) {
-                    const float ig = vi[e], fg = vf[e], gg = vg[e], og = vo[e], cprev = vc[e];
-                    const float tc = tanhf_(vn[e]);
-                    const float dhv = dh[r];
-                    const float d_o = dhv * tc;
-                    const float dct = dc[r] + dhv * og * (1.0f - tc * tc);
-                    float a_i = dct * gg * ig * (1.0f - ig);
-                    float a_f = dct * cprev * fg * (1.0f - fg);
-                    float a_g = dct * ig * (1.0f - gg * gg);
-                    float a_o = d_o * og * (1.0f - og);
-                    if (!ok) a_i = a_f = a_g = a_o = 0.0f;
-                    dc[r] = dct * fg;
+                    const float cprev = vc[e];
+                    const CellGrad c = lstm_bwd(vi[e], vf[e], vg[e], vo[e], cprev, vn[e], dh[r], dc[r], ok);
+                    dc[r] = c.carry;
                     if (CARRY_C) cnext[r] = cprev;
-                    ai[e] = a_i; af[e] = a_f; ag[r] = a_g; ao[r] = a_o;
+                    ai[e] = c.a0; af[e] = c.a1; ag[r] = c.a2; ao[r] = c.a3;
                     if (ok) {
-                        d[0] = a_i; d[H] = a_f; d[2 * (G > 1 ? H : 0)] = a_g; d[3 * (G > 1 ? H : 0)] = a_o;
+                        d[0] = c.a0; d[H] = c.a1; d[2 * (G > 1 ? H : 0)] = c.a2; d[3 * (G > 1 ? H : 0)] = c.a3;
                     }
                 } else {
-                    const float h = vi[e];
-                    const float a = ok ? dh[r] * (1.0f - h * h) : 0.0f;
+                    const float a = rnn_bwd(vi[e], dh[r], ok);
                     ai[e] = a;
                     if (ok) d[0] = a;
                 }
@@ -671,7 +616,7 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWD_WAVES) void seq_b
                     if (p.mask)
                         dx *= p.mask[((uint64_t)t * p.Pmask + s_slotof[row]) * H + col];
                     else if (p.keep)
-                        dx = (s_keep[((t & 1) * MT + row) * (H / 4) + (col >> 2)] >> (col & 3)) & 1 ? dx * keep_scale : 0.0f;
+                        dx = keep_dx(dx, s_keep[((t & 1) * MT + row) * (H / 4) + (col >> 2)], col, keep_scale);
                 }
                 scr[rl * 33 + li_s] = dx;
             }
@@ -702,7 +647,7 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWD_WAVES) void seq_b
                     if (p.mask)
                         dx *= p.mask[((uint64_t)t * p.Pmask + s_slotof[row]) * H + col];
                     else if (p.keep)
-                        dx = (s_keep[((t & 1) * MT + row) * (H / 4) + (col >> 2)] >> (col & 3)) & 1 ? dx * keep_scale : 0.0f;
+                        dx = keep_dx(dx, s_keep[((t & 1) * MT + row) * (H / 4) + (col >> 2)], col, keep_scale);
                     atomicAdd(p.dZ + ((size_t)(uint32_t)s_rowidx[row * p.L + t] * (uint32_t)H + col), dx);
                 }
                 dh[r] = GRU ? acc[1][r] + dc[r] : acc[1][r];
@@ -933,63 +878,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
 }
 
 
-template <int H, int G>
-int launch_seq_bwd(pn_context *ctx, hipStream_t stream, const SeqBwdParams &sp) {
-    constexpr int MT = 32;
-    const size_t lds_bytes = (size_t)3 * MT * (2 * (G >= 3 ? 2 * H : H) + 16) + (size_t)(MT * sp.L + MT) * 4 +
-                             (size_t)2 * MT * (H / 4);      // (G = 3: GRU, on four gate slots)
-    auto kern = seq_bwd3_kernel<H, G>;
-    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), (int)lds_bytes)) return rc;
-    const int blocks = (sp.P + MT - 1) / MT;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(H / 32 * 64), lds_bytes, stream, sp);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
-}
-
-template <int G>
-int dispatch_seq_bwd(pn_context *ctx, hipStream_t stream, int H, const SeqBwdParams &sp) {
-    switch (H) {      // every multiple of 32 up to 256 (the LDS tile of H = 256 is 98 KB)
-        case 32: return launch_seq_bwd<32, G>(ctx, stream, sp);
-        case 64: return launch_seq_bwd<64, G>(ctx, stream, sp);
-        case 96: return launch_seq_bwd<96, G>(ctx, stream, sp);
-        case 128: return launch_seq_bwd<128, G>(ctx, stream, sp);
-        case 160: return launch_seq_bwd<160, G>(ctx, stream, sp);
-        case 192: return launch_seq_bwd<192, G>(ctx, stream, sp);
-        case 224: return launch_seq_bwd<224, G>(ctx, stream, sp);
-        case 256: return launch_seq_bwd<256, G>(ctx, stream, sp);
-    }
-    PN_FAIL(PN_ERR_ARG, "hidden size %d not supported", H);
-}
-
-template <int H, int G>
-int launch_seq_fwd(pn_context *ctx, hipStream_t stream, const SeqFwdParams &sp) {
-    constexpr int MT = 32;
-    const size_t lds_bytes = (size_t)3 * MT * (4 * H + 16) + (size_t)(MT * sp.L + MT) * 4;
-    auto kern = seq_fwd3_kernel<H, G>;
-    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), (int)lds_bytes)) return rc;
-    const int blocks = (sp.P + MT - 1) / MT;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(H / 32 * 64), lds_bytes, stream, sp);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
-}
-
-template <int G>
-int dispatch_seq_fwd(pn_context *ctx, hipStream_t stream, int H, const SeqFwdParams &sp) {
-    switch (H) {
-        case 32: return launch_seq_fwd<32, G>(ctx, stream, sp);
-        case 64: return launch_seq_fwd<64, G>(ctx, stream, sp);
-        case 96: return launch_seq_fwd<96, G>(ctx, stream, sp);
-        case 128: return launch_seq_fwd<128, G>(ctx, stream, sp);
-        case 160: return launch_seq_fwd<160, G>(ctx, stream, sp);
-        case 192: return launch_seq_fwd<192, G>(ctx, stream, sp);
-        case 224: return launch_seq_fwd<224, G>(ctx, stream, sp);
-        case 256: return launch_seq_fwd<256, G>(ctx, stream, sp);
-    }
-    PN_FAIL(PN_ERR_ARG, "hidden size %d not supported", H);
-}
-
-
-
 }  // namespace
 
 namespace pn {
@@ -1010,21 +898,22 @@ int launch_pack_bwd3(void *stream, const float *w_ih, const float *w_hh, int H, 
 }
 
 int launch_seq_fwd3(pn_context *ctx, void *stream, int H, int gc, const SeqFwdParams &sp) {
-    hipStream_t s = (hipStream_t)stream;
-    return gc == 3 ? dispatch_seq_fwd<3>(ctx, s, H, sp) : gc == 4 ? dispatch_seq_fwd<4>(ctx, s, H, sp) : dispatch_seq_fwd<1>(ctx, s, H, sp);
+    return dispatch_seq(H, gc, [&](auto h, auto g) {
+        using T = SeqTile<h.value, g.value, 3>;
+        return launch_seq_tiles<T>(ctx, stream, seq_fwd3_kernel<h.value, g.value>, T::fwd_lds_bytes(sp.L), sp);
+    });
 }
 
 int launch_seq_bwd3(pn_context *ctx, void *stream, int H, int gc, const SeqBwdParams &sp) {
-    hipStream_t s = (hipStream_t)stream;
-    return gc == 3 ? dispatch_seq_bwd<3>(ctx, s, H, sp) : gc == 4 ? dispatch_seq_bwd<4>(ctx, s, H, sp) : dispatch_seq_bwd<1>(ctx, s, H, sp);
+    return dispatch_seq(H, gc, [&](auto h, auto g) {
+        using T = SeqTile<h.value, g.value, 3>;
+        return launch_seq_tiles<T>(ctx, stream, seq_bwd3_kernel<h.value, g.value>, T::bwd_lds_bytes(sp.L), sp);
+    });
 }
 
 int launch_wgrad3(pn_context *ctx, void *stream, const WgradParams &wp, int nsplit) {
-    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(wgrad3_kernel), W3_LDS_BYTES)) return rc;
-    hipLaunchKernelGGL(wgrad3_kernel, dim3((wp.H2 + WG_BN - 1) / WG_BN, (wp.GH + WG_BM - 1) / WG_BM, nsplit), dim3(WG_THREADS),
-                       W3_LDS_BYTES, (hipStream_t)stream, wp);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
+    return launch_with_lds(ctx, stream, wgrad3_kernel, dim3((wp.H2 + WG_BN - 1) / WG_BN, (wp.GH + WG_BM - 1) / WG_BM, nsplit),
+                           dim3(WG_THREADS), W3_LDS_BYTES, wp);
 }
 
 int launch_wgrad_reduce(void *stream, const float *part_w, const float *part_b, int nsplit, int GH, int H, int accumulate, int gru,

@@ -1,11 +1,12 @@
 // pn_seqgen.hip -- the path encoders beside the fused recurrent kernels (pn_seqh.hip / pn_seq3.hip) on gfx950: the
 // order-agnostic mean / sum encoders of the ablation and the step-by-step recurrence for hidden sizes above 256.
-// Launch parameters and launchers: pn_seq.h.
+// Launch parameters and launchers: pn_seq.h; the cell functions and the bias / row maps of the packing: pn_seq_core.h.
 #include <hip/hip_runtime.h>
 
 #include "pn_internal.h"
 #include "pn_kernels.h"
 #include "pn_seq.h"
+#include "pn_seq_core.h"
 
 using namespace pn;
 
@@ -88,20 +89,19 @@ __global__ __launch_bounds__(256) void gen_cell_fwd_kernel(GenParams p) {
     float *sv = p.saved ? p.saved + (((size_t)q * p.L + p.t) * SV) * H + j : nullptr;
     float h;
     if (p.cell == 3) {                     // GRU on the four slots r, z, nx, nh
-        const float rg = sigmoidf_(pre[0]), zg = sigmoidf_(pre[H]), nh = pre[3 * (size_t)H];
-        const float ng = tanhf_(pre[2 * (size_t)H] + rg * nh);
+        const float pr = pre[0], pz = pre[H], pnh = pre[3 * (size_t)H], pnx = pre[2 * (size_t)H];
         const float hp = p.t > 0 ? p.state[i] : 0.0f;
-        h = (1.0f - zg) * ng + zg * hp;
+        const GruFwd c = gru_fwd(pr, pz, pnx, pnh, hp);
+        h = c.h;
         p.state[i] = h;
-        if (sv) { sv[0] = rg; sv[H] = zg; sv[2 * (size_t)H] = ng; sv[3 * (size_t)H] = nh; sv[4 * (size_t)H] = hp; }
+        if (sv) { sv[0] = c.rg; sv[H] = c.zg; sv[2 * (size_t)H] = c.ng; sv[3 * (size_t)H] = c.nh; sv[4 * (size_t)H] = hp; }
     } else if (p.G == 4) {                 // LSTM
-        const float ig = sigmoidf_(pre[0]), fg = sigmoidf_(pre[H]), gg = tanhf_(pre[2 * (size_t)H]), og = sigmoidf_(pre[3 * (size_t)H]);
-        const float c = fg * (p.t > 0 ? p.state[i] : 0.0f) + ig * gg;
-        p.state[i] = c;
-        h = og * tanhf_(c);
-        if (sv) { sv[0] = ig; sv[H] = fg; sv[2 * (size_t)H] = gg; sv[3 * (size_t)H] = og; sv[4 * (size_t)H] = c; }
+        const LstmFwd c = lstm_fwd(pre[0], pre[H], pre[2 * (size_t)H], pre[3 * (size_t)H], p.t > 0 ? p.state[i] : 0.0f);
+        p.state[i] = c.c;
+        h = c.h;
+        if (sv) { sv[0] = c.ig; sv[H] = c.fg; sv[2 * (size_t)H] = c.gg; sv[3 * (size_t)H] = c.og; sv[4 * (size_t)H] = c.c; }
     } else {                                // tanh RNN
-        h = tanhf_(pre[0]);
+        h = rnn_fwd(pre[0]);
         if (sv) sv[0] = h;
     }
     if (p.t == p.L - 1)
@@ -121,25 +121,17 @@ __global__ __launch_bounds__(256) void gen_cell_bwd_kernel(GenParams p) {
     const float dhv = p.dh[i];
     if (p.cell == 3) {
         const float rg = sv[0], zg = sv[H], ng = sv[2 * (size_t)H], nh = sv[3 * (size_t)H], hp = sv[4 * (size_t)H];
-        const float dnp = dhv * (1.0f - zg) * (1.0f - ng * ng);
-        d[0] = dnp * nh * rg * (1.0f - rg);
-        d[H] = dhv * (hp - ng) * zg * (1.0f - zg);
-        d[2 * (size_t)H] = dnp;
-        d[3 * (size_t)H] = dnp * rg;
-        p.state[i] = dhv * zg;              // the direct path d h_t / d h_{t-1}
+        const CellGrad c = gru_bwd(rg, zg, ng, nh, hp, dhv, true);
+        d[0] = c.a0; d[H] = c.a1; d[2 * (size_t)H] = c.a2; d[3 * (size_t)H] = c.a3;
+        p.state[i] = c.carry;               // the direct path d h_t / d h_{t-1}
     } else if (p.G == 4) {
-        const float ig = sv[0], fg = sv[H], gg = sv[2 * (size_t)H], og = sv[3 * (size_t)H], c = sv[4 * (size_t)H];
+        const float ig = sv[0], fg = sv[H], gg = sv[2 * (size_t)H], og = sv[3 * (size_t)H], ct = sv[4 * (size_t)H];
         const float cprev = p.t > 0 ? sv[-(ptrdiff_t)H] : 0.0f;       // slot 4 of step t-1
-        const float tc = tanhf_(c);
-        const float dct = (p.t < p.L - 1 ? p.state[i] : 0.0f) + dhv * og * (1.0f - tc * tc);
-        d[0] = dct * gg * ig * (1.0f - ig);
-        d[H] = dct * cprev * fg * (1.0f - fg);
-        d[2 * (size_t)H] = dct * ig * (1.0f - gg * gg);
-        d[3 * (size_t)H] = dhv * tc * og * (1.0f - og);
-        p.state[i] = dct * fg;
+        const CellGrad c = lstm_bwd(ig, fg, gg, og, cprev, ct, dhv, p.t < p.L - 1 ? p.state[i] : 0.0f, true);
+        d[0] = c.a0; d[H] = c.a1; d[2 * (size_t)H] = c.a2; d[3 * (size_t)H] = c.a3;
+        p.state[i] = c.carry;
     } else {
-        const float h = sv[0];
-        d[0] = dhv * (1.0f - h * h);
+        d[0] = rnn_bwd(sv[0], dhv, true);
     }
 }
 
@@ -167,19 +159,12 @@ __global__ __launch_bounds__(256) void gen_scatter_kernel(GenParams p) {
 }
 
 // Wcat [GH, 2H] = [W_ih | W_hh] in fp32 (GRU: the four slots with their zero halves) and its transpose, biasc as in
-// pack_fwd3_kernel
+// the fused kernels' packings (packed_bias)
 __global__ void gen_pack_kernel(const float *__restrict__ w_ih, const float *__restrict__ w_hh,
                                 const float *__restrict__ b_ih, const float *__restrict__ b_hh, int H, int G, int gru,
                                 float *__restrict__ Wcat, float *__restrict__ WcatT, float *__restrict__ biasc) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < (int64_t)G * H) {
-        if (!gru) {
-            biasc[i] = b_ih[i] + b_hh[i];
-        } else {
-            const int slot = (int)(i / H), j = (int)(i - (int64_t)slot * H), wr = gru_weight_row(slot, j, H);
-            biasc[i] = slot < 2 ? b_ih[wr] + b_hh[wr] : slot == 2 ? b_ih[wr] : b_hh[wr];
-        }
-    }
+    if (i < (int64_t)G * H) biasc[i] = packed_bias(b_ih, b_hh, i, H, gru);
     if (i >= (int64_t)G * H * 2 * H) return;
     const int m = (int)(i / (2 * H)), k = (int)(i - (int64_t)m * 2 * H), slot = m / H, j = m - slot * H;
     const int row = gru ? gru_weight_row(slot, j, H) : m;

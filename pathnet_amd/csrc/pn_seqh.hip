@@ -14,6 +14,8 @@
 // maxima in device memory (SeqRange) -- weights: range_part_kernel + pack_fb_kernel; gathered rows: range_rows_kernel over the bank's output;
 // the BPTT scales every tile of gate gradients by that tile's own maximum (computed in registers, exchanged through LDS
 // at the barrier the step needs anyway) and leaves the launch's maximum for the weight-gradient GEMM.
+// The cell functions, the packings' source half, the dropout pieces, the tile description (LDS layout) and the launch glue
+// are pn_seq_core.h's, shared with pn_seq3.hip and pn_seqgen.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -21,6 +23,7 @@
 
 #include "pn_kernels.h"
 #include "pn_seq.h"
+#include "pn_seq_core.h"
 
 using namespace pn;
 
@@ -173,47 +176,29 @@ __device__ __forceinline__ FwdScales fwd_scales(const SeqRange *rg, float xmul) 
 }
 
 
-__device__ __forceinline__ int gru_weight_row(int slot, int j, int H) { return (slot < 2 ? slot : 2) * H + j; }
-
 // =====================================================================================================================
 // forward recurrence
 //   Weights: pack_fwdh_body (pack_fb_kernel), B fragments of v_mfma_f32_32x32x16_f16,
 //     Wp[(((w*KS + s)*2 + plane)*G + g)*64 + lane] (16 bytes) =
 //         plane of 2^e Wcat[g*H + 32w + (lane & 31)][16 s + 8 (lane >> 5) .. +7],   KS = 2H/16 k-steps, e = e_ih | e_hh
 //   A operand: LDS holds the two planes of the tile [32][x_t | h_{t-1}], row pitch 4H + 16 bytes.
-//   GRU on the LSTM's four gate slots as in pn_seq3.hip (pack_fwd3_kernel).
+//   GRU on the LSTM's four gate slots (pn_seq_core.h: gru_fwd).
 // =====================================================================================================================
 __device__ __forceinline__ void pack_fwdh_body(int idx, const float *__restrict__ w_ih, const float *__restrict__ w_hh,
                                                const float *__restrict__ b_ih, const float *__restrict__ b_hh, int H, int G, int gru,
                                                float m_ih, float m_hh, u32x4 *__restrict__ Wp, float *__restrict__ biasc) {
-    if (idx < G * H) {
-        if (!gru) {
-            biasc[idx] = b_ih[idx] + b_hh[idx];
-        } else {
-            const int slot = idx / H, j = idx - slot * H, wr = gru_weight_row(slot, j, H);
-            biasc[idx] = slot < 2 ? b_ih[wr] + b_hh[wr] : slot == 2 ? b_ih[wr] : b_hh[wr];
-        }
-    }
-    const int KS = H / 8, NW = H / 32;
-    if (idx >= NW * KS * G * 64) return;
-    const int lane = idx & 63;
-    int rest = idx >> 6;
-    const int g = rest % G;
-    rest /= G;
-    const int s = rest % KS, w = rest / KS;
-    const int j = 32 * w + (lane & 31), k = 16 * s + 8 * (lane >> 5);
-    const int row = gru ? gru_weight_row(g, j, H) : g * H + j;
-    const float *src = k < H ? w_ih + (int64_t)row * H + k : w_hh + (int64_t)row * H + (k - H);
-    float4 v0 = reinterpret_cast<const float4 *>(src)[0], v1 = reinterpret_cast<const float4 *>(src)[1];
-    if (gru && ((g == 2 && k >= H) || (g == 3 && k < H))) v0 = v1 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float sc = exp2i(scale_exp(k < H ? m_ih : m_hh));
+    if (idx < G * H) biasc[idx] = packed_bias(b_ih, b_hh, idx, H, gru);
+    if (idx >= pack_fwd_count(H, G)) return;
+    const PackFwdSrc f = pack_fwd_src(idx, w_ih, w_hh, H, G, gru);
+    const float4 v0 = f.v0, v1 = f.v1;
+    const float sc = exp2i(scale_exp(f.xhalf ? m_ih : m_hh));
     u32x4 q0, q1;
     uint32_t x0, x1;
     split2h(v0.x * sc, v0.y * sc, x0, x1); q0[0] = x0; q1[0] = x1;
     split2h(v0.z * sc, v0.w * sc, x0, x1); q0[1] = x0; q1[1] = x1;
     split2h(v1.x * sc, v1.y * sc, x0, x1); q0[2] = x0; q1[2] = x1;
     split2h(v1.z * sc, v1.w * sc, x0, x1); q0[3] = x0; q1[3] = x1;
-    u32x4 *dst = Wp + ((int64_t)(w * KS + s) * 2 * G + g) * 64 + lane;
+    u32x4 *dst = Wp + ((int64_t)f.unit * 2 * G + f.g) * 64 + f.lane;
     dst[0] = q0;
     dst[G * 64] = q1;
 }
@@ -224,20 +209,19 @@ constexpr int fwdh_waves() { return H == 32 ? 1 : H > 128 ? 2 : PN_FWDH_WAVES; }
 // GC: 4 = LSTM, 1 = tanh RNN, 3 = GRU
 template <int H, int GC>
 __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H>())) void seq_fwdh_kernel(SeqFwdParams p) {
-    constexpr int G = GC == 3 ? 4 : GC;
-    constexpr bool GRU = GC == 3;
-    constexpr int MT = 32;
+    using T = SeqTile<H, GC, 2>;
+    constexpr int G = T::G, MT = T::MT, NT = T::NT;
+    constexpr bool GRU = T::GRU;
     constexpr bool PACKED = GC == 4;          // LSTM: {gates as 3 dwords (pack_gates), c_{t-1}}: 4 H dwords per path step
-    constexpr int NW = H / 32, NT = NW * 64, SV = PACKED ? 4 : (G == 4 ? 5 : 1);
+    constexpr int SV = PACKED ? 4 : T::SV;
     constexpr int KS = H / 8, KX = KS / 2;    // k-steps of 16 over [x | h]; the first KX walk x
-    constexpr int PB = 4 * H + 16;            // row pitch of a plane of the tile [x | h], bytes: conflict-free ds_read_b128
-    constexpr int PLANE = MT * PB;
+    constexpr int PB = T::FWD_PB, PLANE = T::FWD_PLANE;     // row pitch of a plane of the tile [x | h] / plane size, bytes
     // three workgroups per CU: no register room for the x_{t+1} rows or a second hi-plane fragment set, the third
     // workgroup covers those latencies instead (as in seq_fwd3_kernel)
     constexpr bool PREFETCH_X = fwdh_waves<H>() < 3, PING_PONG = PREFETCH_X;
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
-    int *s_rowidx = reinterpret_cast<int *>(ldsb + 2 * PLANE);  // [MT][L] gather rows of this tile
-    int *s_slotof = s_rowidx + MT * p.L;                        // [MT]
+    int *s_rowidx = T::fwd_rowidx(ldsb);                        // [MT][L] gather rows of this tile
+    int *s_slotof = T::fwd_slotof(ldsb, p.L);                   // [MT]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31;
     const int q0 = __builtin_amdgcn_readfirstlane((int)blockIdx.x * MT);
     const int rows_here = __builtin_amdgcn_readfirstlane(min(MT, p.P - q0));    // the last tile of a launch is ragged
@@ -282,8 +266,7 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H>())) void seq_fwdh_kerne
                 const int idx = tid_g + NT * i;
                 const int row = idx / (H / 4), c4 = idx - row * (H / 4);
                 const float4 m = dropout4(seed, ((uint64_t)t * p.Pmask + s_slotof[row]) * (H / 4) + c4, 1u, p.p_drop);
-                bits |= ((m.x != 0.f ? 1u : 0u) | (m.y != 0.f ? 2u : 0u) | (m.z != 0.f ? 4u : 0u) |
-                         (m.w != 0.f ? 8u : 0u)) << (4 * i);
+                bits |= keep_nibble(m) << (4 * i);
             }
         }
         asm volatile("" : "+v"(bits));      // drawn here, not sunk to the commit
@@ -305,6 +288,7 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H>())) void seq_fwdh_kerne
                     v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
                 }
             } else if (builtin_drop) {
+                // (written out here and in the other arithmetic's forward, not shared: profiles/seq_core.txt)
                 const uint32_t b = keepbits >> (4 * i);
                 v.x = b & 1u ? v.x * keep_scale : 0.0f;
                 v.y = b & 2u ? v.y * keep_scale : 0.0f;
@@ -407,36 +391,30 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H>())) void seq_fwdh_kerne
             const bool live = row < rows_here;
             float h;
             if (GRU) {
-                // saved: r, z, n, the pre-activation W_hn h + b_hn, h_{t-1}
-                const float rg = sigmoidf_(acc[0][r] * sc.inv_S);
-                const float zg = sigmoidf_(acc[G > 1 ? 1 : 0][r] * sc.inv_S);
-                const float nh = acc[G > 3 ? 3 : 0][r] * sc.inv_S;
-                const float ng = tanhf_(acc[G > 2 ? 2 : 0][r] * sc.inv_S + rg * nh);
                 const float hp = cst[r];
-                h = (1.0f - zg) * ng + zg * hp;
+                const GruFwd c = gru_fwd(acc[0][r] * sc.inv_S, acc[G > 1 ? 1 : 0][r] * sc.inv_S, acc[G > 2 ? 2 : 0][r] * sc.inv_S,
+                                         acc[G > 3 ? 3 : 0][r] * sc.inv_S, hp);
+                h = c.h;
                 cst[r] = h;
                 if (saved_t && live) {
                     float *sv = &at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)(SV * H) + col) * 4u);
-                    sv[0] = rg; sv[H] = zg; sv[2 * H] = ng; sv[3 * H] = nh; sv[4 * H] = hp;
+                    sv[0] = c.rg; sv[H] = c.zg; sv[2 * H] = c.ng; sv[3 * H] = c.nh; sv[4 * H] = hp;
                 }
             } else if (G == 4) {
-                const float ig = sigmoidf_(acc[0][r] * sc.inv_S);
-                const float fg = sigmoidf_(acc[G > 1 ? 1 : 0][r] * sc.inv_S);
-                const float gg = tanhf_(acc[G > 2 ? 2 : 0][r] * sc.inv_S);
-                const float og = sigmoidf_(acc[G > 3 ? 3 : 0][r] * sc.inv_S);
                 const float cprev = cst[r];
-                const float c = fg * cprev + ig * gg;
-                cst[r] = c;
-                h = og * tanhf_(c);
+                const LstmFwd c = lstm_fwd(acc[0][r] * sc.inv_S, acc[G > 1 ? 1 : 0][r] * sc.inv_S, acc[G > 2 ? 2 : 0][r] * sc.inv_S,
+                                           acc[G > 3 ? 3 : 0][r] * sc.inv_S, cprev);
+                cst[r] = c.c;
+                h = c.h;
                 if (saved_t && live) {
                     const uint32_t base = ((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)(SV * H);
                     // what the BPTT needs of this path step and unit as ONE 16-byte quad: {packed gates (3 dwords), c_{t-1}}
-                    const uint3 pk = pack_gates(ig, fg, gg, og);
+                    const uint3 pk = pack_gates(c.ig, c.fg, c.gg, c.og);
                     *reinterpret_cast<uint4 *>(&at_bytes(saved_t, (base + 4u * col) * 4u)) =
                         make_uint4(pk.x, pk.y, pk.z, __float_as_uint(cprev));
                 }
             } else {
-                h = tanhf_(acc[0][r] * sc.inv_S);
+                h = rnn_fwd(acc[0][r] * sc.inv_S);
                 if (saved_t && live) at_bytes(saved_t, (((uint32_t)row * (uint32_t)p.L + t) * (uint32_t)H + col) * 4u) = h;
             }
             hv[r] = h;
@@ -483,14 +461,14 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H>())) void seq_fwdh_kerne
 // =====================================================================================================================
 template <int H, int GC>
 __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H>())) void seq_fwdzw_kernel(SeqFwdParams p) {
-    constexpr int G = GC == 3 ? 4 : GC;
-    constexpr bool GRU = GC == 3;
-    constexpr int MT = 32, NW = H / 32, NT = NW * 64, GH = G * H;
+    using T = SeqTile<H, GC, 2>;
+    constexpr int G = T::G, MT = T::MT, NT = T::NT, GH = T::GH;
+    constexpr bool GRU = T::GRU;
     constexpr int KS = H / 8, KX = KS / 2, KH = KS - KX;      // k-steps of 16 over [x | h]: the last KH walk h
-    constexpr int PB = 2 * H + 16, PLANE = MT * PB;           // the tile holds h_{t-1} only
+    constexpr int PB = T::ZW_PB, PLANE = T::ZW_PLANE;         // the tile holds h_{t-1} only
     constexpr bool PING_PONG = fwdh_waves<H>() < 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
-    int *s_rowidx = reinterpret_cast<int *>(ldsb + 2 * PLANE);  // [MT][L] gather rows of this tile
+    int *s_rowidx = T::zw_rowidx(ldsb);                         // [MT][L] gather rows of this tile
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31;
     const int q0 = blockIdx.x * MT;
     const int col = 32 * wave + li;
@@ -566,22 +544,16 @@ __global__ __launch_bounds__(H / 32 * 64, (fwdh_waves<H>())) void seq_fwdzw_kern
         for (int r = 0; r < 16; r++) {
             float h;
             if (GRU) {
-                const float rg = sigmoidf_(acc[0][r] * sc.inv_S);
-                const float zg = sigmoidf_(acc[G > 1 ? 1 : 0][r] * sc.inv_S);
-                const float nh = acc[G > 3 ? 3 : 0][r] * sc.inv_S;
-                const float ng = tanhf_(acc[G > 2 ? 2 : 0][r] * sc.inv_S + rg * nh);
-                h = (1.0f - zg) * ng + zg * cst[r];
+                h = gru_fwd(acc[0][r] * sc.inv_S, acc[G > 1 ? 1 : 0][r] * sc.inv_S, acc[G > 2 ? 2 : 0][r] * sc.inv_S,
+                            acc[G > 3 ? 3 : 0][r] * sc.inv_S, cst[r]).h;
                 cst[r] = h;
             } else if (G == 4) {
-                const float ig = sigmoidf_(acc[0][r] * sc.inv_S);
-                const float fg = sigmoidf_(acc[G > 1 ? 1 : 0][r] * sc.inv_S);
-                const float gg = tanhf_(acc[G > 2 ? 2 : 0][r] * sc.inv_S);
-                const float og = sigmoidf_(acc[G > 3 ? 3 : 0][r] * sc.inv_S);
-                const float c = fg * cst[r] + ig * gg;
-                cst[r] = c;
-                h = og * tanhf_(c);
+                const LstmFwd c = lstm_fwd(acc[0][r] * sc.inv_S, acc[G > 1 ? 1 : 0][r] * sc.inv_S, acc[G > 2 ? 2 : 0][r] * sc.inv_S,
+                                           acc[G > 3 ? 3 : 0][r] * sc.inv_S, cst[r]);
+                cst[r] = c.c;
+                h = c.h;
             } else {
-                h = tanhf_(acc[0][r] * sc.inv_S);
+                h = rnn_fwd(acc[0][r] * sc.inv_S);
             }
             hv[r] = h;
             const int row = acc_row(r, lane_o);
@@ -622,17 +594,7 @@ __device__ __forceinline__ void pack_bwdh_body(int idx, const float *__restrict_
     const int kk = f >> 1, nt = f & 1;
     const int k = 32 * u + 16 * kk + 8 * (lane >> 5), n = 32 * w + (lane & 31);
     float v[8];
-    if (!gru) {
-        const float *src = (nt == 0 ? w_ih : w_hh) + (int64_t)k * H + n;
-#pragma unroll
-        for (int e = 0; e < 8; e++) v[e] = src[(int64_t)e * H];
-    } else {        // k .. k+7 lie inside one gate slot (8 | H)
-        const int slot = k / H, j = k - slot * H;
-        const bool zero = (slot == 2 && nt == 1) || (slot == 3 && nt == 0);
-        const float *src = (nt == 0 ? w_ih : w_hh) + (int64_t)gru_weight_row(slot, j, H) * H + n;
-#pragma unroll
-        for (int e = 0; e < 8; e++) v[e] = zero ? 0.0f : src[(int64_t)e * H];
-    }
+    pack_bwd_src(k, n, nt, w_ih, w_hh, H, gru, v);
     const float sc = exp2i(scale_exp(nt == 0 ? m_ih : m_hh));
     u32x4 q0, q1;
 #pragma unroll
@@ -667,19 +629,19 @@ __global__ __launch_bounds__(256) void pack_fb_kernel(const float *__restrict__ 
 
 template <int H, int GC>
 __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWDH_WAVES) void seq_bwdh_kernel(SeqBwdParams p) {
-    constexpr int G = GC == 3 ? 4 : GC;         // GC: 4 = LSTM, 1 = tanh RNN, 3 = GRU on the LSTM's four gate slots
-    constexpr bool GRU = GC == 3;
-    constexpr int MT = 32, NW = H / 32;
+    using T = SeqTile<H, GC, 2>;                // GC: 4 = LSTM, 1 = tanh RNN, 3 = GRU on the LSTM's four gate slots
+    constexpr int G = T::G, MT = T::MT, NW = T::NW, NT = T::NT, GH = T::GH;
+    constexpr bool GRU = T::GRU;
     constexpr bool PACKED = GC == 4;                            // (the forward's layout: pack_gates quads)
-    constexpr int NT = NW * 64, GH = G * H, SV = PACKED ? 4 : (G == 4 ? 5 : 1);
-    constexpr int PB = 2 * GH + 16, PLANE = MT * PB;            // plane row pitch / plane size, bytes
+    constexpr int SV = PACKED ? 4 : T::SV;
+    constexpr int PB = T::BWD_PB, PLANE = T::BWD_PLANE;         // plane row pitch / plane size, bytes (all gates resident)
     constexpr int NU = GH / 32;                                 // units of two k-steps
     extern __shared__ __attribute__((aligned(16))) unsigned char ldsb[];
-    int *s_rowidx = reinterpret_cast<int *>(ldsb + 2 * PLANE);   // [L][MT] gather rows of this tile, step-major: the four
+    int *s_rowidx = T::bwd_rowidx(ldsb);                         // [L][MT] gather rows of this tile, step-major: the four
                                                                  // consecutive rows of an accumulator quad are one 16-byte read
-    int *s_slotof = s_rowidx + MT * p.L;                         // [MT]
-    float *s_max = reinterpret_cast<float *>(s_slotof + MT);     // [8] wave maxima of |dG_t|
-    uint8_t *s_keep = reinterpret_cast<uint8_t *>(s_max + 8);    // [2][MT][H/4] dropout keep bits of step t (t & 1)
+    int *s_slotof = T::bwd_slotof(ldsb, p.L);                    // [MT]
+    float *s_max = T::bwd_smax(ldsb, p.L);                       // [8] wave maxima of |dG_t|
+    uint8_t *s_keep = T::bwd_keep(ldsb, p.L);                    // [2][MT][H/4] dropout keep bits of step t (t & 1)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31;
     // (descending path order: the BPTT starts on the tiles the forward wrote last)
     const int q0 = __builtin_amdgcn_readfirstlane((int)(gridDim.x - 1 - blockIdx.x) * MT);
@@ -791,8 +753,8 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWDH_WAVES) void seq_
                 const bool ok = row < rows_here;
                 float *d = &at_bytes(dG_t, (((uint32_t)min(row, rows_here - 1) * (uint32_t)p.L + t) * (uint32_t)GH + col) * 4u);
                 if (GRU) {
-                    // h = (1 - z) n + z h_prev,  n = tanh(nx + r nh):  gradients of the four slots r, z, nx, nh; the direct
-                    // path d h_t / d h_{t-1} = z is carried in dc[] across the GEMM and added to its dh output
+                    // the direct path d h_t / d h_{t-1} = z is carried in dc[] across the GEMM and added to its dh output
+                    // (gru_bwd of pn_seq_core.h, written out in this kernel alone: profiles/seq_core.txt)
                     const float rg = vi_, zg = vf_, ng = vg_, nh = vo_, hp = vc_;
                     const float dhv = dh[r];
                     const float dnp = dhv * (1.0f - zg) * (1.0f - ng * ng);
@@ -806,24 +768,15 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWDH_WAVES) void seq_
                     if (ok) d[0] = a_r, d[H] = a_z, d[2 * (G > 1 ? H : 0)] = a_nx, d[3 * (G > 1 ? H : 0)] = a_nh;
                     vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(a_r), fabsf(a_z))), fmaxf(fabsf(a_nx), fabsf(a_nh)));
                 } else if (G == 4) {
-                    const float ig = vi_, fg = vf_, gg = vg_, og = vo_, cprev = vc_;
-                    const float tc = tanhf_(vn_);
-                    const float dhv = dh[r];
-                    const float d_o = dhv * tc;
-                    const float dct = dc[r] + dhv * og * (1.0f - tc * tc);
-                    float a_i = dct * gg * ig * (1.0f - ig);
-                    float a_f = dct * cprev * fg * (1.0f - fg);
-                    float a_g = dct * ig * (1.0f - gg * gg);
-                    float a_o = d_o * og * (1.0f - og);
-                    if (!ok) a_i = a_f = a_g = a_o = 0.0f;
-                    dc[r] = dct * fg;
+                    const float cprev = vc_;
+                    const CellGrad c = lstm_bwd(vi_, vf_, vg_, vo_, cprev, vn_, dh[r], dc[r], ok);
+                    dc[r] = c.carry;
                     cnext[r] = cprev;
-                    dgv[0][r] = a_i; dgv[G > 1 ? 1 : 0][r] = a_f; dgv[G > 2 ? 2 : 0][r] = a_g; dgv[G > 3 ? 3 : 0][r] = a_o;
-                    if (ok) d[0] = a_i, d[H] = a_f, d[2 * (G > 1 ? H : 0)] = a_g, d[3 * (G > 1 ? H : 0)] = a_o;
-                    vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(a_i), fabsf(a_f))), fmaxf(fabsf(a_g), fabsf(a_o)));
+                    dgv[0][r] = c.a0; dgv[G > 1 ? 1 : 0][r] = c.a1; dgv[G > 2 ? 2 : 0][r] = c.a2; dgv[G > 3 ? 3 : 0][r] = c.a3;
+                    if (ok) d[0] = c.a0, d[H] = c.a1, d[2 * (G > 1 ? H : 0)] = c.a2, d[3 * (G > 1 ? H : 0)] = c.a3;
+                    vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(c.a0), fabsf(c.a1))), fmaxf(fabsf(c.a2), fabsf(c.a3)));
                 } else {
-                    const float h = vi_;
-                    const float a = ok ? dh[r] * (1.0f - h * h) : 0.0f;
+                    const float a = rnn_bwd(vi_, dh[r], ok);
                     dgv[0][r] = a;
                     if (ok) d[0] = a;
                     vmax = fmaxf(vmax, fabsf(a));
@@ -953,7 +906,7 @@ __global__ __launch_bounds__(H / 32 * 64, H == 32 ? 1 : PN_BWDH_WAVES) void seq_
             for (int r = 0; r < 16; r++) {
                 float dx = acc[0][r] * inv_x;
                 if constexpr (MODE == 1) dx *= mv[r];
-                if constexpr (MODE == 2) dx = (kb[r] >> (col_t & 3)) & 1 ? dx * keep_scale : 0.0f;
+                if constexpr (MODE == 2) dx = keep_dx(dx, kb[r], col_t, keep_scale);
                 dxv[r] = acc_row(r, lane_t) < rows_here ? dx : 0.0f;
             }
         };
@@ -1178,84 +1131,6 @@ __global__ __launch_bounds__(WH_THREADS, 2) void wgradh_kernel(WgradParams p, in
             (fl[tid] + fl[WH_BM + tid]) + (fl[2 * WH_BM + tid] + fl[3 * WH_BM + tid]);
 }
 
-template <int H, int GC>
-int launch_fwdh_t(pn_context *ctx, hipStream_t stream, const SeqFwdParams &sp) {
-    constexpr int MT = 32;
-    const size_t lds_bytes = (size_t)2 * MT * (4 * H + 16) + (size_t)(MT * sp.L + MT) * 4;
-    auto kern = seq_fwdh_kernel<H, GC>;
-    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), (int)lds_bytes)) return rc;
-    hipLaunchKernelGGL(kern, dim3((sp.P + MT - 1) / MT), dim3(H / 32 * 64), lds_bytes, stream, sp);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
-}
-template <int H, int GC>
-constexpr size_t bwdh_lds_bytes(int L) {
-    constexpr int MT = 32, G = GC == 3 ? 4 : GC;
-    return (size_t)2 * MT * (2 * G * H + 16) + (size_t)(MT * L + MT) * 4 + 32 + (size_t)2 * MT * (H / 4);
-}
-template <int H, int GC>
-int launch_bwdh_t(pn_context *ctx, hipStream_t stream, const SeqBwdParams &sp) {
-    constexpr int MT = 32;
-    const size_t lds_bytes = bwdh_lds_bytes<H, GC>(sp.L);
-    auto kern = seq_bwdh_kernel<H, GC>;
-    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), (int)lds_bytes)) return rc;
-    hipLaunchKernelGGL(kern, dim3((sp.P + MT - 1) / MT), dim3(H / 32 * 64), lds_bytes, stream, sp);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
-}
-template <int H, int GC>
-int launch_fwdzw_t(pn_context *ctx, hipStream_t stream, const SeqFwdParams &sp) {
-    constexpr int MT = 32;
-    const size_t lds_bytes = (size_t)2 * MT * (2 * H + 16) + (size_t)(MT * sp.L) * 4;
-    auto kern = seq_fwdzw_kernel<H, GC>;
-    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(kern), (int)lds_bytes)) return rc;
-    hipLaunchKernelGGL(kern, dim3((sp.P + MT - 1) / MT), dim3(H / 32 * 64), lds_bytes, stream, sp);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
-}
-template <int GC>
-int dispatch_fwdzw(pn_context *ctx, hipStream_t s, int H, const SeqFwdParams &sp) {
-    switch (H) {
-        case 32: return launch_fwdzw_t<32, GC>(ctx, s, sp);
-        case 64: return launch_fwdzw_t<64, GC>(ctx, s, sp);
-        case 96: return launch_fwdzw_t<96, GC>(ctx, s, sp);
-        case 128: return launch_fwdzw_t<128, GC>(ctx, s, sp);
-        case 160: return launch_fwdzw_t<160, GC>(ctx, s, sp);
-        case 192: return launch_fwdzw_t<192, GC>(ctx, s, sp);
-        case 224: return launch_fwdzw_t<224, GC>(ctx, s, sp);
-        case 256: return launch_fwdzw_t<256, GC>(ctx, s, sp);
-    }
-    PN_FAIL(PN_ERR_ARG, "hidden size %d not supported", H);
-}
-template <int GC>
-int dispatch_fwdh(pn_context *ctx, hipStream_t s, int H, const SeqFwdParams &sp) {
-    switch (H) {
-        case 32: return launch_fwdh_t<32, GC>(ctx, s, sp);
-        case 64: return launch_fwdh_t<64, GC>(ctx, s, sp);
-        case 96: return launch_fwdh_t<96, GC>(ctx, s, sp);
-        case 128: return launch_fwdh_t<128, GC>(ctx, s, sp);
-        case 160: return launch_fwdh_t<160, GC>(ctx, s, sp);
-        case 192: return launch_fwdh_t<192, GC>(ctx, s, sp);
-        case 224: return launch_fwdh_t<224, GC>(ctx, s, sp);
-        case 256: return launch_fwdh_t<256, GC>(ctx, s, sp);
-    }
-    PN_FAIL(PN_ERR_ARG, "hidden size %d not supported", H);
-}
-template <int GC>
-int dispatch_bwdh(pn_context *ctx, hipStream_t s, int H, const SeqBwdParams &sp) {
-    switch (H) {
-        case 32: return launch_bwdh_t<32, GC>(ctx, s, sp);
-        case 64: return launch_bwdh_t<64, GC>(ctx, s, sp);
-        case 96: return launch_bwdh_t<96, GC>(ctx, s, sp);
-        case 128: return launch_bwdh_t<128, GC>(ctx, s, sp);
-        case 160: return launch_bwdh_t<160, GC>(ctx, s, sp);
-        case 192: return launch_bwdh_t<192, GC>(ctx, s, sp);
-        case 224: return launch_bwdh_t<224, GC>(ctx, s, sp);
-        case 256: return launch_bwdh_t<256, GC>(ctx, s, sp);
-    }
-    PN_FAIL(PN_ERR_ARG, "hidden size %d not supported", H);
-}
-
 }  // namespace
 
 #if PN_TRACE_H
@@ -1294,29 +1169,32 @@ int launch_pack_fb(void *stream, const float *w_ih, const float *w_hh, const flo
 
 int launch_seq_fwdh(pn_context *ctx, void *stream, int H, int gc, const SeqFwdParams &sp) {
     if (!sp.range) PN_FAIL(PN_ERR_ARG, "seq_fwdh: operand ranges missing");
-    hipStream_t s = (hipStream_t)stream;
-    return gc == 3 ? dispatch_fwdh<3>(ctx, s, H, sp) : gc == 4 ? dispatch_fwdh<4>(ctx, s, H, sp) : dispatch_fwdh<1>(ctx, s, H, sp);
+    return dispatch_seq(H, gc, [&](auto h, auto g) {
+        using T = SeqTile<h.value, g.value, 2>;
+        return launch_seq_tiles<T>(ctx, stream, seq_fwdh_kernel<h.value, g.value>, T::fwd_lds_bytes(sp.L), sp);
+    });
 }
 
 int launch_seq_fwdzw(pn_context *ctx, void *stream, int H, int gc, const SeqFwdParams &sp) {
     if (!sp.range || !sp.ZW) PN_FAIL(PN_ERR_ARG, "seq_fwdzw: operand ranges / ZW missing");
-    hipStream_t s = (hipStream_t)stream;
-    return gc == 3 ? dispatch_fwdzw<3>(ctx, s, H, sp) : gc == 4 ? dispatch_fwdzw<4>(ctx, s, H, sp) : dispatch_fwdzw<1>(ctx, s, H, sp);
+    return dispatch_seq(H, gc, [&](auto h, auto g) {
+        using T = SeqTile<h.value, g.value, 2>;
+        return launch_seq_tiles<T>(ctx, stream, seq_fwdzw_kernel<h.value, g.value>, T::zw_lds_bytes(sp.L), sp);
+    });
 }
 
 int launch_seq_bwdh(pn_context *ctx, void *stream, int H, int gc, const SeqBwdParams &sp) {
     if (!sp.range) PN_FAIL(PN_ERR_ARG, "seq_bwdh: operand ranges missing");
-    hipStream_t s = (hipStream_t)stream;        // (range->dg was cleared by the forward's launch_pack_fb)
-    return gc == 3 ? dispatch_bwdh<3>(ctx, s, H, sp) : gc == 4 ? dispatch_bwdh<4>(ctx, s, H, sp) : dispatch_bwdh<1>(ctx, s, H, sp);
+    return dispatch_seq(H, gc, [&](auto h, auto g) {        // (range->dg was cleared by the forward's launch_pack_fb)
+        using T = SeqTile<h.value, g.value, 2>;
+        return launch_seq_tiles<T>(ctx, stream, seq_bwdh_kernel<h.value, g.value>, T::bwd_lds_bytes(sp.L), sp);
+    });
 }
 
 int launch_wgradh(pn_context *ctx, void *stream, const WgradParams &wp, int H, int nsplit) {
     if (!wp.range) PN_FAIL(PN_ERR_ARG, "wgradh: operand ranges missing");
-    if (int rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void *>(wgradh_kernel), WH_LDS_BYTES)) return rc;
-    hipLaunchKernelGGL(wgradh_kernel, dim3((wp.H2 + WH_BN - 1) / WH_BN, (wp.GH + WH_BM - 1) / WH_BM, nsplit), dim3(WH_THREADS),
-                       WH_LDS_BYTES, (hipStream_t)stream, wp, H);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
+    return launch_with_lds(ctx, stream, wgradh_kernel, dim3((wp.H2 + WH_BN - 1) / WH_BN, (wp.GH + WH_BM - 1) / WH_BM, nsplit),
+                           dim3(WH_THREADS), WH_LDS_BYTES, wp, H);
 }
 
 }  // namespace pn

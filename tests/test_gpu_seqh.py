@@ -131,6 +131,77 @@ def test_f16_kernels_match_the_oracle(variant, H):
     assert_grads_close(g, wg, zero_ok=ZERO_OK_HETERO if variant == "hetero" else ())
 
 
+_GRID = {}      # (H, cell) -> the case and its oracle results, computed once and shared by both arithmetics
+
+
+def _grid_case(H, cell):
+    if (H, cell) not in _GRID:
+        W, L = 5, 3
+        m, X, sel, ids, codes, ms, mc, G = _oracle_case("homo", H, 7, W, L, N=40, F=12, C=3, cell=cell)
+        params = {k: v.detach().cpu().clone().requires_grad_(True) for k, v in m.state_dict().items()}
+        want = po.forward("homo", params, X, ids, codes, sel, W, L, drop_seq=ms, drop_cls=mc, cell=cell)
+        want.backward(G)
+        wg = {k: params[k].grad for k, _ in m.named_parameters()}
+        with torch.no_grad():
+            want_eval = po.forward("homo", {k: v.detach() for k, v in params.items()}, X, ids, codes, sel, W, L, cell=cell)
+        _GRID[(H, cell)] = (m, X, sel, ids, codes, ms, mc, G, W, L), want.detach(), wg, want_eval
+    return _GRID[(H, cell)]
+
+
+def _bank_brackets(m, args, eval_zw):
+    """one inference forward with every stage bracketed: the logits and how many brackets the bank stage recorded.  The
+    pre-projected route adds one to the plain route's count, around the GEMM ZW = Z . W_ih^T + b (pn_pagg.hip, run_tables)"""
+    import ctypes
+    from pathnet_amd import _lib
+    lib, ctx = _lib.load(), _lib.context("cuda")
+    names = [lib.pn_profile_stage_name(i).decode() for i in range(lib.pn_profile_stage_count())]
+    ms, cnt = (ctypes.c_double * len(names))(), (ctypes.c_int64 * len(names))()
+    _lib.set_knob("PN_EVAL_ZW", eval_zw)
+    try:
+        _lib.check(lib.pn_profile_configure(ctx, 1, -1))
+        with torch.no_grad():
+            got = m(*args).clone()
+        torch.cuda.synchronize()
+        _lib.check(lib.pn_profile_read(ctx, ms, cnt))
+    finally:
+        _lib.check(lib.pn_profile_configure(ctx, 0, -1))
+        _lib.set_knob("PN_EVAL_ZW", 1)
+    return got.cpu(), cnt[names.index("bank")]
+
+
+@pytest.mark.parametrize("math", ["f16x2", "bf16x3"])
+@pytest.mark.parametrize("cell", ["lstm", "gru", "rnn"])
+@pytest.mark.parametrize("H", [32, 64, 96, 128, 160, 192, 224, 256])
+def test_every_fused_hidden_size_cell_and_arithmetic_against_the_oracle(H, cell, math, monkeypatch):
+    """the hidden-size dispatch and the tile description (pn_seq_core.h) of all five kernel families: training forward and
+    every gradient with explicit dropout masks, and the inference forward (seq_fwdzw_kernel under f16x2), against the CPU
+    oracle.  35 paths: one full tile of 32 and a ragged one of 3.
+    The inference forward runs with the touched-row compaction forced on: the table ZW must fit the slot of the saved gates
+    (use_zw, pn_pagg.hip), and the RNN's slot holds 105 rows -- the shape's path steps, which bound the compact bank -- not
+    the dense bank's 120.  Under f16x2 the route is checked, not assumed: the bank stage records one bracket more than
+    with PN_EVAL_ZW = 0."""
+    (m, X, sel, ids, codes, ms, mc, G, W, L), want, wg, want_eval = _grid_case(H, cell)
+    monkeypatch.delenv("PN_COMPACT", raising=False)
+    m.seq_math = math
+    m.train()
+    out, g = _hip(m, X, sel, ids, codes, ms, mc, G, W, L)
+    assert (out - want).abs().max().item() < 1e-5
+    assert_grads_close(g, wg)
+    S, N = len(sel), X.shape[0]
+    mask = np.zeros(N, bool)
+    mask[sel] = True
+    args = (X.cuda(), torch.as_tensor(ids.reshape(S, W * L).astype(np.int64)), W, L, mask, torch.as_tensor(codes.astype(np.int64)), None)
+    m.eval()
+    monkeypatch.setenv("PN_COMPACT", "1")
+    got, brackets = _bank_brackets(m, args, 1)
+    assert (got - want_eval).abs().max().item() < 1e-5
+    if math == "f16x2":
+        plain, brackets_plain = _bank_brackets(m, args, 0)
+        assert brackets == brackets_plain + 1, (brackets, brackets_plain)
+        assert (plain - want_eval).abs().max().item() < 1e-5
+        assert (got - plain).abs().max().item() <= 2e-6
+
+
 def _against_fp64(variant, m, X, sel, ids, codes, ms, mc, G, W, L, floor):
     """max |hip - fp64| per tensor must be within 8 x stock fp32 torch's own distance from fp64, or `floor` of |value|_inf"""
     out, g = _hip(m, X, sel, ids, codes, ms, mc, G, W, L)
