@@ -402,6 +402,15 @@ int pn_walk_stats(pn_context *ctx, int32_t n, int32_t W, int32_t L, int64_t rows
                   int32_t accumulate, const pn_walk_stats_out *out, void *workspace, int64_t workspace_bytes,
                   void *stream);
 
+/* Path multiplicities: mult[r, j] (dev fp32 [rows, W]) = the number of paths k of row r whose id sequence -- and code
+ * sequence, when codes is not NULL -- equals path j's, when j is the lowest such index; otherwise 0.  Every row sums to W
+ * exactly.  As pn_path_weights.weight with PN_PATH_NORM_SUM the result pools a row's distinct paths once each, weighted
+ * by how often they were drawn: the same value as the unweighted pooling of the row (HOMO / PAGG, where a row's entries are
+ * its own paths).  Limits as pn_walk_stats: 1 <= L <= 16, W >= 1, W * L <= 8192, rows >= 0, else PN_ERR_ARG; rows == 0
+ * launches nothing.  Asynchronous on `stream`: nothing is read back.  A new symbol: pn_abi_version keeps answering 12. */
+int pn_path_multiplicity(pn_context *ctx, int32_t W, int32_t L, int64_t rows, const int32_t *ids /* dev [rows, W, L] */,
+                         const uint8_t *codes /* dev [rows, W, L] or NULL */, float *mult /* dev [rows, W] */, void *stream);
+
 /* ---- transition probabilities and path likelihoods (pn_prob.hip): the walker's tables, evaluated --------------------
  * pn_sample_paths draws from the tables; this says how likely given paths are under them.  Added without an ABI bump: two
  * new symbols and one new struct, no existing struct or signature changed, so pn_abi_version keeps answering 12.
@@ -526,6 +535,9 @@ typedef struct pn_pagg_shape {
 #define PN_COMPACT_AUTO 0
 #define PN_COMPACT_ON 1
 #define PN_COMPACT_OFF 2
+/* pn_path_weights.norm */
+#define PN_PATH_NORM_SUM 0    /* the weights of a group are scaled to sum to W (integer weights = repeated paths) */
+#define PN_PATH_NORM_COUNT 1  /* the weights are applied as given: a group with fewer live paths pools less */
 #define PN_CELL_DEFAULT 0
 #define PN_CELL_LSTM 1
 #define PN_CELL_RNN 2
@@ -823,6 +835,43 @@ int pn_cross_entropy_ex(const float *logits, const int64_t *target, int32_t rows
  * reproducible with options as without. */
 int pn_pagg_train_step_loss(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *features /* may be NULL */,
                             const pn_loss_spec *spec, const int64_t *target, float *loss, void *stream);
+
+/* ---- per-path weights in the pooling (pn_pool.hip) --------------------------------------------------------------------
+ * The aggregators pool a node's W paths with fixed coefficients (pn_pagg_args.out_path_weight); a pn_path_weights lets the
+ * caller weigh every path, or leave paths out.  It travels as an argument of its own, like the prepared sparse features:
+ * four new symbols and one new struct, no existing struct or signature changed, so pn_abi_version keeps answering 12.
+ * (pn_pagg_args ends with the version-12 fields, and bindings written against it stay valid.)
+ *
+ * weight: dev fp32, one entry per sequence slot q of the batch, laid out like ids without its last axis: [S_total, W], or
+ * the slice's rows [S, W] with index_rows_local (the same q - first-row indexing as ids).  For HOMO / PAGG entry [s, w]
+ * belongs to path w of masked node s; for HETERO it belongs to slot q of the reference's scrambled batch (see
+ * out_path_weight), the slot whose final hidden state the pooling reads -- NOT to path w of row s.  A weight that is no
+ * finite positive number counts as 0.  With a group's live weights w_m, their sum Om and kappa = W / Om (norm =
+ * PN_PATH_NORM_SUM) or 1 (PN_PATH_NORM_COUNT), kappa = 0 for an empty group (Om = 0: pooled = 0, no gradient):
+ *   PAGG    pooled = (1/W) sum kappa w_m h_m
+ *   HOMO    pooled = (1/W) sum kappa w_m (1 + s_m) h_m
+ *   HETERO  pooled = (1/W) sum kappa a_m h_m,  a_m = w_m e_m / sum_k w_k e_k,  e_m = exp(l_m - max_k l_k), l = LeakyReLU(score)
+ *           (the maximum over all members, live or not; every a_m is 0 when the denominator is)
+ * All-one weights give the unweighted values bit for bit on the same kernels; integer weights with PN_PATH_NORM_SUM give
+ * the unweighted pooling of a row in which path m is written w_m times (pn_path_multiplicity counts them).
+ * out_path_weight then reports the coefficient applied: kappa w_m c_m, or kappa a_m for HETERO.  The weights are data: no
+ * gradient is returned for them.  A path of weight 0 still runs through the recurrence and gets d h_n = 0.
+ * pw == NULL, or pw->weight == NULL: the unweighted call, exactly.  The backward takes the array its forward took.
+ * Micro-batches (the backward's re-runs included), group_begin slices, the deterministic mode, every cell and every H are
+ * covered; the training step runs a weighted node through pool_step_kernel (pn_pool.h), never the register-resident one. */
+typedef struct pn_path_weights {
+    const float *weight;
+    int32_t norm;           /* PN_PATH_NORM_* */
+} pn_path_weights;
+int pn_pagg_forward_weighted(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *sp /* or NULL */,
+                             const pn_path_weights *pw /* or NULL */, void *stream);
+int pn_pagg_backward_weighted(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *sp,
+                              const pn_path_weights *pw, void *stream);
+int pn_pagg_train_step_weighted(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *sp,
+                                const pn_path_weights *pw, const int64_t *target, float grad_scale, float *loss, void *stream);
+int pn_pagg_train_step_loss_weighted(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *sp,
+                                     const pn_loss_spec *spec, const pn_path_weights *pw, const int64_t *target, float *loss,
+                                     void *stream);
 
 /* One Adam update of a list of tensors in a single launch, with the semantics of torch.optim.Adam(lr, betas, eps,
  * weight_decay) (:295-296): g += weight_decay * p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;

@@ -19,6 +19,6 @@ from .sampler import (DRAW_GLIBC_REPLAY, DRAW_PHILOX, BiasedSampler, MerwSampler
                       PathReport, UniformSampler)
 from .pathprob import PathProb, importance_weights  # noqa: F401
 from .synth import PatternCensus  # noqa: F401
-from .walkstats import WalkStats, walk_stats  # noqa: F401
+from .walkstats import WalkStats, path_multiplicity, walk_stats  # noqa: F401
 
 __version__ = "0.1.0"

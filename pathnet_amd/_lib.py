@@ -18,6 +18,7 @@ VARIANT_HETERO, VARIANT_HOMO, VARIANT_PAGG = 0, 1, 2
 CELL_DEFAULT, CELL_LSTM, CELL_RNN, CELL_GRU, CELL_MEAN, CELL_SUM = 0, 1, 2, 3, 4, 5
 SEQ_MATH_DEFAULT, SEQ_MATH_BF16X3, SEQ_MATH_F16X2 = 0, 1, 2     # pn_pagg_shape.seq_math
 COMPACT_AUTO, COMPACT_ON, COMPACT_OFF = 0, 1, 2                 # pn_pagg_shape.compact
+PATH_NORM_SUM, PATH_NORM_COUNT = 0, 1                           # pn_path_weights.norm
 LINEAR_SPLIT_MAX = 8          # PN_LINEAR_SPLIT_MAX: workspace floats per output element of pn_linear_forward
 LINEAR_BWD_SPLIT_MAX = 32     # PN_LINEAR_BWD_SPLIT_MAX: chunk sums of pn_linear_backward's deterministic weight gradient
 
@@ -90,6 +91,11 @@ class PathProbOut(ctypes.Structure):
     _fields_ = [(k, vp) for k in FIELDS]
 
 
+class PathWeights(ctypes.Structure):
+    """struct pn_path_weights: per-path weights of the pooling (dev fp32 [S_total, W]) and their normalisation (PATH_NORM_*)"""
+    _fields_ = [("weight", vp), ("norm", ctypes.c_int32)]
+
+
 LOSS_MEAN, LOSS_SUM = 0, 1        # pn_loss_spec.reduction
 
 
@@ -160,6 +166,7 @@ SIGNATURES = {
                                                      ctypes.c_int32, c_i64p]),
     "pn_walk_stats": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp,
                                      ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(WalkStatsOut), vp, ctypes.c_int64, vp]),
+    "pn_path_multiplicity": (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp]),
     "pn_path_prob_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(SamplerTables), ctypes.c_int32, ctypes.c_int32,
                                                     ctypes.c_int64, ctypes.c_int32, c_i64p]),
     "pn_path_prob": (ctypes.c_int, [vp, ctypes.POINTER(SamplerTables), ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, vp,
@@ -203,6 +210,14 @@ SIGNATURES = {
     "pn_cross_entropy_ex": (ctypes.c_int, [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(LossSpec), vp, vp, vp]),
     "pn_pagg_train_step_loss": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures),
                                                ctypes.POINTER(LossSpec), vp, vp, vp]),
+    "pn_pagg_forward_weighted": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures),
+                                                ctypes.POINTER(PathWeights), vp]),
+    "pn_pagg_backward_weighted": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures),
+                                                 ctypes.POINTER(PathWeights), vp]),
+    "pn_pagg_train_step_weighted": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures),
+                                                   ctypes.POINTER(PathWeights), vp, ctypes.c_float, vp, vp]),
+    "pn_pagg_train_step_loss_weighted": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures),
+                                                        ctypes.POINTER(LossSpec), ctypes.POINTER(PathWeights), vp, vp, vp]),
     "pn_adam_step": (ctypes.c_int, [ctypes.POINTER(AdamTensor), ctypes.c_int32, ctypes.c_float, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int64, vp, vp]),
     "pn_adam_step_advance": (ctypes.c_int, [ctypes.POINTER(AdamTensor), ctypes.c_int32, ctypes.c_float, ctypes.c_float,

@@ -291,6 +291,8 @@ struct Call {
     const float *Xh;
     float *Z;
     const pn_sparse_features *sp;       // prepared features of a->X that this call uses for fc0, or null: the dense kernels
+    const float *omega;                 // pn_path_weights.weight of the call, or null: the unweighted pooling
+    int norm;                           // PN_PATH_NORM_*
     template <class T>
     T *at(size_t off) const { return reinterpret_cast<T *>(ws + off); }
     int groups(int b) const { return std::min(d.Sb, d.S - b * d.Sb); }                 // pooling groups of micro-batch b
@@ -299,7 +301,7 @@ struct Call {
 };
 
 int resolve_call(Call &c, pn_context *ctx, const pn_pagg_args *a, hipStream_t stream, const char *who,
-                 const pn_sparse_features *sp = nullptr) {
+                 const pn_sparse_features *sp = nullptr, const pn_path_weights *pw = nullptr) {
     if (!a) PN_FAIL(PN_ERR_ARG, "%s: null args", who);
     if (int rc = context_check_device(ctx)) return rc;
     if (int rc = make_dims(a->shape, c.d)) return rc;
@@ -316,6 +318,9 @@ int resolve_call(Call &c, pn_context *ctx, const pn_pagg_args *a, hipStream_t st
     c.Z = c.at<float>(c.w.Z);
     // prepared features serve fc0 where the library runs it itself, at the fused hidden sizes; PN_FC0_SPARSE = 0 ignores them
     c.sp = (sp && !a->Xh_in && c.d.H <= 256 && (int64_t)c.d.N * c.d.F <= SPARSE_MAX_ELEMS && knobs_of(ctx).fc0_sparse != 0) ? sp : nullptr;
+    c.omega = pw ? pw->weight : nullptr;
+    c.norm = pw ? pw->norm : PN_PATH_NORM_SUM;
+    if (c.norm != PN_PATH_NORM_SUM && c.norm != PN_PATH_NORM_COUNT) PN_FAIL(PN_ERR_ARG, "%s: unknown pn_path_weights.norm %d", who, c.norm);
     if (a->index_rows_local && c.d.variant == PN_VARIANT_HETERO && (c.d.group_begin != 0 || c.d.S != c.d.S_total))
         PN_FAIL(PN_ERR_ARG, "%s: the hetero class reads paths of the whole batch (PathNet_run.py:196-197): "
                 "index_rows_local needs the whole batch's ids / codes", who);
@@ -559,6 +564,10 @@ PoolParams pool_fwd_params(const Call &c, int b, float *out) {
     pp.rawsc = c.at<float>(c.w.rawsc);
     pp.layer1 = c.at<float>(c.w.layer1);
     pp.out = out;
+    pp.omega = c.omega;       // (laid out like ids without the last axis: the plan's slot q, less the slice's first)
+    pp.slotof = c.at<int32_t>(c.w.slotof);
+    pp.wbase = a->index_rows_local ? (int64_t)d.group_begin * d.W : 0;
+    pp.norm = c.norm;
     return pp;
 }
 // outputs: pn_pagg_forward's own pass writes the caller's optional outputs (out_*: rows of micro-batch b); the backward's
@@ -867,6 +876,10 @@ PoolBwdParams pool_bwd_params(const Call &c, int b, const float *g_out) {
         pp.det_sel = c.at<float>(c.w.dsel);
         pp.det_ds = c.at<float>(c.w.dds);
     }
+    pp.omega = c.omega;
+    pp.slotof = c.at<int32_t>(c.w.slotof);
+    pp.wbase = a->index_rows_local ? (int64_t)d.group_begin * d.W : 0;
+    pp.norm = c.norm;
     return pp;
 }
 
@@ -1186,10 +1199,15 @@ int pn_pagg_forward(pn_context *ctx, const pn_pagg_args *a, void *stream) {
     return pn_pagg_forward_sparse(ctx, a, nullptr, stream);
 }
 
-int pn_pagg_forward_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, void *stream_) {
+int pn_pagg_forward_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, void *stream) {
+    return pn_pagg_forward_weighted(ctx, a, sp, nullptr, stream);
+}
+
+int pn_pagg_forward_weighted(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const pn_path_weights *pw,
+                             void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     Call c;
-    if (int rc = resolve_call(c, ctx, a, stream, "pn_pagg_forward", sp)) return rc;
+    if (int rc = resolve_call(c, ctx, a, stream, "pn_pagg_forward", sp, pw)) return rc;
     const Dims &d = c.d;
     if (int rc = check_forward_args(c, "pn_pagg_forward")) return rc;
     if (d.S == 0) return PN_OK;
@@ -1213,11 +1231,11 @@ int pn_pagg_forward_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_spar
 // backward (saved tensors in place), the loss gradient of its rows is formed in between
 static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stream_, const int64_t *target, float grad_scale,
                               float *loss, const pn_sparse_features *sp, const LossOpts *opts = nullptr,
-                              float *denom_out = nullptr) {
+                              float *denom_out = nullptr, const pn_path_weights *pw = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     const bool fused = target != nullptr;
     Call c;
-    if (int rc = resolve_call(c, ctx, a, stream, fused ? "pn_pagg_train_step" : "pn_pagg_backward", sp)) return rc;
+    if (int rc = resolve_call(c, ctx, a, stream, fused ? "pn_pagg_train_step" : "pn_pagg_backward", sp, pw)) return rc;
     const Dims &d = c.d;
     if (fused) {
         if (d.S > 0)
@@ -1366,6 +1384,11 @@ int pn_pagg_backward_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_spa
     return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp);
 }
 
+int pn_pagg_backward_weighted(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const pn_path_weights *pw,
+                              void *stream) {
+    return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp, nullptr, nullptr, pw);
+}
+
 int pn_pagg_train_step(pn_context *ctx, const pn_pagg_args *a, const int64_t *target, float grad_scale, float *loss,
                        void *stream) {
     return pn_pagg_train_step_sparse(ctx, a, nullptr, target, grad_scale, loss, stream);
@@ -1373,16 +1396,26 @@ int pn_pagg_train_step(pn_context *ctx, const pn_pagg_args *a, const int64_t *ta
 
 int pn_pagg_train_step_sparse(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const int64_t *target,
                               float grad_scale, float *loss, void *stream) {
+    return pn_pagg_train_step_weighted(ctx, a, sp, nullptr, target, grad_scale, loss, stream);
+}
+
+int pn_pagg_train_step_weighted(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const pn_path_weights *pw,
+                                const int64_t *target, float grad_scale, float *loss, void *stream) {
     if (int rc = check_train_step_args(a, target, loss, "pn_pagg_train_step")) return rc;
     if (a->shape.S == 0) {          // nothing to aggregate: zero loss, zero gradients
         PN_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float), (hipStream_t)stream));
         return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp);
     }
-    return pagg_backward_impl(ctx, a, stream, target, grad_scale, loss, sp);
+    return pagg_backward_impl(ctx, a, stream, target, grad_scale, loss, sp, nullptr, nullptr, pw);
 }
 
 int pn_pagg_train_step_loss(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const pn_loss_spec *spec,
                             const int64_t *target, float *loss, void *stream) {
+    return pn_pagg_train_step_loss_weighted(ctx, a, sp, spec, nullptr, target, loss, stream);
+}
+
+int pn_pagg_train_step_loss_weighted(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const pn_loss_spec *spec,
+                                     const pn_path_weights *pw, const int64_t *target, float *loss, void *stream) {
     LossOpts o;
     if (int rc = loss_opts_from_spec(spec, "pn_pagg_train_step_loss", &o)) return rc;
     if (int rc = check_train_step_args(a, target, loss, "pn_pagg_train_step_loss")) return rc;
@@ -1392,7 +1425,7 @@ int pn_pagg_train_step_loss(pn_context *ctx, const pn_pagg_args *a, const pn_spa
         if (denom_out) PN_CHECK_HIP(hipMemsetAsync(denom_out, 0, sizeof(float), (hipStream_t)stream));
         return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp);
     }
-    return pagg_backward_impl(ctx, a, stream, target, o.grad_scale, loss, sp, &o, denom_out);
+    return pagg_backward_impl(ctx, a, stream, target, o.grad_scale, loss, sp, &o, denom_out, pw);
 }
 
 }  // extern "C"

@@ -34,6 +34,12 @@ struct PoolParams {
     float *embed;           // [S, 2H] classifier input before the dropout
     float *path_weight;     // [S, W]  coef in member order
     float *path_state;      // [S, W, H] hn in member order
+    // pn_path_weights.weight, or null: today's coefficients (a kernel argument too, tested uniformly over the grid).  The
+    // weight of slot' is omega[slotof[slot'] - wbase]: one entry per sequence slot q of the batch, laid out like ids
+    const float *omega;
+    const int32_t *slotof;  // [P] the plan's slot q of every slot' of this launch
+    int64_t wbase;          // first slot the caller's array holds (index_rows_local: the slice's, else 0)
+    int norm;               // PN_PATH_NORM_*
 };
 int launch_pool_fwd(void *stream, const PoolParams &p);
 
@@ -60,6 +66,12 @@ struct PoolBwdParams {
     // pn_pagg_args.g_embed: d loss / d (classifier input before the dropout) [S, 2H] of this launch's groups, or null.  g_out
     // may be null when it is set (the classifier's term is then absent)
     const float *g_embed;
+    // the path weights, as in PoolParams: coef holds kappa * omega * c already; the score gradient needs kappa, recomputed from
+    // the group's W weights
+    const float *omega;
+    const int32_t *slotof;
+    int64_t wbase;
+    int norm;
 };
 // HI = 4 up to H = 256, HI = 16 above
 int launch_pool_bwd(pn_context *ctx, void *stream, const PoolBwdParams &p);
@@ -92,8 +104,9 @@ struct PoolStepLossParams {
 };
 // The pooling step of micro-batch ps.f.S groups, with the loss options when opts is set.  knob = PN_POOL_STEP (Knobs::pool_step,
 // non-zero here): the node's rows in registers (pool_step2_kernel<10, 2>) when
-//     W <= 40 && 32 <= H <= 128 && its LDS <= 64 KiB && knob >= 1 && knob != 2,
-// else the three bodies back to back: pool_step_kernel<4> up to H = 256, <16> above.
+//     W <= 40 && 32 <= H <= 128 && its LDS <= 64 KiB && knob >= 1 && knob != 2 && no path weights (ps.f.omega null),
+// else the three bodies back to back: pool_step_kernel<4> up to H = 256, <16> above.  pool_step2_kernel does not carry the
+// path weights: a weighted call always takes the three bodies, an unweighted one goes exactly where it went before.
 int launch_pool_step(pn_context *ctx, void *stream, const PoolStepParams &ps, const LossOpts *opts, int knob);
 
 // loss[0] (+)= k * sum of the rows' terms lossg[0 .. rows), one workgroup, cross_entropy_kernel's order; k = scale, or with opts

@@ -16,6 +16,21 @@ using namespace pn;
 
 namespace {
 
+// ---- path weights (pn_path_weights; PoolParams::omega) ---------- ----------------------------------------------------------
+// a weight that is no finite positive number counts as 0 (bit test: positive, non-zero, below +inf)
+__device__ __forceinline__ float live_weight(float w) { return (__float_as_uint(w) - 1u) < 0x7f7fffffu ? w : 0.0f; }
+// kappa of a group from its W live weights in LDS: W / sum (PN_PATH_NORM_SUM) or 1 (PN_PATH_NORM_COUNT); 0 for an empty group,
+// and for a sum so small that W / sum leaves fp32.  Every wave adds all W in the same order: the same value in each; W ones
+// add up to W exactly, so all-one weights give exactly 1.
+__device__ __forceinline__ float pool_kappa(const float *s_om, int W, int norm, int lane) {
+    float om = 0.0f;
+    for (int mem = lane; mem < W; mem += 64) om += s_om[mem];
+    om = wave_sum(om);
+    if (norm == PN_PATH_NORM_COUNT) return om > 0.0f ? 1.0f : 0.0f;
+    const float k = (float)W / om;
+    return k < 3.0e38f ? k : 0.0f;
+}
+
 // (PoolParams: pn_pool.h)
 __device__ __forceinline__ void pool_fwd_body(const PoolParams &p, float *lds) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -24,7 +39,17 @@ __device__ __forceinline__ void pool_fwd_body(const PoolParams &p, float *lds) {
     int *s_erow = reinterpret_cast<int *>(sc + W);              // [W] ego rows of the group's members
     float *part4 = reinterpret_cast<float *>(s_erow + W);       // [4][H] the waves' partial pooled sums
     float *l1s = part4 + 4 * H;                                 // [2H] classifier input
+    float *s_om = l1s + 2 * H;                                  // [W] live path weights (with p.omega)
     const float inv_w = 1.0f / (float)W;
+    // without weights every factor below is the constant 1: x * 1 is x, the coefficients keep their bits
+    float kappa = 1.0f;
+    if (p.omega) {
+        for (int mem = tid; mem < W; mem += 256)
+            s_om[mem] = live_weight(p.omega[(int64_t)p.slotof[(int64_t)g * W + mem] - p.wbase]);
+        __syncthreads();
+        kappa = pool_kappa(s_om, W, p.norm, lane);
+    }
+    auto om = [&](int mem) { return p.omega ? s_om[mem] : 1.0f; };
 
     if (p.variant != PN_VARIANT_PAGG) {
         // the ego rows, fetched up front: the score loop then has no index -> row dependent load pair
@@ -72,19 +97,20 @@ __device__ __forceinline__ void pool_fwd_body(const PoolParams &p, float *lds) {
         for (int mem = lane; mem < W; mem += 64) {
             float v = sc[mem];
             v = v > 0.0f ? v : 0.01f * v;
-            sum += expf(v - mx);
+            sum += om(mem) * expf(v - mx);
         }
         sum = wave_sum(sum);
         __syncthreads();
+        // (the maximum is over all members, live or not; a group whose live members' terms sum to 0 pools nothing)
         for (int mem = tid; mem < W; mem += 256) {
             float v = sc[mem];
             v = v > 0.0f ? v : 0.01f * v;
-            sc[mem] = expf(v - mx) / sum;
+            sc[mem] = (!p.omega || sum > 0.0f) ? kappa * (om(mem) * expf(v - mx) / sum) : 0.0f;
         }
     } else if (p.variant == PN_VARIANT_HOMO) {
-        for (int mem = tid; mem < W; mem += 256) sc[mem] = 1.0f + sc[mem];
+        for (int mem = tid; mem < W; mem += 256) sc[mem] = (kappa * om(mem)) * (1.0f + sc[mem]);
     } else {
-        for (int mem = tid; mem < W; mem += 256) sc[mem] = 1.0f;
+        for (int mem = tid; mem < W; mem += 256) sc[mem] = kappa * om(mem);
     }
     __syncthreads();
     for (int mem = tid; mem < W; mem += 256) p.coef[(int64_t)g * W + mem] = sc[mem];
@@ -145,7 +171,7 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(PoolParams p) {
     extern __shared__ float lds[];
     pool_fwd_body(p, lds);
 }
-inline size_t pool_fwd_lds_bytes(int W, int H) { return (2 * (size_t)W + 6 * (size_t)H) * sizeof(float); }
+inline size_t pool_fwd_lds_bytes(int W, int H) { return (3 * (size_t)W + 6 * (size_t)H) * sizeof(float); }
 
 // ================================================================================================
 // BACKWARD
@@ -167,6 +193,7 @@ __device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *
     int *s_erow = reinterpret_cast<int *>(red + 8 * H);    // [W] ego rows of the group
     float *s_coef = reinterpret_cast<float *>(s_erow + W);  // [W]
     float *s_tot = s_coef + W;               // [4] hetero: partial sums of coef * d coef
+    float *s_kw = s_tot + 4;                 // [W] live path weights (with p.omega; pool_bwd_lds_bytes has the room)
     const int g = blockIdx.x;
     const float inv_w = 1.0f / (float)W;
     for (int mem = tid; mem < W; mem += 256) {
@@ -174,6 +201,8 @@ __device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *
         s_erow[mem] = p.variant == PN_VARIANT_PAGG ? 0 : p.egoidx[s];
         s_coef[mem] = p.coef[s];
     }
+    if (p.omega)        // (a loop of its own: inside the one above it costs pool_bwd_wg_kernel<4> 22 registers)
+        for (int mem = tid; mem < W; mem += 256) s_kw[mem] = live_weight(p.omega[(int64_t)p.slotof[(int64_t)g * W + mem] - p.wbase]);
     for (int j = tid; j < H; j += 256) {
         float a = 0.0f, b = 0.0f;
         if (p.g_out)
@@ -220,19 +249,23 @@ __device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *
         }
     }
     __syncthreads();
+    // coef = kappa * omega * c: d score = kappa * omega * d coef (HOMO), and the softmax's sum carries 1 / kappa (HETERO: with
+    // coef = kappa * a, d l_m = coef_m * (d coef_m - sum_k coef_k d coef_k / kappa)).  Without weights both factors are 1.
+    const float kappa = p.omega ? pool_kappa(s_kw, W, p.norm, lane) : 1.0f;
     if (p.variant == PN_VARIANT_HETERO) {
         float tot = 0.0f;
         for (int mem = tid; mem < W; mem += 256) tot += s_coef[mem] * dco[mem];
         tot = wave_sum(tot);
         if (lane == 0) s_tot[wave] = tot;
         __syncthreads();
-        tot = (s_tot[0] + s_tot[1]) + (s_tot[2] + s_tot[3]);
+        tot = ((s_tot[0] + s_tot[1]) + (s_tot[2] + s_tot[3])) * (kappa > 0.0f ? 1.0f / kappa : 0.0f);
         for (int mem = tid; mem < W; mem += 256) {
             const int64_t s = (int64_t)g * W + mem;
             dsc[mem] = s_coef[mem] * (dco[mem] - tot) * (p.rawsc[s] > 0.0f ? 1.0f : 0.01f);
         }
     } else {
-        for (int mem = tid; mem < W; mem += 256) dsc[mem] = p.variant == PN_VARIANT_HOMO ? dco[mem] : 0.0f;
+        for (int mem = tid; mem < W; mem += 256)
+            dsc[mem] = p.variant == PN_VARIANT_HOMO ? (p.omega ? (kappa * s_kw[mem]) * dco[mem] : dco[mem]) : 0.0f;
     }
     __syncthreads();
     // per member: d h_n, the attention-weight terms and the attention-ego term; wave w takes members w, w + 4, ...
@@ -478,7 +511,8 @@ int launch_pool_step(pn_context *ctx, void *stream, const PoolStepParams &ps, co
     // pool_lds_bytes does not bound: past 64 KiB (C > 7 424 at H = 128) the node goes to pool_step_kernel<4>, whose LDS does
     // not depend on C (within 64 KiB by make_dims)
     const size_t lds_step2 = pool_step2_lds_bytes(10, H, C);
-    const bool step2 = W <= 40 && H <= 128 && H >= 32 && lds_step2 <= 64 * 1024 && knob >= 1 && knob != 2;
+    // (pool_step2_kernel does not carry the path weights: a weighted call takes the three bodies)
+    const bool step2 = W <= 40 && H <= 128 && H >= 32 && lds_step2 <= 64 * 1024 && knob >= 1 && knob != 2 && !ps.f.omega;
     if (opts) {         // pn_pagg_train_step_loss: the same three routes, their option-aware kernels
         const PoolStepLossParams ql{ps, *opts};
         if (step2) {

@@ -25,6 +25,7 @@
 //     atomicAdd each.  label_pairs is held in LDS while L * C * C <= kLabelPairsLds; a larger table takes one global
 //     atomic per entry of the paths instead.  visits [n] is always global: one atomic per entry at a step >= 1.
 //   stats_zero_kernel: clears the global tables of a call that does not accumulate, in one launch.
+//   path_mult_kernel (pn_path_multiplicity): how often each path of a row occurs in it, as weights for the aggregators' pooling.
 // LDS per workgroup: (W * L + W / 2 + 2) words per row slot and L * L + 4 L + 3 (+ L * C * C) words of tables:
 // 3.3 KB at Cornell's shape, 59 KB at the largest.  gfx950 only.
 #include <hip/hip_runtime.h>
@@ -306,6 +307,41 @@ __global__ __launch_bounds__(kStatsThreads) void walk_stats_kernel(StatsParams p
     }
 }
 
+// ---- path multiplicities (pn_path_multiplicity) -----------------------------------------------------------------------------
+// mult[r, j] = paths of row r whose id sequence (and code sequence, with codes) equals path j's when j is the first of them,
+// else 0.  A workgroup per row, striding over the rows: the row's ids (and codes) are staged in LDS, a thread per path compares
+// its path with every path of the row -- W * W * L LDS reads, 6 400 at W = 40, L = 4; the unique-path count's sort would save
+// nothing at that size.  Integer counts written as floats (<= W <= 8192: exact).
+__global__ __launch_bounds__(kStatsThreads) void path_mult_kernel(int W, int L, int64_t rows, const int32_t *__restrict__ ids,
+                                                                  const uint8_t *__restrict__ codes, float *__restrict__ mult) {
+    extern __shared__ int32_t smem[];
+    const int WL = W * L;
+    int32_t *a = smem;                                              // [W][L] ids
+    uint8_t *cd = reinterpret_cast<uint8_t *>(smem + WL);           // [W][L] codes (with codes)
+    for (int64_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        const int64_t at = row * WL;
+        __syncthreads();                  // the last row is done with
+        for (int e = threadIdx.x; e < WL; e += kStatsThreads) {
+            a[e] = ids[at + e];
+            if (codes) cd[e] = codes[at + e];
+        }
+        __syncthreads();
+        for (int j = threadIdx.x; j < W; j += kStatsThreads) {
+            int count = 0;
+            bool first = true;
+            for (int k = 0; k < W; k++) {
+                bool eq = true;
+                for (int t = L - 1; t >= 0 && eq; t--) eq = a[j * L + t] == a[k * L + t];
+                if (codes)
+                    for (int t = 0; t < L && eq; t++) eq = cd[j * L + t] == cd[k * L + t];
+                count += eq;
+                first = first && !(eq && k < j);
+            }
+            mult[row * W + j] = first ? (float)count : 0.0f;
+        }
+    }
+}
+
 int check_shape(const char *who, int32_t n, int32_t W, int32_t L, int64_t rows, int32_t C) {
     if (n < 1 || W < 1 || L < 1 || rows < 0)
         PN_FAIL(PN_ERR_ARG, "%s: bad shape (n=%d W=%d L=%d rows=%lld)", who, n, W, L, (long long)rows);
@@ -388,6 +424,21 @@ int pn_walk_stats(pn_context *ctx, int32_t n, int32_t W, int32_t L, int64_t rows
         const size_t lds = sizeof(int32_t) * ((size_t)L * L + 4 * L + 3 + sp.lp_lds + (size_t)rpb * (WL + (W + 1) / 2 + 2));
         hipLaunchKernelGGL(walk_stats_kernel, dim3((unsigned)blocks), dim3(kStatsThreads), lds, stream, sp);
     }
+    PN_CHECK_HIP(hipGetLastError());
+    return PN_OK;
+}
+
+int pn_path_multiplicity(pn_context *ctx, int32_t W, int32_t L, int64_t rows, const int32_t *ids, const uint8_t *codes,
+                         float *mult, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = check_shape("pn_path_multiplicity", 1, W, L, rows, 0)) return rc;
+    if (rows > 0 && (!ids || !mult)) PN_FAIL(PN_ERR_ARG, "pn_path_multiplicity: null ids or mult");
+    if (int rc = pn::context_check_device(ctx)) return rc;
+    if (rows == 0) return PN_OK;
+    const int WL = W * L;
+    const size_t lds = sizeof(int32_t) * (size_t)WL + (codes ? ((size_t)WL + 3) / 4 * 4 : 0);
+    const int64_t blocks = rows < kMaxBlocks ? rows : kMaxBlocks;
+    hipLaunchKernelGGL(path_mult_kernel, dim3((unsigned)blocks), dim3(kStatsThreads), lds, stream, W, L, rows, ids, codes, mult);
     PN_CHECK_HIP(hipGetLastError());
     return PN_OK;
 }

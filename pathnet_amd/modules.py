@@ -53,6 +53,30 @@ def default_budget(device=None):
 _SEQ_MATH = {None: _lib.SEQ_MATH_DEFAULT, "": _lib.SEQ_MATH_DEFAULT, "f16x2": _lib.SEQ_MATH_F16X2, "bf16x3": _lib.SEQ_MATH_BF16X3}
 
 
+_PATH_NORM = {"sum": _lib.PATH_NORM_SUM, "count": _lib.PATH_NORM_COUNT}
+
+
+def as_path_weights(path_weights, rows, W, check=False):
+    """path_weights= of the aggregators -> a float32 tensor [rows, W] (still on its own device), or None.  Any float (or
+    integer) dtype, shape [rows, W] or [rows * W]; rows: the rows of the call's neis.  A wrong shape or a tensor that requires
+    grad raises ValueError -- the weights are data, no gradient is returned for them.  check: also raise on a negative or
+    non-finite entry (one host read); unchecked, the kernels count such an entry as 0."""
+    if path_weights is None:
+        return None
+    w = torch.as_tensor(path_weights)
+    if w.requires_grad:
+        raise ValueError("path_weights requires grad: the weights are data, no gradient is returned for them (detach them)")
+    if w.dtype == torch.bool or w.dtype.is_complex:
+        raise TypeError("path_weights: a real dtype expected, got %s" % w.dtype)
+    if tuple(w.shape) not in ((rows, W), (rows * W,)):
+        raise ValueError("path_weights of shape %s: [%d, %d] (masked nodes of neis x paths) or [%d] expected"
+                         % (tuple(w.shape), rows, W, rows * W))
+    w = w.reshape(rows, W)
+    if check and bool((~torch.isfinite(w) | (w < 0)).any()):
+        raise ValueError("path_weights hold negative or non-finite entries")
+    return w.to(torch.float32)
+
+
 def compact_default():
     """pn_pagg_shape.compact when a call does not say: PN_COMPACT=1 / 0 in the environment forces the touched-row
     compaction of the distance bank on / off (tests, A/B runs); otherwise the library decides from the shape.  Read when a
@@ -86,12 +110,13 @@ class PaggCall:
                     "deterministic", "compact", "seq_math")
     __slots__ = SHAPE_FIELDS + ("p_seq", "p_cls", "seed", "mask_seq", "mask_cls", "step_state", "index_rows_local", "bank_w",
                                 "bank_b", "grad", "reuse_tables", "grad_scale", "path_state", "sparse_plan", "workspace",
-                                "features", "loss", "_shape", "_ws_bytes")
+                                "features", "loss", "path_weights", "path_weight_norm", "_shape", "_ws_bytes")
 
     def __init__(self, variant, N, F, H, C, S, W, L, S_total=0, group_begin=0, batch_groups=0, cell=None, deterministic=False,
                  compact=None, seq_math=None, *, p_seq=0.0, p_cls=0.0, seed=0, mask_seq=None, mask_cls=None, step_state=None,
                  index_rows_local=False, bank_w=None, bank_b=None, grad=True, reuse_tables=0, grad_scale=1.0,
-                 path_state=False, sparse_plan=None, workspace=None, features=None, loss=None):
+                 path_state=False, sparse_plan=None, workspace=None, features=None, loss=None, path_weights=None,
+                 path_weight_norm="sum"):
         self.variant, self.N, self.F, self.H, self.C, self.S, self.W, self.L = variant, N, F, H, C, S, W, L
         self.S_total, self.group_begin, self.batch_groups, self.cell = S_total, group_begin, batch_groups, cell
         # decisions that shape the workspace are taken once per call and travel with its shape
@@ -107,6 +132,9 @@ class PaggCall:
         self.features = features        # PreparedFeatures of the call's X (fc0 over its non-zeros), or None: the dense kernels
         # (optim.CrossEntropyLoss with options, grad_scale of the reduced loss) of forward_loss(loss=...), or None: the plain loss
         self.loss = loss
+        # per-path weights of the pooling: a contiguous fp32 device tensor [rows of ids, W] (as_path_weights) or None, and
+        # "sum" / "count".  The call keeps the tensor alive until its backward has read it.
+        self.path_weights, self.path_weight_norm = path_weights, path_weight_norm
         self._shape = self._ws_bytes = None
 
     def get(self, name, default=None):
@@ -177,6 +205,12 @@ class PaggCall:
         a.step_state = self.step_state.ptr() if self.step_state is not None else None
         a.index_rows_local = 1 if self.index_rows_local else 0
         return a
+
+    def weights_ref(self):
+        """the call's pn_path_weights for the pn_pagg_*_weighted entry points (None = NULL: the unweighted pooling)"""
+        if self.path_weights is None:
+            return None
+        return ctypes.byref(_lib.PathWeights(self.path_weights.data_ptr(), _PATH_NORM[self.path_weight_norm]))
 
     def grad_buffers(self, a, p, X=None, flat=False):
         """Gradient tensors for every parameter `a` names (and for X, when given), their addresses set in a.g_*.
@@ -346,8 +380,8 @@ class _PaggFunction(torch.autograd.Function):
                 a.out_embed, a.out_path_weight = encode_out[0].data_ptr(), encode_out[1].data_ptr()
                 a.out_path_state = encode_out[2].data_ptr() if encode_out[2] is not None else None
             if call.S > 0:
-                _lib.check(_lib.load().pn_pagg_forward_sparse(_lib.context(dev), ctypes.byref(a), call.features_ref(),
-                                                              _lib.stream_ptr(dev)))
+                _lib.check(_lib.load().pn_pagg_forward_weighted(_lib.context(dev), ctypes.byref(a), call.features_ref(),
+                                                                call.weights_ref(), _lib.stream_ptr(dev)))
         ctx.call, ctx.ws = call, ws
         ctx.present = [t is not None for t in params]
         ctx.save_for_backward(X, ids, codes, sel, *[t for t in params if t is not None])
@@ -380,8 +414,8 @@ class _PaggFunction(torch.autograd.Function):
             a.g_out = g_out.data_ptr() if g_out is not None else None
             a.g_embed = g_embed.data_ptr() if g_embed is not None else None
             if call.S > 0:
-                _lib.check(_lib.load().pn_pagg_backward_sparse(_lib.context(dev), ctypes.byref(a), call.features_ref(),
-                                                               _lib.stream_ptr(dev)))
+                _lib.check(_lib.load().pn_pagg_backward_weighted(_lib.context(dev), ctypes.byref(a), call.features_ref(),
+                                                                 call.weights_ref(), _lib.stream_ptr(dev)))
             else:
                 for g in list(grads.values()) + [gX] * (gX is not None):
                     g.zero_()
@@ -436,13 +470,13 @@ class _PaggLossFunction(torch.autograd.Function):
                 #  graph's pool's, like every other tensor of the step)
                 loss_fn, scale = call.loss
                 spec, ctx.loss_keep = loss_fn.spec(dev, call.C, scale)
-                _lib.check(_lib.load().pn_pagg_train_step_loss(_lib.context(dev), ctypes.byref(a), call.features_ref(),
-                                                               ctypes.byref(spec), target.data_ptr(), loss.data_ptr(),
-                                                               _lib.stream_ptr(dev)))
+                _lib.check(_lib.load().pn_pagg_train_step_loss_weighted(
+                    _lib.context(dev), ctypes.byref(a), call.features_ref(), ctypes.byref(spec), call.weights_ref(),
+                    target.data_ptr(), loss.data_ptr(), _lib.stream_ptr(dev)))
             elif call.S > 0:
-                _lib.check(_lib.load().pn_pagg_train_step_sparse(_lib.context(dev), ctypes.byref(a), call.features_ref(),
-                                                                 target.data_ptr(), float(call.grad_scale), loss.data_ptr(),
-                                                                 _lib.stream_ptr(dev)))
+                _lib.check(_lib.load().pn_pagg_train_step_weighted(
+                    _lib.context(dev), ctypes.byref(a), call.features_ref(), call.weights_ref(), target.data_ptr(),
+                    float(call.grad_scale), loss.data_ptr(), _lib.stream_ptr(dev)))
             else:
                 flat.zero_()
                 if gX is not None:
@@ -745,7 +779,7 @@ class _Aggregator(nn.Module):
         return fw, fb, head + tuple(ws) + tuple(bs)
 
     def forward_loss(self, X, neis, num_w, walk_len, indices, layer_type, target, indxx=None, grad_scale=None, fused=None,
-                     loss=None):
+                     loss=None, *, path_weights=None, path_weight_norm="sum", check_weights=False):
         """(loss, logits) of a training step's forward + torch.nn.CrossEntropyLoss() (PathNet_run.py:343-346); loss.backward()
         yields the parameter gradients.  target: class index of every masked node, in the order of the logits' rows.
         grad_scale: weight of a row's loss (default 1 / rows = the mean).
@@ -758,15 +792,28 @@ class _Aggregator(nn.Module):
         with every option at its default: the plain mean, today's call and bits).  Every route above takes it -- fused or
         not, micro-batches, sparse features, the deterministic mode -- and the weighted mean's denominator is formed on the
         device over the whole batch, so a captured step follows targets whose ignored count changes.  With a loss, grad_scale
-        (default 1 / rows) times rows multiplies the reduced loss: the default is torch's value."""
+        (default 1 / rows) times rows multiplies the reduced loss: the default is torch's value.
+        path_weights / path_weight_norm / check_weights: forward()'s.  A weighted fused step runs the pooling as three kernel
+        bodies in one launch; the register-resident pooling step is the unweighted call's."""
         return self._run(X, neis, num_w, walk_len, indices, layer_type, target=target, grad_scale=grad_scale, fused=fused,
-                         loss=loss)
+                         loss=loss, path_weights=path_weights, path_weight_norm=path_weight_norm, check_weights=check_weights)
 
-    def forward(self, X, neis, num_w, walk_len, indices, layer_type, indxx=None, reuse_tables=False, group_slice=None):
-        return self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=reuse_tables, group_slice=group_slice)
+    def forward(self, X, neis, num_w, walk_len, indices, layer_type, indxx=None, reuse_tables=False, group_slice=None, *,
+                path_weights=None, path_weight_norm="sum", check_weights=False):
+        """path_weights (extension; None: the reference's pooling, bit for bit): a weight per path, float [S, W] or [S * W] on
+        any device, S the masked nodes of neis (the whole batch also with group_slice).  PathNet_homo / PAGG: entry [s, w]
+        weighs path w of masked node s.  PathNet: entry [s, w] weighs sequence slot q = s * W + w of the reference's scrambled
+        LSTM batch, which the pooling reads as member q // S of node q % S (encode()'s member order) -- not path w of node s.
+        An entry that is no finite positive number counts as 0: the path is left out of the row.  path_weight_norm="sum"
+        scales a row's weights to sum to W, so integer weights are repeated paths and pathnet_amd.importance_weights are a
+        self-normalised estimate; "count" applies them as given.  A row without a live path pools zeros and passes no
+        gradient to its paths.  The weights are data: no gradient is returned for them, a tensor that requires grad is
+        refused.  check_weights=True raises on a negative or non-finite entry (one host read)."""
+        return self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=reuse_tables, group_slice=group_slice,
+                         path_weights=path_weights, path_weight_norm=path_weight_norm, check_weights=check_weights)
 
     def encode(self, X, neis, num_w, walk_len, indices, layer_type, indxx=None, *, path_state=False, group_slice=None,
-               reuse_tables=False, seed=None):
+               reuse_tables=False, seed=None, path_weights=None, path_weight_norm="sum", check_weights=False):
         """The model's internals next to its logits, from the same single forward: ``Encoded(logits, embedding, path_weight,
         path_state)``, every tensor fp32 on X's device, one row per masked node (of the group_slice, when given).
 
@@ -775,7 +822,8 @@ class _Aggregator(nn.Module):
                                  (layer1 = torch.cat((ego, h_n), dim=1), PathNet_run.py:207 / :275, copy.py:355); in training
                                  it holds the sequence dropout of the same call.  Differentiable w.r.t. every parameter and X.
           path_weight [S, W]     the coefficient that multiplies member j's final hidden state in row s's mean: the softmax
-                                 weight (PathNet), 1 + att (PathNet_homo), 1 (PAGG).  Not differentiable.
+                                 weight (PathNet), 1 + att (PathNet_homo), 1 (PAGG); with path_weights (forward()'s) the
+                                 coefficient actually applied, kappa * weight * that.  Not differentiable.
           path_state  [S, W, H]  member j's final hidden state h_n; only with path_state=True (it is large), else None.
                                  Not differentiable.
 
@@ -789,7 +837,8 @@ class _Aggregator(nn.Module):
         generator.  Not covered: gradients through path_weight / path_state, the node-sharded and replicated aggregators
         of pathnet_amd.dist, and the fused training step (forward_loss(fused=True))."""
         res = self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=reuse_tables, group_slice=group_slice,
-                        seed=seed, _encode=bool(path_state))
+                        seed=seed, _encode=bool(path_state), path_weights=path_weights, path_weight_norm=path_weight_norm,
+                        check_weights=check_weights)
         logits, emb, pw = res[:3]
         ps = res[3] if path_state else None
         H = self.hidden_size
@@ -871,7 +920,8 @@ class _Aggregator(nn.Module):
                 seq_math_default() if self.seq_math is None else _SEQ_MATH[self.seq_math])
 
     def _run(self, X, neis, num_w, walk_len, indices, layer_type, reuse_tables=False, group_slice=None, target=None,
-             grad_scale=None, fused=None, batch_position=None, seed=None, _math=None, _encode=None, loss=None):
+             grad_scale=None, fused=None, batch_position=None, seed=None, _math=None, _encode=None, loss=None,
+             path_weights=None, path_weight_norm="sum", check_weights=False):
         """reuse_tables (extension, inference only): X and the weights are those of the previous no-grad forward of this
         module -- the validation and the test forward of an epoch (PathNet_run.py:362, :378) -- so the projected
         feature matrix and the distance bank still sitting in the module's workspace are used again.
@@ -879,6 +929,12 @@ class _Aggregator(nn.Module):
         the logits of its masked nodes [begin, begin + count) are computed and returned -- exactly those rows of the
         whole-batch result, also for the hetero class whose rows read paths of other masked nodes of the batch."""
         dev = X.device
+        # (the weights are judged first: what is wrong with them does not depend on where the call runs)
+        if path_weight_norm not in _PATH_NORM:
+            raise ValueError("path_weight_norm=%r: 'sum' or 'count'" % (path_weight_norm,))
+        if path_weights is not None:
+            rows = int(torch.as_tensor(neis).numel()) // max(int(num_w) * int(walk_len), 1)       # the masked nodes neis describes
+            path_weights = as_path_weights(path_weights, rows, int(num_w), check=check_weights)
         if dev.type != "cuda":
             raise RuntimeError("pathnet_amd aggregators run on the GPU only (X is on %s); no CPU fallback" % dev)
         X_given = X
@@ -924,7 +980,8 @@ class _Aggregator(nn.Module):
         call = PaggCall(self.variant, X.shape[0], X.shape[1], Hk, self.out_size, S, int(num_w), L, S_total, begin, 0,
                         self._cell_kind, det, compact, math, p_seq=p_drop, p_cls=p_drop, seed=seed, mask_seq=ms, mask_cls=mc,
                         step_state=self.step_state, index_rows_local=batch_position is not None, bank_w=fw, bank_b=fb,
-                        grad=grad, path_state=bool(_encode))
+                        grad=grad, path_state=bool(_encode), path_weight_norm=path_weight_norm,
+                        path_weights=path_weights.to(dev).contiguous() if path_weights is not None else None)
         # (a converted copy of X is a new tensor in every call: nothing to remember it by)
         whole = batch_position is None and group_slice is None
         call.features = self._features_for(X, Hk) if (X is X_given and S > 0 and whole) else None
@@ -987,7 +1044,8 @@ class _Aggregator(nn.Module):
                 if first and self._range_wide:      # the very first result is not handed out on a range it cannot carry
                     return self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=False, group_slice=group_slice,
                                      target=target, grad_scale=grad_scale, fused=fused, batch_position=batch_position,
-                                     seed=seed, _math=_lib.SEQ_MATH_BF16X3, _encode=_encode, loss=loss)
+                                     seed=seed, _math=_lib.SEQ_MATH_BF16X3, _encode=_encode, loss=loss,
+                                     path_weights=path_weights, path_weight_norm=path_weight_norm)
         return res
 
 

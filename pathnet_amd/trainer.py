@@ -54,13 +54,16 @@ def _index_tensor(mask_or_index, device):
 def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices, test_indices, num_w, hid_size,
                         walk_len, paths, round_i=0, *, epochs=1000, lr=0.005, weight_decay=0.0005, dropout=0.7,
                         device="cuda:0", save_dir="./saved_models", sampler_seed=0, model=None, verbose=False,
-                        fused_step=None, loss=None):
+                        fused_step=None, loss=None, path_weights=None):
     """paths: (ids, codes) tensors [epochs, N, W, L] (int32 / uint8, any device) or a MerwSampler.
     fused_step: True = forward, loss and backward of the training step in one library call (module.forward_loss ->
     pn_pagg_train_step), False = three calls, None = fused exactly when the batch needs micro-batches (then it saves every
     micro-batch's second forward).  Same values.
     loss: a pathnet_amd.CrossEntropyLoss (class weights, ignore_index, label smoothing) handed to forward_loss; None = the
     plain mean.  With ignore_index the training rows may hold unlabelled nodes (Y = the ignore value).
+    path_weights: a callable (ids, codes, nodes32, epoch) -> weights [S, W] of the S nodes' paths (or None for that call),
+    handed as path_weights= to the training step and to the validation and test forwards: importance weights of a biased
+    sampler, pathnet_amd.path_multiplicity, zeros for paths a check found broken.  None: the loop as it is without them.
     Returns (test macro-F1, micro-F1, macro recall, macro precision, accuracy) at the best-validation epoch."""
     dev = torch.device(device)
     loss_fn = loss          # (`loss` is the step's value below)
@@ -90,17 +93,20 @@ def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices
         def paths_of(nodes32, epoch, check=False):
             idx = nodes32.long()
             return ids_all[epoch].index_select(0, idx), codes_all[epoch].index_select(0, idx)
+    def weights_of(ids, codes, nodes32, epoch):       # the extra keyword of a call, only when the caller weights paths
+        return {} if path_weights is None else {"path_weights": path_weights(ids, codes, nodes32, epoch)}
     for epoch in range(epochs):
         model.train()
         ids_tr, codes_tr = paths_of(tr32, epoch, check=(epoch == 0))
-        loss, out = model.forward_loss(X, ids_tr, num_w, walk_len, tr32, codes_tr, Y[tr], fused=fused_step, loss=loss_fn)
+        loss, out = model.forward_loss(X, ids_tr, num_w, walk_len, tr32, codes_tr, Y[tr], fused=fused_step, loss=loss_fn,
+                                       **weights_of(ids_tr, codes_tr, tr32, epoch))
         opt.zero_grad(set_to_none=True)
         optim.backward(loss)        # = loss.backward(), minus the seed gradient's fill and multiply
         opt.step()
         with torch.no_grad():
             model.eval()
             ids_va, codes_va = paths_of(va32, epoch)
-            pred = model(X, ids_va, num_w, walk_len, va32, codes_va, None).argmax(1)
+            pred = model(X, ids_va, num_w, walk_len, va32, codes_va, None, **weights_of(ids_va, codes_va, va32, epoch)).argmax(1)
             val_acc = float((pred == Y[va]).double().mean())      # the one host round trip of an epoch
             if best_val < val_acc:
                 best_val = val_acc
@@ -108,7 +114,8 @@ def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices
                 # same X, same weights as the validation forward just above: its projected features and distance
                 # bank are still in the module's workspace (PathNet_run.py:362 and :378 recompute them)
                 ids_te, codes_te = paths_of(te32, epoch)
-                pred = model(X, ids_te, num_w, walk_len, te32, codes_te, None, reuse_tables=True).argmax(1)
+                pred = model(X, ids_te, num_w, walk_len, te32, codes_te, None, reuse_tables=True,
+                             **weights_of(ids_te, codes_te, te32, epoch)).argmax(1)
                 result = classification_metrics(Y[te], pred, num_classes)
         if verbose and (epoch % 50 == 0 or epoch == epochs - 1):
             print("epoch %d loss %.4f val_acc %.4f test_acc %.4f" % (epoch, float(loss), val_acc, result[4]))

@@ -178,6 +178,35 @@ def walk_stats(ids, codes, n, *, labels=None, num_classes=None, sources=None, vi
     return WalkStats(*(got.get(f) for f in FIELDS))
 
 
+def path_multiplicity(ids, codes=None):
+    """How often each path of a row occurs in it (pn_path_multiplicity): ids ``[..., W, L]`` (codes alike, or None) ->
+    float32 ``[..., W]`` on the device.  Entry j of a row counts the paths whose id sequence -- and code sequence, with
+    codes -- equals path j's when j is the first of them, and is 0 otherwise, so every row sums to W.  Passed as
+    ``path_weights=`` to PathNet_homo / PAGG it pools every distinct path of a node once, weighted by how often it was drawn:
+    the same value as the unweighted call.  (Not for PathNet, whose pooling slots are not its rows' paths.)
+    Limits: L <= 16, W * L <= 8192.  Enqueued on the current stream; nothing is read back."""
+    t = ids if isinstance(ids, torch.Tensor) else torch.as_tensor(ids)
+    if t.dim() < 2:
+        raise ValueError("path_multiplicity: ids of shape [..., W, L] expected, got %s" % (tuple(t.shape),))
+    dev = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    t = _int32(t, "ids", dev)
+    c = None
+    if codes is not None:
+        c = codes if isinstance(codes, torch.Tensor) else torch.as_tensor(codes)
+        if tuple(c.shape) != tuple(t.shape):
+            raise ValueError("path_multiplicity: codes of shape %s for ids of shape %s" % (tuple(c.shape), tuple(t.shape)))
+        if c.dtype != torch.uint8:
+            c = c.clamp(0, 255).to(torch.uint8)
+        c = c.to(dev).contiguous()
+    W, L = int(t.shape[-2]), int(t.shape[-1])
+    rows = t.numel() // max(W * L, 1)
+    with torch.cuda.device(dev):
+        mult = torch.empty(tuple(t.shape[:-1]), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().pn_path_multiplicity(_lib.context(dev), W, L, rows, _lib.ptr(t), _lib.ptr(c), _lib.ptr(mult),
+                                                    _lib.stream_ptr(dev)))
+    return mult
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     from . import sampler
