@@ -895,6 +895,97 @@ int pn_adam_step(const pn_adam_tensor *tensors, int32_t n_tensors, float lr, flo
 int pn_adam_step_advance(const pn_adam_tensor *tensors, int32_t n_tensors, float lr, float beta1, float beta2, float eps,
                          float weight_decay, pn_step_state *step_state /* dev */, void *stream);
 
+/* ---- optimizer options (pn_optim.hip): gradient-norm clipping, decoupled weight decay, amsgrad, a device-side learning-
+ * rate schedule and a non-finite guard -----------------------------------------------------------------------------------
+ * Added without an ABI bump: six new symbols and three new structs, no existing struct or signature changed, so
+ * pn_abi_version keeps answering 12.  pn_adam_step / pn_adam_step_advance are untouched; a call with every option off
+ * (flags 0, max_grad_norm 0, PN_LR_CONSTANT, warmup_steps 0) is their update on the new kernel (the same operations, not
+ * promised to round the same: the bias corrections are always formed on the device here).
+ * Everything here is asynchronous on `stream` and capturable: no allocation, no synchronisation, no memset, nothing read
+ * back.  No workgroup waits for another: the norm is handed from launch to launch through the state buffer.
+ *
+ * The state buffer (dev, caller-owned, pn_optim_state_bytes bytes, 8-byte aligned, ZERO before its first use) starts with a
+ * pn_optim_report and continues with the partial sums of squares (double, one per workgroup of pn_grad_norm's launches).
+ *
+ * Order of one update, per element (fp32; coef, lr_now and the bias corrections are formed in double, once per workgroup):
+ *   1. g = coef * grad                         coef = min(1, max_grad_norm / (norm + 1e-6)), torch's clip_grad_norm_;
+ *                                              the gradient in memory is NOT modified
+ *   2. L2:        g += weight_decay * p        (torch.optim.Adam)
+ *      decoupled: p *= 1 - lr_now * weight_decay, g as it is   (torch.optim.AdamW)
+ *   3. m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
+ *   4. amsgrad: vmax = max(vmax, v), and vmax stands under the square root
+ *   5. p -= lr_now / (1 - b1^step) * m / (sqrt(v or vmax) / sqrt(1 - b2^step) + eps)
+ * Schedule, with e = step - 1 (step from step_state->adam_step when a step state is given, else the argument):
+ *   lr_now = lr * warm(e) * decay(max(e - warmup_steps, 0))
+ *   warm(e) = start_factor + (1 - start_factor) * min(e, warmup_steps) / warmup_steps      (1 when warmup_steps == 0)
+ *   decay(e): PN_LR_CONSTANT 1 | PN_LR_STEP gamma^floor(e / step_size) | PN_LR_EXPONENTIAL gamma^e |
+ *             PN_LR_COSINE (lr_min + (lr - lr_min) (1 + cos(pi min(e, t_max) / t_max)) / 2) / lr
+ * The cosine stays at lr_min after t_max: the closed form of torch's CosineAnnealingLR, clamped (torch's recursion turns
+ * upwards again there; this does not).
+ * Non-finite guard, active whenever max_grad_norm != 0 (+inf: the guard alone, coef is exactly 1): when the sum of squares is
+ * not finite the call updates NOTHING -- param, exp_avg, exp_avg_sq and max_exp_avg_sq keep their bits -- and the report's
+ * `skipped` goes up by one.  The step count advances as it always does (pn_adam_step_ex_advance moves the state, the caller
+ * of pn_adam_step_ex passes the next step next time): a skipped step still uses up its place in the schedule and in the
+ * bias corrections. */
+#define PN_OPTIM_DECOUPLED_WD 1 /* pn_optim_spec.flags */
+#define PN_OPTIM_AMSGRAD 2
+#define PN_OPTIM_NO_REPORT 4    /* not the step's first update call (a further parameter group): leave the report alone */
+#define PN_LR_CONSTANT 0        /* pn_optim_spec.schedule */
+#define PN_LR_STEP 1
+#define PN_LR_EXPONENTIAL 2
+#define PN_LR_COSINE 3
+typedef struct pn_optim_spec {
+    int32_t flags;          /* PN_OPTIM_* */
+    int32_t schedule;       /* PN_LR_* */
+    float max_grad_norm;    /* 0: no clipping, the state's partial sums are not read; +inf: the non-finite guard alone */
+    int32_t reserved;       /* 0 */
+    int64_t warmup_steps;   /* >= 0 */
+    double start_factor;    /* [0, 1]: warm(0) */
+    int64_t step_size;      /* PN_LR_STEP: >= 1 */
+    double gamma;           /* PN_LR_STEP, PN_LR_EXPONENTIAL: > 0 */
+    int64_t t_max;          /* PN_LR_COSINE: >= 1 */
+    double lr_min;          /* PN_LR_COSINE: 0 <= lr_min <= lr */
+} pn_optim_spec;
+typedef struct pn_adam_tensor_ex {      /* pn_adam_tensor and amsgrad's running maximum (torch's state key max_exp_avg_sq) */
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    float *max_exp_avg_sq;  /* PN_OPTIM_AMSGRAD: dev fp32 [count], zero before step 1; otherwise not looked at */
+    int64_t count;
+} pn_adam_tensor_ex;
+typedef struct pn_optim_report {        /* the head of the state buffer; written with plain stores, read by nobody here */
+    double grad_norm;       /* the norm of the last pn_grad_norm / pn_clip_grad_norm as the last update saw it; NaN: none taken */
+    double lr;              /* lr_now of the last update */
+    float clip_coef;        /* coef of the last update (1 without clipping) */
+    int32_t n_partials;     /* partial sums behind this struct (pn_grad_norm) */
+    int64_t skipped;        /* updates the guard has skipped since the buffer was zeroed */
+} pn_optim_report;
+/* *bytes = size of the state buffer for lists of up to n_tensors tensors (total_elements: their element count, >= 0).
+ * The partial count is bounded by the launch count, not by the model: 256 per PN_ADAM_MAX_TENSORS tensors. */
+int pn_optim_state_bytes(int64_t total_elements, int32_t n_tensors, int64_t *bytes);
+/* The sum of squares of every grad of the list, accumulated in double, as per-workgroup partials in `state` (only grad and
+ * count of each tensor are looked at; at most 256 workgroups per launch, one launch per PN_ADAM_MAX_TENSORS tensors, each
+ * summing in a fixed order: the same bits in every run).  The norm itself is formed by the launches that consume it. */
+int pn_grad_norm(const pn_adam_tensor *tensors, int32_t n_tensors, void *state, void *stream);
+/* The update above.  max_grad_norm != 0 needs `state` and a pn_grad_norm on the same stream before it (taken over every
+ * parameter group's gradients when there are several: the norm is global); `state` may be NULL otherwise, and then no
+ * report is written.  Argument errors, PN_ERR_ARG before any launch: a null list / spec / pointer of a non-empty tensor,
+ * unknown flags or schedule, a negative or NaN max_grad_norm, schedule parameters outside the ranges above, step < 1
+ * without a step state. */
+int pn_adam_step_ex(const pn_adam_tensor_ex *tensors, int32_t n_tensors, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, const pn_optim_spec *spec, void *state /* dev or NULL */, int64_t step,
+                    const pn_step_state *step_state /* dev or NULL: replaces step */, void *stream);
+/* ... and the step state moved on by the update's last launch, exactly as pn_adam_step_advance does it (the same ticket
+ * in step_state->reserved) -- also on a skipped step. */
+int pn_adam_step_ex_advance(const pn_adam_tensor_ex *tensors, int32_t n_tensors, float lr, float beta1, float beta2,
+                            float eps, float weight_decay, const pn_optim_spec *spec, void *state,
+                            pn_step_state *step_state /* dev */, void *stream);
+/* torch.nn.utils.clip_grad_norm_(max_norm) in place in two launches (per PN_ADAM_MAX_TENSORS tensors): pn_grad_norm, then
+ * grad *= coef.  The report's grad_norm and clip_coef are written; max_norm > 0, +inf allowed.  A non-finite norm leaves
+ * the gradients as they are (clip_coef 1; torch would turn all of them into NaN): test grad_norm. */
+int pn_clip_grad_norm(const pn_adam_tensor *tensors, int32_t n_tensors, float max_norm, void *state, void *stream);
+
 /* Byte offsets inside the aggregator workspace of the intermediates tests look at:
  * out[0] Xh [N,H], out[1] Z [N,L,H], out[2] hn [P,H] (pooling-group order), out[3] layer1 [S,2H]. */
 int pn_pagg_debug_offsets(const pn_pagg_shape *shape, int64_t out[4]);

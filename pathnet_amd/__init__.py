@@ -4,7 +4,8 @@
   pathnet_amd.pathfile  the reference's text path-file format
   pathnet_amd.modules   PathNet / PathNet_homo / PAGG nn.Modules on hand-written HIP kernels
   pathnet_amd.dist      node sharding across the GPUs of one box (RCCL)
-  pathnet_amd.optim     CrossEntropyLoss / Adam of the reference's training step as single launches
+  pathnet_amd.optim     CrossEntropyLoss / Adam of the reference's training step as single launches; AdamW, amsgrad,
+                        gradient-norm clipping and a device-side learning-rate schedule (LRSchedule)
   pathnet_amd.trainer   train_fixed_indices with everything resident on the GPU
   pathnet_amd.walkstats statistics of sampled paths, counted on the GPU (the walkstats CLI)
   pathnet_amd.pathprob  transition probabilities and path likelihoods under the sampler's tables; importance weights
@@ -14,7 +15,8 @@ Everything computes through csrc/libpathnet_hip.so (C ABI: include/pathnet_hip.h
 """
 from . import _lib  # noqa: F401
 from .modules import PAGG, PathNet, PathNet_homo  # noqa: F401
-from .optim import Adam, CrossEntropyLoss, StepState, backward, balanced_class_weight, cross_entropy  # noqa: F401
+from .optim import (Adam, AdamW, CrossEntropyLoss, LRSchedule, StepState, backward, balanced_class_weight,  # noqa: F401
+                    clip_grad_norm_, cross_entropy)
 from .sampler import (DRAW_GLIBC_REPLAY, DRAW_PHILOX, BiasedSampler, MerwSampler, PathAnnotator,  # noqa: F401
                       PathReport, UniformSampler)
 from .pathprob import PathProb, importance_weights  # noqa: F401

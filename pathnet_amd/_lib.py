@@ -113,6 +113,30 @@ class AdamTensor(ctypes.Structure):
                 ("exp_avg_sq", ctypes.c_void_p), ("count", ctypes.c_int64)]
 
 
+OPTIM_DECOUPLED_WD, OPTIM_AMSGRAD, OPTIM_NO_REPORT = 1, 2, 4      # pn_optim_spec.flags
+LR_CONSTANT, LR_STEP, LR_EXPONENTIAL, LR_COSINE = 0, 1, 2, 3      # pn_optim_spec.schedule
+
+
+class OptimSpec(ctypes.Structure):
+    """struct pn_optim_spec: the optimizer's options (decay mode, amsgrad, clip norm, learning-rate schedule)"""
+    _fields_ = [("flags", ctypes.c_int32), ("schedule", ctypes.c_int32), ("max_grad_norm", ctypes.c_float),
+                ("reserved", ctypes.c_int32), ("warmup_steps", ctypes.c_int64), ("start_factor", ctypes.c_double),
+                ("step_size", ctypes.c_int64), ("gamma", ctypes.c_double), ("t_max", ctypes.c_int64),
+                ("lr_min", ctypes.c_double)]
+
+
+class AdamTensorEx(ctypes.Structure):
+    """struct pn_adam_tensor_ex"""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
+                ("exp_avg_sq", ctypes.c_void_p), ("max_exp_avg_sq", ctypes.c_void_p), ("count", ctypes.c_int64)]
+
+
+class OptimReport(ctypes.Structure):
+    """struct pn_optim_report: the head of the optimizer's state buffer"""
+    _fields_ = [("grad_norm", ctypes.c_double), ("lr", ctypes.c_double), ("clip_coef", ctypes.c_float),
+                ("n_partials", ctypes.c_int32), ("skipped", ctypes.c_int64)]
+
+
 SIGNATURES = {
     "pn_abi_version": (ctypes.c_int, []),
     "pn_last_error": (ctypes.c_char_p, []),
@@ -222,6 +246,15 @@ SIGNATURES = {
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int64, vp, vp]),
     "pn_adam_step_advance": (ctypes.c_int, [ctypes.POINTER(AdamTensor), ctypes.c_int32, ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp]),
+    "pn_optim_state_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, c_i64p]),
+    "pn_grad_norm": (ctypes.c_int, [ctypes.POINTER(AdamTensor), ctypes.c_int32, vp, vp]),
+    "pn_adam_step_ex": (ctypes.c_int, [ctypes.POINTER(AdamTensorEx), ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+                                       ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.POINTER(OptimSpec), vp,
+                                       ctypes.c_int64, vp, vp]),
+    "pn_adam_step_ex_advance": (ctypes.c_int, [ctypes.POINTER(AdamTensorEx), ctypes.c_int32, ctypes.c_float,
+                                               ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                               ctypes.POINTER(OptimSpec), vp, vp, vp]),
+    "pn_clip_grad_norm": (ctypes.c_int, [ctypes.POINTER(AdamTensor), ctypes.c_int32, ctypes.c_float, vp, vp]),
 }
 
 _lib = None

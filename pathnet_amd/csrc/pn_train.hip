@@ -10,6 +10,7 @@
 
 #include "../../include/pathnet_hip.h"
 #include "pn_internal.h"
+#include "pn_step_state.h"
 #include "pn_loss.h"
 
 namespace {
@@ -126,15 +127,7 @@ struct AdamList {
     int advance;                  // pn_adam_step_advance, last launch: the workgroup that finishes last moves *dyn to the next step
 };
 
-// epoch += 1, adam_step += 1, seed = splitmix64(seed)   (= step_state_advance_kernel, pn_context.hip)
-__device__ __forceinline__ void advance_step_state(pn_step_state *s) {
-    s->epoch += 1;
-    s->adam_step += 1;
-    uint64_t z = (s->seed += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    s->seed = z ^ (z >> 31);
-}
+using pn::advance_step_state;      // pn_step_state.h
 __global__ void adam_advance_only_kernel(pn_step_state *s) {
     if (threadIdx.x == 0 && blockIdx.x == 0) advance_step_state(s);
 }

@@ -2,8 +2,12 @@
 launches of the HIP library (``pn_cross_entropy``, ``pn_adam_step``): same arithmetic as ``torch.nn.CrossEntropyLoss()``
 and ``torch.optim.Adam(lr, betas, eps, weight_decay)``, ~10 us instead of ~100 us per step on the bench workload.
 Class weights, ``ignore_index`` and label smoothing go through ``pn_cross_entropy_ex`` (one launch more: the weighted
-mean's denominator, formed on the device)."""
+mean's denominator, formed on the device).  The optimizer's options -- amsgrad, decoupled weight decay (AdamW),
+gradient-norm clipping, a non-finite guard and a learning-rate schedule evaluated on the device -- go through
+``pn_grad_norm`` / ``pn_adam_step_ex`` (one launch more when a norm is wanted)."""
 import ctypes
+import math
+import struct
 
 import torch
 
@@ -189,17 +193,192 @@ class CrossEntropyLoss(torch.nn.Module):
         return _CrossEntropyEx.apply(logits, target, self)
 
 
-class Adam(torch.optim.Optimizer):
-    """Drop-in for ``torch.optim.Adam(params, lr, betas, eps, weight_decay)`` (no amsgrad / maximize): one launch
-    per step over all parameters.  State keys match torch's (``step``, ``exp_avg``, ``exp_avg_sq``)."""
+def _f32(x):
+    """the float a hyper-parameter becomes when it crosses the C ABI, as a Python double"""
+    return struct.unpack("f", struct.pack("f", float(x)))[0]
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step_state=None):
+
+class LRSchedule:
+    """A learning-rate schedule that the optimizer's kernel evaluates ON THE DEVICE from the step count (so a step captured
+    in a hipGraph replays with the learning rate of its own step).  With e = step - 1 (step counts from 1):
+
+        lr_now = lr * warm(e) * decay(max(e - warmup_steps, 0))
+        warm(e) = start_factor + (1 - start_factor) * min(e, warmup_steps) / warmup_steps        (1 without warm-up)
+
+    kind        decay(e)                                                                 torch
+    constant    1                                                                        (LinearLR for the warm-up)
+    step        gamma ** (e // step_size)                                                StepLR
+    exponential gamma ** e                                                               ExponentialLR
+    cosine      (lr_min + (lr - lr_min) * (1 + cos(pi * min(e, t_max) / t_max)) / 2) / lr   CosineAnnealingLR, closed form
+
+    The cosine stays at lr_min after t_max; torch's recursion turns upwards again there, this does not.  A value object:
+    `lr_at(base_lr, step)` is the host mirror in Python doubles -- nothing is read back from the device."""
+
+    KINDS = {"constant": _lib.LR_CONSTANT, "step": _lib.LR_STEP, "exponential": _lib.LR_EXPONENTIAL, "cosine": _lib.LR_COSINE}
+
+    def __init__(self, kind="constant", warmup_steps=0, start_factor=1.0 / 3.0, step_size=None, gamma=None, t_max=None,
+                 lr_min=0.0):
+        if kind not in self.KINDS:
+            raise ValueError("LRSchedule: kind %r (constant | step | exponential | cosine)" % (kind,))
+        if int(warmup_steps) != warmup_steps or warmup_steps < 0:
+            raise ValueError("LRSchedule: warmup_steps %r" % (warmup_steps,))
+        if not 0.0 <= float(start_factor) <= 1.0:
+            raise ValueError("LRSchedule: start_factor %r outside [0, 1]" % (start_factor,))
+        if kind == "step" and (step_size is None or int(step_size) != step_size or step_size < 1):
+            raise ValueError("LRSchedule: step needs an integer step_size >= 1 (got %r)" % (step_size,))
+        if kind in ("step", "exponential") and (gamma is None or not 0.0 < float(gamma) < math.inf):
+            raise ValueError("LRSchedule: %s needs a finite gamma > 0 (got %r)" % (kind, gamma))
+        if kind == "cosine" and (t_max is None or int(t_max) != t_max or t_max < 1):
+            raise ValueError("LRSchedule: cosine needs an integer t_max >= 1 (got %r)" % (t_max,))
+        if not 0.0 <= float(lr_min) < math.inf:
+            raise ValueError("LRSchedule: lr_min %r" % (lr_min,))
+        self.kind = kind
+        self.warmup_steps = int(warmup_steps)
+        self.start_factor = float(start_factor)
+        self.step_size = int(step_size) if step_size is not None else 1
+        self.gamma = float(gamma) if gamma is not None else 1.0
+        self.t_max = int(t_max) if t_max is not None else 1
+        self.lr_min = float(lr_min)
+
+    def check_lr(self, lr):
+        if self.kind == "cosine" and self.lr_min > _f32(lr):
+            raise ValueError("LRSchedule: lr_min %r above the learning rate %r" % (self.lr_min, lr))
+
+    def lr_at(self, base_lr, step):
+        """the learning rate of step `step` (from 1) for the base rate `base_lr` (as the kernel sees it: rounded to fp32)"""
+        lr = _f32(base_lr)
+        e = int(step) - 1
+        if e < 0:
+            raise ValueError("LRSchedule.lr_at: step counts from 1")
+        warm = 1.0
+        if self.warmup_steps > 0:
+            warm = self.start_factor + (1.0 - self.start_factor) * float(min(e, self.warmup_steps)) / float(self.warmup_steps)
+        d = max(e - self.warmup_steps, 0)
+        decay = 1.0
+        if self.kind == "step":
+            decay = self.gamma ** float(d // self.step_size)
+        elif self.kind == "exponential":
+            decay = self.gamma ** float(d)
+        elif self.kind == "cosine" and lr > 0.0:
+            c = float(min(d, self.t_max)) / float(self.t_max)
+            decay = (self.lr_min + (lr - self.lr_min) * (1.0 + math.cos(math.pi * c)) / 2.0) / lr
+        return lr * warm * decay
+
+    def fill(self, spec):
+        spec.schedule = self.KINDS[self.kind]
+        spec.warmup_steps, spec.start_factor = self.warmup_steps, self.start_factor
+        spec.step_size, spec.gamma, spec.t_max, spec.lr_min = self.step_size, self.gamma, self.t_max, self.lr_min
+
+    def __repr__(self):
+        return ("LRSchedule(%r, warmup_steps=%d, start_factor=%r, step_size=%d, gamma=%r, t_max=%d, lr_min=%r)"
+                % (self.kind, self.warmup_steps, self.start_factor, self.step_size, self.gamma, self.t_max, self.lr_min))
+
+
+def _adam_tensors(items):
+    arr = (_lib.AdamTensor * max(len(items), 1))()
+    for i, (p, g, st) in enumerate(items):
+        arr[i] = _lib.AdamTensor(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr() if st else None,
+                                 st["exp_avg_sq"].data_ptr() if st else None, p.numel())
+    return arr
+
+
+def _optim_state(device, n_tensors, total_elements):
+    """a zeroed pn_optim state buffer as float64 words: [grad_norm, lr, (clip_coef, n_partials), skipped, partials ...]"""
+    nbytes = ctypes.c_int64()
+    _lib.check(_lib.load().pn_optim_state_bytes(total_elements, n_tensors, ctypes.byref(nbytes)))
+    return torch.zeros((nbytes.value + 7) // 8, dtype=torch.float64, device=device)
+
+
+class Adam(torch.optim.Optimizer):
+    """Drop-in for ``torch.optim.Adam(params, lr, betas, eps, weight_decay)`` (no maximize): one launch per step over all
+    parameters.  State keys match torch's (``step``, ``exp_avg``, ``exp_avg_sq``, with amsgrad ``max_exp_avg_sq``), and
+    ``load_state_dict`` takes the state of a torch.optim.Adam / AdamW.
+
+    With no option set ``step()`` is ``pn_adam_step`` / ``pn_adam_step_advance``, as it always was.  The options
+    (``pn_adam_step_ex``, include/pathnet_hip.h has the order of operations):
+
+    amsgrad                    ``torch.optim.Adam(amsgrad=True)``
+    decoupled_weight_decay     ``torch.optim.AdamW``: ``p *= 1 - lr_now * weight_decay`` instead of ``g += weight_decay * p``
+    max_grad_norm              ``torch.nn.utils.clip_grad_norm_(all parameters of all groups, max_grad_norm)`` before the
+                               update, fused into it: one launch more for the norm, taken once per ``step()`` over every
+                               group's gradients; the gradients themselves are NOT modified
+    skip_nonfinite             the non-finite guard without clipping (clipping always has it): when the gradients' sum of
+                               squares is inf or NaN the step updates nothing -- parameters and state keep their bits --
+                               and ``skipped_steps`` goes up.  The step count still advances: a skipped step uses up its
+                               place in the schedule and in the bias corrections.
+    schedule                   an LRSchedule, evaluated on the device from the step count
+
+    ``last_grad_norm`` (float64; NaN when no norm is taken), ``last_lr`` (float64), ``last_clip_coef`` (float32) and
+    ``skipped_steps`` (int64) are 0-d VIEWS of the optimizer's device state buffer, None before the first ``step()``:
+    reading one (``.item()``) is the caller's synchronisation, the library reads nothing back.  The buffer is allocated at
+    the first ``step()`` and kept, so a step captured after a warm-up step stays valid."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step_state=None, *, amsgrad=False,
+                 decoupled_weight_decay=False, max_grad_norm=None, skip_nonfinite=False, schedule=None):
         """step_state (StepState): the step count of the bias corrections is read from device memory when the kernel runs
         (a step captured in a hipGraph can be replayed); state["step"] then only counts the Python-side calls."""
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("Adam: invalid hyper-parameter")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("Adam: max_grad_norm %r (a positive number, inf for the non-finite guard alone)" % (max_grad_norm,))
+        if schedule is not None:
+            if not isinstance(schedule, LRSchedule):
+                raise ValueError("Adam: schedule must be an LRSchedule")
+            schedule.check_lr(lr)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.step_state = step_state
+        self.amsgrad = bool(amsgrad)
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.schedule = schedule
+        self._optim_state = None        # the device state buffer of the option route (float64 words)
+
+    @property
+    def has_options(self):
+        return (self.amsgrad or self.decoupled_weight_decay or self.max_grad_norm is not None or self.skip_nonfinite or
+                self.schedule is not None)
+
+    @property
+    def last_grad_norm(self):
+        return None if self._optim_state is None else self._optim_state[0]
+
+    @property
+    def last_lr(self):
+        return None if self._optim_state is None else self._optim_state[1]
+
+    @property
+    def last_clip_coef(self):
+        return None if self._optim_state is None else self._optim_state[2:3].view(torch.float32)[0]
+
+    @property
+    def skipped_steps(self):
+        return None if self._optim_state is None else self._optim_state[3:4].view(torch.int64)[0]
+
+    def load_state_dict(self, state_dict):
+        """torch's, after which a ``step`` that arrived as a tensor (torch.optim's own state) is a Python int again"""
+        super().load_state_dict(state_dict)
+        for st in self.state.values():
+            if torch.is_tensor(st.get("step")):
+                st["step"] = int(st["step"].item())
+
+    def _collect(self, group):
+        todo = []
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("pathnet_amd.Adam: contiguous fp32 GPU parameters only")
+            st = self.state[p]
+            if not st:
+                st["step"] = 0
+                st["exp_avg"] = torch.zeros_like(p)
+                st["exp_avg_sq"] = torch.zeros_like(p)
+            if self.amsgrad and "max_exp_avg_sq" not in st:
+                st["max_exp_avg_sq"] = torch.zeros_like(p)
+            st["step"] += 1
+            todo.append((p, p.grad.contiguous(), st))
+        return todo
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -208,20 +387,11 @@ class Adam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         lib = _lib.load()
+        if self.has_options:
+            self._step_with_options(lib)
+            return loss
         for group in self.param_groups:
-            todo = []
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("pathnet_amd.Adam: contiguous fp32 GPU parameters only")
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p)
-                    st["exp_avg_sq"] = torch.zeros_like(p)
-                st["step"] += 1
-                todo.append((p, p.grad.contiguous(), st))
+            todo = self._collect(group)
             # tensors that have taken the same number of steps share a launch (normally: all of them)
             by_step = {}
             for item in todo:
@@ -229,10 +399,7 @@ class Adam(torch.optim.Optimizer):
             groups_left = len(by_step)
             for step, items in by_step.items():
                 groups_left -= 1
-                arr = (_lib.AdamTensor * len(items))()
-                for i, (p, g, st) in enumerate(items):
-                    arr[i] = _lib.AdamTensor(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(),
-                                             st["exp_avg_sq"].data_ptr(), p.numel())
+                arr = _adam_tensors(items)
                 ss = self.step_state
                 with torch.cuda.device(items[0][0].device):
                     if ss is not None and ss.advance_in_adam and groups_left == 0 and group is self.param_groups[-1]:
@@ -250,6 +417,92 @@ class Adam(torch.optim.Optimizer):
                 for p, _, _ in items:
                     torch.autograd.graph.increment_version(p)
         return loss
+
+    def _step_with_options(self, lib):
+        """pn_grad_norm once over every group's gradients (when a norm is wanted), then pn_adam_step_ex per group"""
+        work = []       # (group, step, items): the launches of this step, in order
+        for group in self.param_groups:
+            by_step = {}
+            for item in self._collect(group):
+                by_step.setdefault(item[2]["step"], []).append(item)
+            work += [(group, step, items) for step, items in by_step.items()]
+        everything = [item for _, _, items in work for item in items]
+        if not everything:
+            return
+        device = everything[0][0].device
+        if any(p.device != device for p, _, _ in everything):
+            raise RuntimeError("pathnet_amd.Adam: the gradient norm is global -- every parameter on one device")
+        if self._optim_state is None:
+            # sized once, for every parameter of every group: a later step with more gradients than the first still fits
+            every = [p for group in self.param_groups for p in group["params"]]
+            self._optim_state = _optim_state(device, len(every), sum(p.numel() for p in every))
+        state = _lib.ptr(self._optim_state)
+        max_norm = self.max_grad_norm if self.max_grad_norm is not None else (math.inf if self.skip_nonfinite else 0.0)
+        flags = ((_lib.OPTIM_DECOUPLED_WD if self.decoupled_weight_decay else 0) | (_lib.OPTIM_AMSGRAD if self.amsgrad else 0))
+        ss = self.step_state
+        with torch.cuda.device(device):
+            if max_norm != 0.0:
+                _lib.check(lib.pn_grad_norm(_adam_tensors(everything), len(everything), state, _stream()))
+            for k, (group, step, items) in enumerate(work):
+                spec = _lib.OptimSpec(flags=flags | (_lib.OPTIM_NO_REPORT if k else 0), max_grad_norm=max_norm,
+                                      start_factor=1.0, step_size=1, gamma=1.0, t_max=1)
+                if self.schedule is not None:
+                    self.schedule.check_lr(group["lr"])
+                    self.schedule.fill(spec)
+                arr = (_lib.AdamTensorEx * len(items))()
+                for i, (p, g, st) in enumerate(items):
+                    vmax = st["max_exp_avg_sq"].data_ptr() if self.amsgrad else None
+                    arr[i] = _lib.AdamTensorEx(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(),
+                                               st["exp_avg_sq"].data_ptr(), vmax, p.numel())
+                hyper = (group["lr"], group["betas"][0], group["betas"][1], group["eps"], group["weight_decay"])
+                if ss is not None and ss.advance_in_adam and k == len(work) - 1:
+                    _lib.check(lib.pn_adam_step_ex_advance(arr, len(items), *hyper, ctypes.byref(spec), state, ss.ptr(),
+                                                           _stream()))
+                    ss._advanced_by_adam = True
+                else:
+                    _lib.check(lib.pn_adam_step_ex(arr, len(items), *hyper, ctypes.byref(spec), state, step,
+                                                   ss.ptr() if ss is not None else None, _stream()))
+                for p, _, _ in items:       # (see step(): the version counters of what the kernel wrote)
+                    torch.autograd.graph.increment_version(p)
+
+
+class AdamW(Adam):
+    """``torch.optim.AdamW``: pathnet_amd.Adam with decoupled weight decay and torch's default ``weight_decay=1e-2``;
+    every other option as there."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, step_state=None, *, amsgrad=False,
+                 max_grad_norm=None, skip_nonfinite=False, schedule=None):
+        super().__init__(params, lr, betas, eps, weight_decay, step_state, amsgrad=amsgrad, decoupled_weight_decay=True,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, schedule=schedule)
+
+
+def clip_grad_norm_(parameters, max_norm):
+    """``torch.nn.utils.clip_grad_norm_(parameters, max_norm)`` (the 2-norm) in place, in two launches and without a host
+    read: the sum of squares in float64, then ``grad *= min(1, max_norm / (norm + 1e-6))``.  Returns the norm before
+    clipping as a 0-d float64 device tensor.  A non-finite norm leaves the gradients as they are (torch turns all of them
+    into NaN): test the returned norm, or let the optimizer's ``skip_nonfinite`` skip the step."""
+    if not float(max_norm) > 0.0:
+        raise ValueError("clip_grad_norm_: max_norm %r" % (max_norm,))
+    if torch.is_tensor(parameters):
+        parameters = [parameters]
+    items = []
+    for p in parameters:
+        g = p.grad
+        if g is None:
+            continue
+        if not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous():
+            raise RuntimeError("pathnet_amd.clip_grad_norm_: contiguous fp32 GPU gradients only")
+        items.append((g, g, None))
+    if not items:
+        return torch.zeros((), dtype=torch.float64)
+    device = items[0][0].device
+    if any(g.device != device for g, _, _ in items):
+        raise RuntimeError("pathnet_amd.clip_grad_norm_: every gradient on one device")
+    state = _optim_state(device, len(items), sum(g.numel() for g, _, _ in items))
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().pn_clip_grad_norm(_adam_tensors(items), len(items), float(max_norm), _lib.ptr(state),
+                                                 _stream()))
+    return state[0]
 
 
 class StepState:

@@ -54,7 +54,7 @@ def _index_tensor(mask_or_index, device):
 def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices, test_indices, num_w, hid_size,
                         walk_len, paths, round_i=0, *, epochs=1000, lr=0.005, weight_decay=0.0005, dropout=0.7,
                         device="cuda:0", save_dir="./saved_models", sampler_seed=0, model=None, verbose=False,
-                        fused_step=None, loss=None, path_weights=None):
+                        fused_step=None, loss=None, path_weights=None, optimizer=None):
     """paths: (ids, codes) tensors [epochs, N, W, L] (int32 / uint8, any device) or a MerwSampler.
     fused_step: True = forward, loss and backward of the training step in one library call (module.forward_loss ->
     pn_pagg_train_step), False = three calls, None = fused exactly when the batch needs micro-batches (then it saves every
@@ -64,6 +64,8 @@ def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices
     path_weights: a callable (ids, codes, nodes32, epoch) -> weights [S, W] of the S nodes' paths (or None for that call),
     handed as path_weights= to the training step and to the validation and test forwards: importance weights of a biased
     sampler, pathnet_amd.path_multiplicity, zeros for paths a check found broken.  None: the loop as it is without them.
+    optimizer: a callable (parameters) -> optimizer that replaces the built-in Adam(lr, weight_decay) -- pathnet_amd.AdamW
+    with max_grad_norm= and schedule=, say; called once, with the model's parameters.  None: the loop as it is.
     Returns (test macro-F1, micro-F1, macro recall, macro precision, accuracy) at the best-validation epoch."""
     dev = torch.device(device)
     loss_fn = loss          # (`loss` is the step's value below)
@@ -73,7 +75,10 @@ def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices
     if model is None:
         cls = modules.PathNet_homo if data_name in HOMO_DATASETS else modules.PathNet
         model = cls(X.shape[-1], hid_size, num_classes, walk_len, dropout=dropout).to(dev)
-    opt = optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)     # = torch.optim.Adam, one launch
+    if optimizer is None:
+        opt = optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)     # = torch.optim.Adam, one launch
+    else:
+        opt = optimizer(model.parameters())
     from_sampler = hasattr(paths, "sample")
     if not from_sampler:
         ids_all, codes_all = (torch.as_tensor(t).to(dev) for t in paths)
