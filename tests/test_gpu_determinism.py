@@ -4,7 +4,9 @@ is BITWISE equal, and equals the default (atomic) backward within the parity tol
 
 The reference has no such switch -- its gather backward is torch's embedding / index_select backward, whose CUDA kernels
 add with atomics too (PathNet_run.py:164,185-197 via autograd) -- so the contract here is torch's own for
-torch.use_deterministic_algorithms(True): same inputs, same bits."""
+torch.use_deterministic_algorithms(True): same inputs, same bits.
+
+The chunk and run edges of det_scatter_kernel itself (exact counts on every route): tests/test_gpu_scatter_exact.py."""
 import os
 
 import numpy as np
