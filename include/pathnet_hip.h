@@ -986,6 +986,79 @@ int pn_adam_step_ex_advance(const pn_adam_tensor_ex *tensors, int32_t n_tensors,
  * the gradients as they are (clip_coef 1; torch would turn all of them into NaN): test grad_norm. */
 int pn_clip_grad_norm(const pn_adam_tensor *tensors, int32_t n_tensors, float max_norm, void *state, void *stream);
 
+/* ---- ensemble prediction over resampled paths (pn_ensemble.hip) ---------------------------------------------------------
+ * The logits of a node depend on the W paths the sampler drew for it.  K draws give K logit rows per node; these calls
+ * average their class probabilities on the device and say how much the draws disagree.  Added without an ABI bump: four
+ * new symbols and one new struct, no existing struct or signature changed, so pn_abi_version keeps answering 12.
+ *
+ * The state is ONE caller-owned device allocation of pn_ensemble_state_bytes(rows, C) = rows * (12 C + 16) bytes, 8-byte
+ * aligned, laid out as
+ *     double  psum [rows, C]   sum over the samples of the class probabilities
+ *     double  hsum [rows]      sum over the samples of the sample's entropy
+ *     int32_t votes[rows, C]   samples whose largest logit is class c
+ *     int32_t count[rows]      samples added
+ *     int32_t bad  [rows]      samples refused because a logit was not finite
+ * in that order without padding.  All zeros is the empty ensemble: the caller clears it with a memset.
+ *
+ * pn_ensemble_add: logits is dev fp32 [R, S, C], R samples of the same S rows, sample-major, contiguous.  Logits row s
+ * belongs to state row index[s] (dev int32 [S]; NULL: row s, which needs S <= rows).  For every (r, s), in ascending r for
+ * a fixed s, by the one thread group that owns the row:
+ *   - any of the C logits NaN or +-inf: bad[row] += 1 and nothing else of the row is touched for this sample;
+ *   - otherwise, in fp64 on the converted logits: m = max x, e_c = exp(x_c - m), Z = sum e_c, p_c = e_c / Z;
+ *     psum[row, c] += p_c;  votes[row, argmax_c x_c] += 1 (the logits themselves, lowest c on ties);
+ *     hsum[row] += -sum_c p_c log p_c (0 log 0 = 0);  count[row] += 1.
+ * Sums over c: ascending c for C <= 16; above that every lane adds its classes (lane, lane + 64 ... or + 256 ...) in
+ * ascending c, the lanes meet in a fixed butterfly and a workgroup's four waves as (w0 + w1) + (w2 + w3): an order that
+ * depends on C alone.  There is no floating-point atomic, the result does not depend on the launch geometry, and one call
+ * with [R, S, C] leaves the bits of R calls with [1, S, C] in the same order.
+ * An index entry outside [0, rows) skips its logits rows and adds R (one per skipped logits row) to status[0] (dev int32,
+ * may be NULL).  The same state row named twice in one call is a caller error (two groups would own it).
+ *
+ * pn_ensemble_finish reads the state and writes what pn_ensemble_out names; every pointer may be NULL = not written.
+ * Without a subset it finishes rows 0 .. rows-1 and output j describes row j; with subset (dev int32 [subset_rows]) output j
+ * describes row subset[j] (repeats allowed; an entry outside [0, rows) is an empty row), so one state of N rows serves a
+ * validation and a test mask.  With n = count[row], for n > 0:
+ *   prob[j, c]      fp32   psum / n
+ *   label[j]        int64  argmax_c psum, lowest c on ties
+ *   vote_label[j]   int64  argmax_c votes, lowest c on ties
+ *   confidence[j]   fp32   psum[label] / n
+ *   entropy[j]      fp32   -sum_c q log q of the mean distribution q = psum / n, in fp64, rounded once
+ *   mutual_info[j]  fp32   max(0, entropy - hsum / n): the part of the uncertainty that comes from the path draw
+ *   agreement[j]    fp32   votes[label] / n
+ * and for n == 0 zeros and the labels -1.  target (dev int64 [rows], indexed by STATE row, may be NULL) adds
+ *   confusion[t, label] += 1 (int64 [C, C]) for rows with 0 <= t < C and label >= 0, t = target[row];
+ *   skipped[0] += 1 for a target outside [0, C), skipped[1] += 1 for label == -1 (a row can count in both).
+ * Both are ADDED to with integer atomics (exact, order-free): the caller zeroes them, or keeps them to sum several calls.
+ *
+ * Limits, refused with PN_ERR_ARG before any device call: 1 <= C <= 4096, 0 <= rows, S, subset_rows < 2^31, R >= 1, S > rows
+ * without an index, confusion or skipped without a target, subset_rows != 0 without a subset, NULL logits / state / out
+ * where they would be read.  rows == 0 and S == 0 are valid and launch nothing.  Asynchronous on `stream`; nothing is read
+ * back and nothing is allocated, so a captured step may contain them.  pn_ensemble_state_bytes and pn_ensemble_route need
+ * no device.  The route is the work split a shape takes (it depends on C; rows == 0 launches nothing): */
+#define PN_ENSEMBLE_ROUTE_NONE 0   /* rows == 0 */
+#define PN_ENSEMBLE_ROUTE_THREAD 1 /* C <= 16: a thread per row */
+#define PN_ENSEMBLE_ROUTE_WAVE 2   /* 16 < C <= 1024: a wave per row */
+#define PN_ENSEMBLE_ROUTE_BLOCK 3  /* 1024 < C <= 4096: a workgroup per row */
+typedef struct pn_ensemble_out {   /* device pointers, caller-owned, each may be NULL; n = rows, or subset_rows with a subset */
+    float *prob;                   /* [n, C] */
+    int64_t *label;                /* [n] */
+    int64_t *vote_label;           /* [n] */
+    float *confidence;             /* [n] */
+    float *entropy;                /* [n] */
+    float *mutual_info;            /* [n] */
+    float *agreement;              /* [n] */
+    int64_t *confusion;            /* [C, C], added to; needs target */
+    int64_t *skipped;              /* [2], added to; needs target */
+} pn_ensemble_out;
+int pn_ensemble_state_bytes(int64_t rows, int32_t C, int64_t *bytes);
+int pn_ensemble_route(int64_t rows, int32_t C, int32_t *route);
+int pn_ensemble_add(pn_context *ctx, const float *logits /* dev [R, S, C] */, int32_t R, int64_t S, int32_t C,
+                    const int32_t *index /* dev [S] or NULL */, int64_t rows, void *state, int32_t *status /* dev or NULL */,
+                    void *stream);
+int pn_ensemble_finish(pn_context *ctx, int64_t rows, int32_t C, const void *state,
+                       const int32_t *subset /* dev [subset_rows] or NULL */, int64_t subset_rows,
+                       const int64_t *target /* dev [rows] or NULL */, const pn_ensemble_out *out, void *stream);
+
 /* Byte offsets inside the aggregator workspace of the intermediates tests look at:
  * out[0] Xh [N,H], out[1] Z [N,L,H], out[2] hn [P,H] (pooling-group order), out[3] layer1 [S,2H]. */
 int pn_pagg_debug_offsets(const pn_pagg_shape *shape, int64_t out[4]);

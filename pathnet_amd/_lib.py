@@ -91,6 +91,15 @@ class PathProbOut(ctypes.Structure):
     _fields_ = [(k, vp) for k in FIELDS]
 
 
+class EnsembleOut(ctypes.Structure):
+    """struct pn_ensemble_out: device pointers, None = not wanted"""
+    FIELDS = ("prob", "label", "vote_label", "confidence", "entropy", "mutual_info", "agreement", "confusion", "skipped")
+    _fields_ = [(k, vp) for k in FIELDS]
+
+
+ENSEMBLE_ROUTE_NONE, ENSEMBLE_ROUTE_THREAD, ENSEMBLE_ROUTE_WAVE, ENSEMBLE_ROUTE_BLOCK = 0, 1, 2, 3   # pn_ensemble_route
+
+
 class PathWeights(ctypes.Structure):
     """struct pn_path_weights: per-path weights of the pooling (dev fp32 [S_total, W]) and their normalisation (PATH_NORM_*)"""
     _fields_ = [("weight", vp), ("norm", ctypes.c_int32)]
@@ -255,6 +264,12 @@ SIGNATURES = {
                                                ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                ctypes.POINTER(OptimSpec), vp, vp, vp]),
     "pn_clip_grad_norm": (ctypes.c_int, [ctypes.POINTER(AdamTensor), ctypes.c_int32, ctypes.c_float, vp, vp]),
+    "pn_ensemble_state_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, c_i64p]),
+    "pn_ensemble_route": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, c_i32p]),
+    "pn_ensemble_add": (ctypes.c_int, [vp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int64, vp, vp,
+                                       vp]),
+    "pn_ensemble_finish": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, vp, vp, ctypes.c_int64, vp,
+                                          ctypes.POINTER(EnsembleOut), vp]),
 }
 
 _lib = None

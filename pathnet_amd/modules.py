@@ -849,6 +849,41 @@ class _Aggregator(nn.Module):
             ps = ps[:, :, :H].contiguous() if ps is not None else None
         return Encoded(logits, emb, pw, ps)
 
+    def predict(self, X, paths, num_w, walk_len, nodes=None, *, samples=8, seed=0, first_epoch=0, batch_nodes=None,
+                samples_per_call=None, labels=None, path_weights=None, path_weight_norm="sum", ensemble=None,
+                reuse_tables=False):
+        """Ensemble prediction: ``samples`` independent path draws per node, their class probabilities averaged on the
+        device (pathnet_amd.Ensemble: fp64 softmax and sums, no read-back) -> ``pathnet_amd.Prediction`` of device tensors
+        (prob, label, vote_label, confidence, entropy, mutual_info, agreement, count, bad, confusion, skipped), one row per
+        node of `nodes` in their order.
+
+        paths: a sampler (anything with ``.sample``, ``smp.biased(p, q)`` included) -- sample k draws epoch_begin =
+        first_epoch + k with ``nodes=`` and `seed` -- or pre-sampled ``(ids, codes)`` tensors ``[E, N, W, L]``, where sample k
+        is epoch ``(first_epoch + k) % E``.  nodes: a bool mask or node ids (forward()'s rules); default all N nodes.
+        labels (int, per node of X or per node of `nodes`): also the confusion matrix [true, predicted] and the skipped counts.
+        path_weights: a callable ``(ids, codes, nodes32, k) -> [S, W]`` or None, as the trainer's.
+        ensemble: an Ensemble of len(nodes) rows to continue -- more samples later (a new first_epoch), or several checkpoints
+        averaged; the returned Prediction describes everything it holds.
+        reuse_tables (extension, forward()'s): X and the weights are those of this module's previous no-grad forward, so
+        the first forward of this call reuses the tables too (a test predict right after the validation predict).
+
+        The forwards run under no_grad in eval mode (no dropout, torch's generator untouched); the module's training flag is
+        restored afterwards.  PathNet_homo / PAGG, where a row depends on its own paths only: the nodes are taken in chunks of
+        batch_nodes (default: all of them; a batch beyond the workspace budget runs in the library's own micro-batches), and
+        up to samples_per_call samples of a chunk share ONE forward, the chunk's node list tiled R times (default: as many
+        as keep a call at about 32 K rows).  Every forward after the first reuses the projected features and the distance bank
+        (reuse_tables): fc0 and the bank run once per predict.  Stacked and single calls may take different GEMM routes, so
+        their probabilities agree to rounding, not to the bit.
+        PathNet (the hetero class): a row reads paths of other masked nodes of its batch, so its
+        prediction is a property of (node, batch), as in the reference.  Every sample is the reference's single whole-batch
+        forward over `nodes`; batch_nodes only cuts it into group_slice pieces with the same values, and samples_per_call is
+        ignored -- samples are never stacked."""
+        from . import ensemble as ens
+        return ens.predict_with(self, X, paths, num_w, walk_len, nodes, samples=samples, seed=seed, first_epoch=first_epoch,
+                                batch_nodes=batch_nodes, samples_per_call=samples_per_call, labels=labels,
+                                path_weights=path_weights, path_weight_norm=path_weight_norm, ensemble=ensemble,
+                                reuse_tables=reuse_tables)
+
     def paths_stream(self):
         """The torch stream on which this module's NEXT call will read its path arrays (neis / layer_type), judged by the
         shape of its last call on the current stream (pn_pagg_paths_stream): the library's second stream when the call forks

@@ -29,6 +29,13 @@ def classification_metrics(y_true, y_pred, num_classes):
     y_true, y_pred = y_true.reshape(-1).long(), y_pred.reshape(-1).long()
     conf = torch.bincount(y_true * num_classes + y_pred, minlength=num_classes * num_classes).view(
         num_classes, num_classes).double()
+    return metrics_from_confusion(conf)
+
+
+def metrics_from_confusion(conf):
+    """classification_metrics' tuple from a confusion matrix [true, predicted] (any real dtype, any device): the matrix an
+    Ensemble counts on the device (Prediction.confusion) needs no per-sample read-back."""
+    conf = torch.as_tensor(conf).double()
     tp = conf.diag()
     support, predicted = conf.sum(1), conf.sum(0)
     present = (support + predicted) > 0
@@ -51,10 +58,26 @@ def _index_tensor(mask_or_index, device):
     return t.to(device=device, dtype=torch.int64)
 
 
+class _EvalDraws:
+    """The sampler as train_fixed_indices(eval_samples=K) hands it to model.predict: sample 0 of epoch e is the epoch's own
+    draw, samples 1 .. K-1 come from epochs behind the training run's, epochs + e (K-1) + (k-1), which no step uses."""
+
+    def __init__(self, sampler, epoch, epochs, K):
+        self.sampler, self.epoch, self.epochs, self.K = sampler, int(epoch), int(epochs), int(K)
+
+    def epoch_of(self, k):
+        return self.epoch if k == 0 else self.epochs + self.epoch * (self.K - 1) + (k - 1)
+
+    def sample(self, num_w, seed, epoch_begin=0, epoch_count=1, **kw):
+        if epoch_count != 1:
+            raise ValueError("one epoch per call")
+        return self.sampler.sample(num_w, seed, epoch_begin=self.epoch_of(int(epoch_begin)), epoch_count=1, **kw)
+
+
 def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices, test_indices, num_w, hid_size,
                         walk_len, paths, round_i=0, *, epochs=1000, lr=0.005, weight_decay=0.0005, dropout=0.7,
                         device="cuda:0", save_dir="./saved_models", sampler_seed=0, model=None, verbose=False,
-                        fused_step=None, loss=None, path_weights=None, optimizer=None):
+                        fused_step=None, loss=None, path_weights=None, optimizer=None, eval_samples=1):
     """paths: (ids, codes) tensors [epochs, N, W, L] (int32 / uint8, any device) or a MerwSampler.
     fused_step: True = forward, loss and backward of the training step in one library call (module.forward_loss ->
     pn_pagg_train_step), False = three calls, None = fused exactly when the batch needs micro-batches (then it saves every
@@ -66,6 +89,12 @@ def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices
     sampler, pathnet_amd.path_multiplicity, zeros for paths a check found broken.  None: the loop as it is without them.
     optimizer: a callable (parameters) -> optimizer that replaces the built-in Adam(lr, weight_decay) -- pathnet_amd.AdamW
     with max_grad_norm= and schedule=, say; called once, with the model's parameters.  None: the loop as it is.
+    eval_samples: K > 1 scores validation and test of an epoch with a K-sample ensemble (model.predict with labels=Y: fp64
+    mean of the class probabilities, confusion matrix counted on the device) instead of one draw.  Sample 0 of epoch e is
+    today's draw (sampler and tensors: epoch e); samples k = 1 .. K-1 draw from epochs no training step uses -- sampler:
+    epochs + e (K-1) + (k-1); tensors: (e + k) % E, which REUSES other epochs' paths.  path_weights then sees that epoch
+    number.  The validation accuracy is the trace of the confusion matrix over its sum: one host read per epoch, as now.
+    1: the loop exactly as it is without the keyword.
     Returns (test macro-F1, micro-F1, macro recall, macro precision, accuracy) at the best-validation epoch."""
     dev = torch.device(device)
     loss_fn = loss          # (`loss` is the step's value below)
@@ -100,6 +129,28 @@ def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices
             return ids_all[epoch].index_select(0, idx), codes_all[epoch].index_select(0, idx)
     def weights_of(ids, codes, nodes32, epoch):       # the extra keyword of a call, only when the caller weights paths
         return {} if path_weights is None else {"path_weights": path_weights(ids, codes, nodes32, epoch)}
+    K = int(eval_samples)
+    if K < 1:
+        raise ValueError("eval_samples=%d, at least 1" % K)
+
+    def ensemble_eval(epoch, best_val):
+        """eval_samples > 1: -> (validation accuracy, test metrics when it beats best_val, else None)"""
+        if from_sampler:
+            draws, first = _EvalDraws(paths, epoch, epochs, K), 0
+            epoch_of = draws.epoch_of
+        else:
+            draws, first = (ids_all, codes_all), epoch
+            epoch_of = lambda k: (epoch + k) % int(ids_all.shape[0])        # noqa: E731
+        weigh = None if path_weights is None else (lambda ids, codes, nodes32, k: path_weights(ids, codes, nodes32, epoch_of(k)))
+        kw = dict(samples=K, seed=sampler_seed, first_epoch=first, labels=Y, path_weights=weigh)
+        conf = model.predict(X, draws, num_w, walk_len, va32, **kw).confusion.double()
+        val_acc = float(conf.diag().sum() / conf.sum().clamp(min=1))      # the one host round trip of an epoch
+        if not best_val < val_acc:
+            return val_acc, None
+        torch.save(model.state_dict(), ckpt)
+        # (same X, same weights as the validation forwards just above: the test forwards reuse their tables)
+        return val_acc, metrics_from_confusion(model.predict(X, draws, num_w, walk_len, te32, reuse_tables=True, **kw).confusion)
+
     for epoch in range(epochs):
         model.train()
         ids_tr, codes_tr = paths_of(tr32, epoch, check=(epoch == 0))
@@ -110,18 +161,24 @@ def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices
         opt.step()
         with torch.no_grad():
             model.eval()
-            ids_va, codes_va = paths_of(va32, epoch)
-            pred = model(X, ids_va, num_w, walk_len, va32, codes_va, None, **weights_of(ids_va, codes_va, va32, epoch)).argmax(1)
-            val_acc = float((pred == Y[va]).double().mean())      # the one host round trip of an epoch
-            if best_val < val_acc:
-                best_val = val_acc
-                torch.save(model.state_dict(), ckpt)
-                # same X, same weights as the validation forward just above: its projected features and distance
-                # bank are still in the module's workspace (PathNet_run.py:362 and :378 recompute them)
-                ids_te, codes_te = paths_of(te32, epoch)
-                pred = model(X, ids_te, num_w, walk_len, te32, codes_te, None, reuse_tables=True,
-                             **weights_of(ids_te, codes_te, te32, epoch)).argmax(1)
-                result = classification_metrics(Y[te], pred, num_classes)
+            if K > 1:
+                val_acc, improved = ensemble_eval(epoch, best_val)
+                if improved is not None:
+                    best_val, result = val_acc, improved
+            else:
+                ids_va, codes_va = paths_of(va32, epoch)
+                pred = model(X, ids_va, num_w, walk_len, va32, codes_va, None,
+                             **weights_of(ids_va, codes_va, va32, epoch)).argmax(1)
+                val_acc = float((pred == Y[va]).double().mean())      # the one host round trip of an epoch
+                if best_val < val_acc:
+                    best_val = val_acc
+                    torch.save(model.state_dict(), ckpt)
+                    # same X, same weights as the validation forward just above: its projected features and distance
+                    # bank are still in the module's workspace (PathNet_run.py:362 and :378 recompute them)
+                    ids_te, codes_te = paths_of(te32, epoch)
+                    pred = model(X, ids_te, num_w, walk_len, te32, codes_te, None, reuse_tables=True,
+                                 **weights_of(ids_te, codes_te, te32, epoch)).argmax(1)
+                    result = classification_metrics(Y[te], pred, num_classes)
         if verbose and (epoch % 50 == 0 or epoch == epochs - 1):
             print("epoch %d loss %.4f val_acc %.4f test_acc %.4f" % (epoch, float(loss), val_acc, result[4]))
     if os.path.exists(ckpt):
