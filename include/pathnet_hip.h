@@ -1059,6 +1059,92 @@ int pn_ensemble_finish(pn_context *ctx, int64_t rows, int32_t C, const void *sta
                        const int32_t *subset /* dev [subset_rows] or NULL */, int64_t subset_rows,
                        const int64_t *target /* dev [rows] or NULL */, const pn_ensemble_out *out, void *stream);
 
+/* ---- explanations: exact path and group occlusion (pn_explain.hip) --------------------------------------------------------
+ * What would the model say without some of a node's paths, or with those paths alone?  pn_path_weights answers with one
+ * forward per question.  None of that is needed: the recurrence never sees the pooling, leaving members out of a row changes
+ * only the pooling's normalisation and which terms enter the sum, and the classifier is linear after it.  These calls
+ * evaluate the closed form for all groups of all rows in one pass over the final hidden states.  Added without an ABI bump:
+ * three new symbols and one new struct, no existing struct or signature changed, so pn_abi_version keeps answering 12.
+ *
+ * Row s has members j = 0 .. W-1 in encode()'s member order (out_path_weight's): for HOMO / PAGG path j of masked node s,
+ * for HETERO slot q = j * S + s.  Inputs, dev fp32 unless noted:
+ *   state  [S, W, ld_state]  final hidden states, the first H entries of a member's row are used
+ *   coef   [S, W]            the coefficient applied (out_path_weight: already kappa w c)
+ *   ego    [S, ld_ego]       the first H entries of a row are used (the ego half of the embedding)
+ *   fc2_w  [C, ld_w]         columns 0 .. H-1 multiply ego, columns H .. 2H-1 multiply pooled;  fc2_b [C]
+ *   weight [S, W] or NULL    the caller's path weights IN MEMBER ORDER.  A member is live when weight is NULL or its entry is a
+ *                            finite positive number
+ *   group  [S, W] int32      a value outside [0, G): the member belongs to no group -- never removed, never kept alone
+ *   norm   PN_PATH_NORM_*;   renorm  1 for HETERO, whose softmax renormalises over the remaining members, 0 for HOMO / PAGG
+ *   target [S] int64 or NULL NULL: the argmax of the full logits, lowest class on ties
+ * All arithmetic is fp64 on the converted inputs:
+ *   t_j[c] = sum_h fc2_w[c, H+h] state[s,j,h]            e[c] = fc2_b[c] + sum_h fc2_w[c,h] ego[s,h]
+ *   contribution[s,j,c] = coef_j t_j[c] / W               full[c] = e[c] + sum_j contribution[s,j,c]     (every j)
+ *   R = live members with group_j == g;   present[s,g] = |R|
+ *   Om = sum_live w_j (w = 1 without weights), Om_R, Om_rest (live, not in R);   K = sum_live coef_j, K_R, K_rest
+ *   drop_g[c] = e[c] + rho_d sum_{live, not in R} contribution[.,c],  rho_d = (norm == SUM ? Om / Om_rest : 1) (renorm ? K / K_rest : 1)
+ *   keep_g[c] = e[c] + rho_k sum_{j in R} contribution[.,c],           rho_k = (norm == SUM ? Om / Om_R : 1) (renorm ? K / K_R : 1)
+ * Edge rules.  R empty: drop_g = full, bit for bit (rho_d = 1 exactly and the sum runs over every j, as full's does; a dead
+ * member's coefficient is 0 in what the library reports).  No live member remains, or renorm and the remaining coefficient
+ * mass is not > 0: the pooled part is zero and the logits are e -- the library's rule for a group without a live path.  The
+ * sums Om_rest, K_rest and the logit sum over the remaining members are formed by direct summation, never by subtraction.
+ * With lp(x) = x_t - logsumexp(x) for the row's target t:
+ *   drop_delta[s,g] = lp(full) - lp(drop_g)     positive: the group supports the class
+ *   keep_gain[s,g]  = lp(keep_g) - lp(e)
+ *   flip[s,g]       = argmax(drop_g) != argmax(full) (lowest class on ties) and present > 0
+ *   target_used[s]  = t
+ * A target outside [0, C): the row's drop_delta and keep_gain are 0, flip is 0 and status[0] += 1 (dev int32 [2], may be
+ * NULL; added to).  A row in which any value read of state, coef, ego, fc2_w or fc2_b is not finite is a bad row: every float
+ * output of the row is NaN, flip is 0, present is still counted, status[1] += 1 (and not status[0]), and target_used is the
+ * target given, or -1 without one.
+ * fp32 outputs are the fp64 value rounded once; a NULL pointer of pn_explain_out is not computed and not written, and
+ * drop_delta / keep_gain / flip need no logits stored.
+ *
+ * Order of the sums: dot products in ascending h; sums over members in ascending j; a logit vector's logsumexp by the
+ * lanes that share it (8 for C <= 8, 16 for C <= 16, else 64), each keeping a running (max, sum of exp) over its classes
+ * c = lane, lane + lanes, ...; the lanes' maxima meet in a butterfly, every lane rescales its sum to the common maximum,
+ * the sums meet in a butterfly, and with class chunks one further merge per chunk.  All of it
+ * depends on (W, H, C, G) alone: there is no floating-point atomic, a row's result does not depend on the launch geometry or
+ * on the other rows of the call, and the rows split over two calls leave the bits of one call.
+ * Work split: one workgroup owns a row; the row's states go through LDS once, in 16-byte loads where ld_state and the
+ * address allow, fc2_w's rows beside them, t_j stays in LDS.  pn_explain_route reports {route, lanes, class chunk, H tile}:
+ * the class chunk is min(C, 4096 / (W + 1)) -- below C the route is CHUNKED and state is read once per chunk -- and the H tile
+ * the largest Ht with (W + 1 + 2 chunk) (Ht | 1) <= 7168, a multiple of 4 when below H.
+ *
+ * pn_explain_totals adds a call's rows (all S, or rows [n_rows] int32; an entry outside [0, S) is skipped) into a caller-
+ * zeroed state of 40 G bytes, 8-byte aligned:
+ *     int64 rows_present[G], members[G], flips[G];  double drop_delta_sum[G], keep_gain_sum[G]
+ * over the rows with present > 0 and finite drop_delta and keep_gain.  One workgroup owns a group: it adds the call's rows in
+ * ascending order in fp64, then adds once into the running total, so the bits depend on the sequence of calls alone.  The
+ * integer totals are exact.
+ *
+ * Limits, refused with PN_ERR_ARG before any device call: 1 <= W, G <= 1024, 1 <= H <= 4096, 1 <= C <= 1024, 0 <= S < 2^31,
+ * ld_state, ld_ego >= H, ld_w >= 2 H, norm and renorm as above, NULL where something would be read, n_rows != 0 without rows.
+ * S == 0 launches nothing.  Asynchronous on `stream`, nothing read back, nothing allocated. */
+#define PN_EXPLAIN_ROUTE_NONE 0    /* S == 0 */
+#define PN_EXPLAIN_ROUTE_ROW 1     /* every class in one chunk: state is read once */
+#define PN_EXPLAIN_ROUTE_CHUNKED 2 /* (W + 1) * C > 4096: classes in chunks */
+typedef struct pn_explain_out {    /* device pointers, caller-owned, each may be NULL */
+    float *full;                   /* [S, C] */
+    float *contribution;           /* [S, W, C] */
+    float *drop_logits;            /* [S, G, C] */
+    float *keep_logits;            /* [S, G, C] */
+    float *drop_delta;             /* [S, G] */
+    float *keep_gain;              /* [S, G] */
+    uint8_t *flip;                 /* [S, G] */
+    int32_t *present;              /* [S, G] */
+    int64_t *target_used;          /* [S] */
+} pn_explain_out;
+int pn_explain_route(int64_t S, int32_t W, int32_t H, int32_t C, int32_t G, int32_t route[4]);
+int pn_explain_groups(pn_context *ctx, int64_t S, int32_t W, int32_t H, int32_t C, int32_t G, const float *state,
+                      int64_t ld_state, const float *coef, const float *ego, int64_t ld_ego, const float *fc2_w, int64_t ld_w,
+                      const float *fc2_b, const float *weight /* or NULL */, const int32_t *group, int32_t norm, int32_t renorm,
+                      const int64_t *target /* or NULL */, const pn_explain_out *out, int32_t *status /* dev [2] or NULL */,
+                      void *stream);
+int pn_explain_totals(pn_context *ctx, int64_t S, int32_t G, const float *drop_delta, const float *keep_gain,
+                      const uint8_t *flip, const int32_t *present, const int32_t *rows /* dev [n_rows] or NULL */,
+                      int64_t n_rows, void *totals, void *stream);
+
 /* Byte offsets inside the aggregator workspace of the intermediates tests look at:
  * out[0] Xh [N,H], out[1] Z [N,L,H], out[2] hn [P,H] (pooling-group order), out[3] layer1 [S,2H]. */
 int pn_pagg_debug_offsets(const pn_pagg_shape *shape, int64_t out[4]);

@@ -100,6 +100,15 @@ class EnsembleOut(ctypes.Structure):
 ENSEMBLE_ROUTE_NONE, ENSEMBLE_ROUTE_THREAD, ENSEMBLE_ROUTE_WAVE, ENSEMBLE_ROUTE_BLOCK = 0, 1, 2, 3   # pn_ensemble_route
 
 
+class ExplainOut(ctypes.Structure):
+    """struct pn_explain_out: device pointers, None = not wanted"""
+    FIELDS = ("full", "contribution", "drop_logits", "keep_logits", "drop_delta", "keep_gain", "flip", "present", "target_used")
+    _fields_ = [(k, vp) for k in FIELDS]
+
+
+EXPLAIN_ROUTE_NONE, EXPLAIN_ROUTE_ROW, EXPLAIN_ROUTE_CHUNKED = 0, 1, 2      # pn_explain_route, route[0]
+
+
 class PathWeights(ctypes.Structure):
     """struct pn_path_weights: per-path weights of the pooling (dev fp32 [S_total, W]) and their normalisation (PATH_NORM_*)"""
     _fields_ = [("weight", vp), ("norm", ctypes.c_int32)]
@@ -270,6 +279,12 @@ SIGNATURES = {
                                        vp]),
     "pn_ensemble_finish": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, vp, vp, ctypes.c_int64, vp,
                                           ctypes.POINTER(EnsembleOut), vp]),
+    "pn_explain_route": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                        c_i32p]),
+    "pn_explain_groups": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, vp,
+                                         ctypes.c_int32, ctypes.c_int32, vp, ctypes.POINTER(ExplainOut), vp, vp]),
+    "pn_explain_totals": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int64, vp, vp]),
 }
 
 _lib = None

@@ -884,6 +884,45 @@ class _Aggregator(nn.Module):
                                 path_weights=path_weights, path_weight_norm=path_weight_norm, ensemble=ensemble,
                                 reuse_tables=reuse_tables)
 
+    def explain(self, X, neis, num_w, walk_len, indices, layer_type, *, groups="path", num_groups=None, target=None,
+                path_weights=None, path_weight_norm="sum", batch_nodes=None, logits=False, contribution=False, totals=None):
+        """Which paths the prediction of every masked node rests on -> ``pathnet_amd.Explanation`` of device tensors (logits,
+        drop_delta, keep_gain, flip, present, target, drop_logits / keep_logits with logits=True, contribution with
+        contribution=True, totals), one row per masked node, one column per group.
+
+        drop_delta[s, g] = log p(target) of row s minus log p(target) of the row WITHOUT the members of group g (positive: the
+        group supports the class); keep_gain[s, g] = log p(target) with group g ALONE minus log p(target) with no path at all;
+        flip[s, g]: the argmax changes without the group.  drop_logits[:, g] are the logits of this module's own
+        forward(path_weights=...) with the group's members given weight 0, keep_logits[:, g] those with every other member
+        given weight 0 -- but all of them come from ONE encode(path_state=True) forward and one kernel over the paths' final
+        hidden states (pn_explain_groups, fp64 on the device): the recurrence never sees the pooling, and the classifier is
+        linear after it.  Every cell= works, and any hidden size.
+
+        groups: "path" -- group = member index, G = W.  For PathNet_homo / PAGG member j is path j of the node; for PathNet it
+                is SLOT q = j * S + s of the reference's scrambled LSTM batch (encode()'s member order), whose steps come from
+                other masked nodes' paths: what the reference pools for node s, not a path of node s.
+                "reach" -- group = the largest distance code along the path, G = walk_len; computed from layer_type on the
+                device.  PathNet_homo / PAGG only; PathNet raises.
+                an int tensor [S, W] in member order, G = num_groups or max + 1 (inferred: one host read); an entry outside
+                [0, G) belongs to no group and is never removed.
+        target (int [S]): the class the scores refer to; default the argmax of the row's logits.
+        path_weights / path_weight_norm: forward()'s, by sequence slot; a member of weight 0 is in no group's count, and
+                "sum" renormalises what remains.  (PathNet: re-ordered to member order for the kernel, w.reshape(W, S).t().)
+        batch_nodes: the node list is taken in chunks of that many nodes -- path_state is S * W * H * 4 bytes -- each a
+                group_slice of the same batch (PathNet's rows read paths of the batch's other nodes, which a group_slice
+                keeps).  The chunks leave the bits of the unchunked call: explain runs its forwards with PN_EVAL_ZW off (and
+                puts the knob back), because that shortcut is taken or not by the size of the slice and rounds differently;
+                `logits` are therefore within the forward's 1e-5 of forward()'s, not its bits.
+        totals: an earlier Explanation.totals to continue (added into, e.g. over epochs of resampled paths); summary() reads it.
+
+        Runs under no_grad in eval mode (no dropout, torch's generator untouched) and restores the training flag.  Not
+        covered: the attribution of single steps or nodes inside a path (the recurrence is not linear), the aggregators of
+        pathnet_amd.dist, and training mode."""
+        from .explain import explain as explain_with       # (the package attribute `explain` is this function, not the module)
+        return explain_with(self, X, neis, num_w, walk_len, indices, layer_type, groups=groups, num_groups=num_groups,
+                            target=target, path_weights=path_weights, path_weight_norm=path_weight_norm,
+                            batch_nodes=batch_nodes, logits=logits, contribution=contribution, totals=totals)
+
     def paths_stream(self):
         """The torch stream on which this module's NEXT call will read its path arrays (neis / layer_type), judged by the
         shape of its last call on the current stream (pn_pagg_paths_stream): the library's second stream when the call forks
