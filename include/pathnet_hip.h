@@ -854,8 +854,9 @@ int pn_pagg_train_step_loss(pn_context *ctx, const pn_pagg_args *args, const pn_
  *           (the maximum over all members, live or not; every a_m is 0 when the denominator is)
  * All-one weights give the unweighted values bit for bit on the same kernels; integer weights with PN_PATH_NORM_SUM give
  * the unweighted pooling of a row in which path m is written w_m times (pn_path_multiplicity counts them).
- * out_path_weight then reports the coefficient applied: kappa w_m c_m, or kappa a_m for HETERO.  The weights are data: no
- * gradient is returned for them.  A path of weight 0 still runs through the recurrence and gets d h_n = 0.
+ * out_path_weight then reports the coefficient applied: kappa w_m c_m, or kappa a_m for HETERO.  The entry points below treat
+ * the weights as data; pn_pagg_backward_paths / pn_pagg_train_step_paths (further down) also return d loss / d weight.  A path
+ * of weight 0 still runs through the recurrence and gets d h_n = 0.
  * pw == NULL, or pw->weight == NULL: the unweighted call, exactly.  The backward takes the array its forward took.
  * Micro-batches (the backward's re-runs included), group_begin slices, the deterministic mode, every cell and every H are
  * covered; the training step runs a weighted node through pool_step_kernel (pn_pool.h), never the register-resident one. */
@@ -872,6 +873,35 @@ int pn_pagg_train_step_weighted(pn_context *ctx, const pn_pagg_args *args, const
 int pn_pagg_train_step_loss_weighted(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *sp,
                                      const pn_loss_spec *spec, const pn_path_weights *pw, const int64_t *target, float *loss,
                                      void *stream);
+
+/* ---- gradients at the per-path interface (pn_pool.hip: pool_bwd_wg_body) -------------------------------------------------
+ * The backward with the upstream gradients of out_path_state / out_path_weight as further inputs and d loss / d weight as a
+ * further output.  Two new symbols and one new struct; pn_abi_version keeps answering 12.  pg == NULL: pn_pagg_backward_weighted
+ * / pn_pagg_train_step_weighted / pn_pagg_train_step_loss_weighted, exactly.
+ *   g_path_state   dev fp32 [S, W, H], laid out like out_path_state (rows of the call's groups), 16-byte aligned; added to d h_n
+ *   g_path_weight  dev fp32 [S, W], laid out like out_path_weight; with D_m = h_m . d pooled / W + g_path_weight[m] the
+ *                  attention's chain and g_weight see D
+ *   g_weight       out, dev fp32, laid out and indexed like pn_path_weights.weight, which it needs (else PN_ERR_ARG).  The
+ *                  call stores the entry of every member of its S groups (plain stores, no atomics: the same bits in every
+ *                  run) and touches no other: the caller of a group_begin slice zero-fills the rest.  0 where the weight is not
+ *                  live and in an empty group.  With T = sum_m coef_m D_m, r_j = coef_j / w_j:
+ *                      PAGG / HOMO   "count"  r_j D_j           "sum"  r_j D_j - T / Om
+ *                      HETERO        "count"  r_j (D_j - T)     "sum"  r_j (D_j - T / kappa) - T / Om
+ * pn_pagg_backward_paths takes any subset of g_out, g_embed, g_path_state and g_path_weight (at least one).
+ * pn_pagg_train_step_paths (spec == NULL: the plain mean with grad_scale; else the options, whose grad_scale counts) takes
+ * g_weight only -- g_path_state / g_path_weight there are PN_ERR_ARG -- and g_weight carries the step's grad_scale and loss
+ * options like every other gradient of the step.  Micro-batches (the re-runs included), group_begin slices, index_rows_local,
+ * the deterministic mode, every cell and every H are covered. */
+typedef struct pn_path_grads {
+    const float *g_path_state;
+    const float *g_path_weight;
+    float *g_weight;
+} pn_path_grads;
+int pn_pagg_backward_paths(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *sp, const pn_path_weights *pw,
+                           const pn_path_grads *pg /* or NULL */, void *stream);
+int pn_pagg_train_step_paths(pn_context *ctx, const pn_pagg_args *args, const pn_sparse_features *sp,
+                             const pn_loss_spec *spec /* or NULL */, const pn_path_weights *pw, const pn_path_grads *pg,
+                             const int64_t *target, float grad_scale, float *loss, void *stream);
 
 /* One Adam update of a list of tensors in a single launch, with the semantics of torch.optim.Adam(lr, betas, eps,
  * weight_decay) (:295-296): g += weight_decay * p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;

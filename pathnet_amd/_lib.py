@@ -114,6 +114,12 @@ class PathWeights(ctypes.Structure):
     _fields_ = [("weight", vp), ("norm", ctypes.c_int32)]
 
 
+class PathGrads(ctypes.Structure):
+    """struct pn_path_grads: upstream gradients of out_path_state / out_path_weight (None = absent) and the output
+    d loss / d pn_path_weights.weight (None = not wanted)"""
+    _fields_ = [("g_path_state", vp), ("g_path_weight", vp), ("g_weight", vp)]
+
+
 LOSS_MEAN, LOSS_SUM = 0, 1        # pn_loss_spec.reduction
 
 
@@ -260,6 +266,11 @@ SIGNATURES = {
                                                    ctypes.POINTER(PathWeights), vp, ctypes.c_float, vp, vp]),
     "pn_pagg_train_step_loss_weighted": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures),
                                                         ctypes.POINTER(LossSpec), ctypes.POINTER(PathWeights), vp, vp, vp]),
+    "pn_pagg_backward_paths": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures),
+                                              ctypes.POINTER(PathWeights), ctypes.POINTER(PathGrads), vp]),
+    "pn_pagg_train_step_paths": (ctypes.c_int, [vp, ctypes.POINTER(PaggArgs), ctypes.POINTER(SparseFeatures),
+                                                ctypes.POINTER(LossSpec), ctypes.POINTER(PathWeights), ctypes.POINTER(PathGrads),
+                                                vp, ctypes.c_float, vp, vp]),
     "pn_adam_step": (ctypes.c_int, [ctypes.POINTER(AdamTensor), ctypes.c_int32, ctypes.c_float, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int64, vp, vp]),
     "pn_adam_step_advance": (ctypes.c_int, [ctypes.POINTER(AdamTensor), ctypes.c_int32, ctypes.c_float, ctypes.c_float,

@@ -1231,9 +1231,15 @@ int pn_pagg_forward_weighted(pn_context *ctx, const pn_pagg_args *a, const pn_sp
 // backward (saved tensors in place), the loss gradient of its rows is formed in between
 static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stream_, const int64_t *target, float grad_scale,
                               float *loss, const pn_sparse_features *sp, const LossOpts *opts = nullptr,
-                              float *denom_out = nullptr, const pn_path_weights *pw = nullptr) {
+                              float *denom_out = nullptr, const pn_path_weights *pw = nullptr,
+                              const pn_path_grads *pg = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     const bool fused = target != nullptr;
+    // gradients at the per-path interface (pn_path_grads; all null: the call as it was)
+    const float *g_pstate = pg ? pg->g_path_state : nullptr, *g_pweight = pg ? pg->g_path_weight : nullptr;
+    float *g_weight = pg ? pg->g_weight : nullptr;
+    if (g_weight && !(pw && pw->weight))
+        PN_FAIL(PN_ERR_ARG, "%s: pn_path_grads.g_weight needs pn_path_weights.weight", fused ? "pn_pagg_train_step_paths" : "pn_pagg_backward_paths");
     Call c;
     if (int rc = resolve_call(c, ctx, a, stream, fused ? "pn_pagg_train_step" : "pn_pagg_backward", sp, pw)) return rc;
     const Dims &d = c.d;
@@ -1248,7 +1254,7 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
     }
     // (S == 0 -- a rank of a sharded batch without masked nodes: its index arrays and g_out are empty tensors, i.e. NULL;
     //  the call still zero-fills every gradient it was given)
-    if (!a->bank_w || !a->fc2_w || (d.S > 0 && (!a->ids || !a->codes || !a->sel || (!fused && !a->g_out && !a->g_embed))))
+    if (!a->bank_w || !a->fc2_w || (d.S > 0 && (!a->ids || !a->codes || !a->sel || (!fused && !a->g_out && !a->g_embed && !g_pstate && !g_pweight))))
         PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: null tensor");
     if (d.G > 0 && (!a->w_ih || !a->w_hh)) PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: recurrent weights missing");
     if (!a->Xh_in && (!a->X || !a->fc0_w)) PN_FAIL(PN_ERR_ARG, "pn_pagg_backward: X / fc0 missing");
@@ -1340,6 +1346,9 @@ static int pagg_backward_impl(pn_context *ctx, const pn_pagg_args *a, void *stre
         }
         PoolBwdParams pp = pool_bwd_params(c, b, g_out);
         if (a->g_embed) pp.g_embed = a->g_embed + (size_t)b * d.Sb * 2 * H;     // (never with the pooling step: train_step refuses it)
+        if (g_pstate) pp.g_state = g_pstate + (size_t)b * d.Sb * d.W * H;       // (rows of the call's groups, like out_path_state)
+        if (g_pweight) pp.g_coef = g_pweight + (size_t)b * d.Sb * d.W;
+        pp.d_omega = g_weight;      // (indexed by slot like omega: no row offset)
         if (pool_step)
             if (int rc = run_pool_step(c, b, pp, target, grad_scale, opts)) return rc;
         if (!small_behind_pool)
@@ -1426,6 +1435,33 @@ int pn_pagg_train_step_loss_weighted(pn_context *ctx, const pn_pagg_args *a, con
         return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp);
     }
     return pagg_backward_impl(ctx, a, stream, target, o.grad_scale, loss, sp, &o, denom_out, pw);
+}
+
+int pn_pagg_backward_paths(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const pn_path_weights *pw,
+                           const pn_path_grads *pg, void *stream) {
+    return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp, nullptr, nullptr, pw, pg);
+}
+
+int pn_pagg_train_step_paths(pn_context *ctx, const pn_pagg_args *a, const pn_sparse_features *sp, const pn_loss_spec *spec,
+                             const pn_path_weights *pw, const pn_path_grads *pg, const int64_t *target, float grad_scale,
+                             float *loss, void *stream) {
+    // (before the device is looked at, like out_embed in check_train_step_args)
+    if (pg && (pg->g_path_state || pg->g_path_weight))
+        PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step_paths: g_path_state / g_path_weight are for pn_pagg_backward_paths");
+    if (pg && pg->g_weight && !(pw && pw->weight))
+        PN_FAIL(PN_ERR_ARG, "pn_pagg_train_step_paths: pn_path_grads.g_weight needs pn_path_weights.weight");
+    LossOpts o;
+    if (spec)
+        if (int rc = loss_opts_from_spec(spec, "pn_pagg_train_step_paths", &o)) return rc;
+    if (int rc = check_train_step_args(a, target, loss, "pn_pagg_train_step_paths")) return rc;
+    float *denom_out = spec && !spec->denominator_given ? spec->denominator : nullptr;
+    if (a->shape.S == 0) {          // nothing to aggregate: zero loss, zero gradients; g_weight has no entry of this call's
+        PN_CHECK_HIP(hipMemsetAsync(loss, 0, sizeof(float), (hipStream_t)stream));
+        if (denom_out) PN_CHECK_HIP(hipMemsetAsync(denom_out, 0, sizeof(float), (hipStream_t)stream));
+        return pagg_backward_impl(ctx, a, stream, nullptr, 0.0f, nullptr, sp);
+    }
+    if (spec) return pagg_backward_impl(ctx, a, stream, target, o.grad_scale, loss, sp, &o, denom_out, pw, pg);
+    return pagg_backward_impl(ctx, a, stream, target, grad_scale, loss, sp, nullptr, nullptr, pw, pg);
 }
 
 }  // extern "C"

@@ -72,6 +72,11 @@ struct PoolBwdParams {
     const int32_t *slotof;
     int64_t wbase;
     int norm;
+    // gradients at the per-path interface (pn_path_grads), each null or set for the whole launch:
+    const float *g_state;   // [S, W, H] upstream of PoolParams::path_state, rows of this launch's groups: joins d h_n
+    const float *g_coef;    // [S, W]    upstream of PoolParams::path_weight: joins d coef behind the dot product
+    float *d_omega;         // out, indexed like omega: d loss / d weight, 0 where the weight is not live or the group is empty;
+                            // every member of every group of the launch is stored once (needs omega)
 };
 // HI = 4 up to H = 256, HI = 16 above
 int launch_pool_bwd(pn_context *ctx, void *stream, const PoolBwdParams &p);

@@ -194,6 +194,7 @@ __device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *
     float *s_coef = reinterpret_cast<float *>(s_erow + W);  // [W]
     float *s_tot = s_coef + W;               // [4] hetero: partial sums of coef * d coef
     float *s_kw = s_tot + 4;                 // [W] live path weights (with p.omega; pool_bwd_lds_bytes has the room)
+    int *s_slot = reinterpret_cast<int *>(s_kw + W);       // [W] their entries of omega / d_omega (5 W + 9 H + 4 words so far of 16 W + 12 H)
     const int g = blockIdx.x;
     const float inv_w = 1.0f / (float)W;
     for (int mem = tid; mem < W; mem += 256) {
@@ -202,7 +203,11 @@ __device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *
         s_coef[mem] = p.coef[s];
     }
     if (p.omega)        // (a loop of its own: inside the one above it costs pool_bwd_wg_kernel<4> 22 registers)
-        for (int mem = tid; mem < W; mem += 256) s_kw[mem] = live_weight(p.omega[(int64_t)p.slotof[(int64_t)g * W + mem] - p.wbase]);
+        for (int mem = tid; mem < W; mem += 256) {
+            const int64_t q = (int64_t)p.slotof[(int64_t)g * W + mem] - p.wbase;
+            s_kw[mem] = live_weight(p.omega[q]);
+            s_slot[mem] = (int)q;       // (d_omega's index, kept here: formed again at its store it costs the <4> kernel 24 registers)
+        }
     for (int j = tid; j < H; j += 256) {
         float a = 0.0f, b = 0.0f;
         if (p.g_out)
@@ -245,13 +250,40 @@ __device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *
             acc += __shfl_xor(acc, 1, 64);
             acc += __shfl_xor(acc, 2, 64);
             acc += __shfl_xor(acc, 4, 64);
-            if (part == 0 && mem < W) dco[mem] = acc;
+            if (part == 0 && mem < W) dco[mem] = p.g_coef ? acc + p.g_coef[(int64_t)g * W + mem] : acc;
         }
     }
     __syncthreads();
     // coef = kappa * omega * c: d score = kappa * omega * d coef (HOMO), and the softmax's sum carries 1 / kappa (HETERO: with
     // coef = kappa * a, d l_m = coef_m * (d coef_m - sum_k coef_k d coef_k / kappa)).  Without weights both factors are 1.
     const float kappa = p.omega ? pool_kappa(s_kw, W, p.norm, lane) : 1.0f;
+    if (p.d_omega) {
+#pragma clang fp contract(off)      // (an fma of the last difference would keep one product's rounding error)
+        // d loss / d w_j of the live weights, D = d coef above (g_coef included), T = sum coef D, Om = sum w:
+        //   PAGG / HOMO  (coef_j D_j Om - [sum] w_j T) / (w_j Om)         HETERO  (coef_j (D_j - T / kappa) Om - [sum] w_j T) / (w_j Om)
+        // ([sum]: PN_PATH_NORM_SUM only, kappa's own derivative).  T, Om and the differences in fp64 -- W scalar operations: a
+        // group with one live path under "sum" is scale invariant, and (coef_j D_j) w_j - w_j (coef_j D_j) is 0 exactly.  Every
+        // wave adds all W in the same order; every member is stored, the dead ones and an empty group's as 0
+        double T = 0.0, Om = 0.0;
+        for (int mem = lane; mem < W; mem += 64) {
+            T += (double)s_coef[mem] * (double)dco[mem];
+            Om += (double)s_kw[mem];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            T += __shfl_xor(T, o, 64);
+            Om += __shfl_xor(Om, o, 64);
+        }
+        const double Tk = (p.variant == PN_VARIANT_HETERO && kappa > 0.0f) ? T / (double)kappa : 0.0;
+        const double To = p.norm == PN_PATH_NORM_SUM ? T : 0.0;
+        for (int mem = tid; mem < W; mem += 256) {
+            const double w = (double)s_kw[mem];
+            double gw = 0.0;
+            if (w > 0.0 && kappa > 0.0f)
+                gw = (((double)s_coef[mem] * ((double)dco[mem] - Tk)) * Om - w * To) / (w * Om);
+            p.d_omega[s_slot[mem]] = (float)gw;
+        }
+    }
     if (p.variant == PN_VARIANT_HETERO) {
         float tot = 0.0f;
         for (int mem = tid; mem < W; mem += 256) tot += s_coef[mem] * dco[mem];
@@ -299,6 +331,7 @@ __device__ __forceinline__ void pool_bwd_wg_body(const PoolBwdParams &p, float *
                     else if (!p.det_ds)
                         atomicAdd(&p.dego[erow + j], eg);
                 }
+                if (p.g_state) dh += p.g_state[s * H + j];
                 p.dhn[s * H + j] = dh;
             }
         }

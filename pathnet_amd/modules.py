@@ -56,16 +56,18 @@ _SEQ_MATH = {None: _lib.SEQ_MATH_DEFAULT, "": _lib.SEQ_MATH_DEFAULT, "f16x2": _l
 _PATH_NORM = {"sum": _lib.PATH_NORM_SUM, "count": _lib.PATH_NORM_COUNT}
 
 
-def as_path_weights(path_weights, rows, W, check=False):
+def as_path_weights(path_weights, rows, W, check=False, path_grad=False):
     """path_weights= of the aggregators -> a float32 tensor [rows, W] (still on its own device), or None.  Any float (or
-    integer) dtype, shape [rows, W] or [rows * W]; rows: the rows of the call's neis.  A wrong shape or a tensor that requires
-    grad raises ValueError -- the weights are data, no gradient is returned for them.  check: also raise on a negative or
-    non-finite entry (one host read); unchecked, the kernels count such an entry as 0."""
+    integer) dtype, shape [rows, W] or [rows * W]; rows: the rows of the call's neis.  A wrong shape, or without path_grad a
+    tensor that requires grad, raises ValueError -- by default the weights are data, no gradient is returned for them.  With
+    path_grad=True (the aggregators' keyword) the result is a differentiable function of the caller's tensor.  check: also
+    raise on a negative or non-finite entry (one host read); unchecked, the kernels count such an entry as 0."""
     if path_weights is None:
         return None
     w = torch.as_tensor(path_weights)
-    if w.requires_grad:
-        raise ValueError("path_weights requires grad: the weights are data, no gradient is returned for them (detach them)")
+    if w.requires_grad and not path_grad:
+        raise ValueError("path_weights requires grad: by default the weights are data and no gradient is returned for them "
+                         "(detach them, or pass path_grad=True)")
     if w.dtype == torch.bool or w.dtype.is_complex:
         raise TypeError("path_weights: a real dtype expected, got %s" % w.dtype)
     if tuple(w.shape) not in ((rows, W), (rows * W,)):
@@ -211,6 +213,13 @@ class PaggCall:
         if self.path_weights is None:
             return None
         return ctypes.byref(_lib.PathWeights(self.path_weights.data_ptr(), _PATH_NORM[self.path_weight_norm]))
+
+    def weight_grad_buffer(self):
+        """the tensor for pn_path_grads.g_weight, laid out like the call's path_weights.  The library stores the entries of the
+        call's own groups and touches no other: a call that computes a part of the batch its weights describe (group_slice),
+        or nothing, starts from zeros."""
+        whole = self.S > 0 and (self.index_rows_local or self.S_total in (0, self.S))
+        return (torch.empty_like if whole else torch.zeros_like)(self.path_weights)
 
     def grad_buffers(self, a, p, X=None, flat=False):
         """Gradient tensors for every parameter `a` names (and for X, when given), their addresses set in a.g_*.
@@ -396,8 +405,10 @@ class _PaggFunction(torch.autograd.Function):
         return _PaggFunction._backward(ctx, g_out, None)
 
     @staticmethod
-    def _backward(ctx, g_out, g_embed):
-        """one pn_pagg_backward for d loss / d logits (g_out) and / or d loss / d embedding (g_embed); either may be None"""
+    def _backward(ctx, g_out, g_embed, g_pw=None, g_ps=None, g_weight=None, want_gX=None):
+        """one pn_pagg_backward for d loss / d logits (g_out) and / or d loss / d embedding (g_embed); either may be None.
+        _PaggPathFunction: also the upstream gradients of encode()'s path_weight / path_state (g_pw / g_ps) and the tensor
+        d loss / d path weights goes to (g_weight: PaggCall.weight_grad_buffer) -- then one pn_pagg_backward_paths"""
         call = ctx.call
         saved = list(ctx.saved_tensors)
         X, ids, codes, sel = saved[:4]
@@ -409,11 +420,18 @@ class _PaggFunction(torch.autograd.Function):
             g_out = g_out.contiguous().float() if g_out is not None else None
             g_embed = g_embed.contiguous().float() if g_embed is not None else None
             a = call.args(ids, codes, sel, p, X=X)
-            grads, gX, _ = call.grad_buffers(a, p, X if ctx.needs_input_grad[1] else None)
+            grads, gX, _ = call.grad_buffers(a, p, X if (ctx.needs_input_grad[1] if want_gX is None else want_gX) else None)
             a.workspace, a.workspace_bytes = ctx.ws.data_ptr(), ctx.ws.numel()
             a.g_out = g_out.data_ptr() if g_out is not None else None
             a.g_embed = g_embed.data_ptr() if g_embed is not None else None
-            if call.S > 0:
+            if call.S > 0 and (g_pw is not None or g_ps is not None or g_weight is not None):
+                g_pw = g_pw.contiguous().float() if g_pw is not None else None
+                g_ps = g_ps.contiguous().float() if g_ps is not None else None
+                pg = _lib.PathGrads(g_ps.data_ptr() if g_ps is not None else None, g_pw.data_ptr() if g_pw is not None else None,
+                                    g_weight.data_ptr() if g_weight is not None else None)
+                _lib.check(_lib.load().pn_pagg_backward_paths(_lib.context(dev), ctypes.byref(a), call.features_ref(),
+                                                              call.weights_ref(), ctypes.byref(pg), _lib.stream_ptr(dev)))
+            elif call.S > 0:
                 _lib.check(_lib.load().pn_pagg_backward_weighted(_lib.context(dev), ctypes.byref(a), call.features_ref(),
                                                                  call.weights_ref(), _lib.stream_ptr(dev)))
             else:
@@ -448,6 +466,41 @@ class _PaggEncodeFunction(torch.autograd.Function):
         return _PaggFunction._backward(ctx, g_out, g_embed)
 
 
+class _PaggPathFunction(torch.autograd.Function):
+    """path_grad=True: _PaggFunction (encode False: logits) or _PaggEncodeFunction (encode True) with the gradients at the
+    per-path interface.  `weights` -- the tensor call.path_weights was detached from, or None -- is a differentiable input,
+    and encode()'s path_weight / path_state are differentiable outputs; one pn_pagg_backward_paths takes whichever upstream
+    gradients the loss produced and returns d loss / d weights with the parameters' gradients."""
+
+    @staticmethod
+    def forward(ctx, call, encode, weights, X, ids, codes, sel, *params):
+        S, W, H, dev = call.S, call.W, call.H, X.device
+        enc = None
+        if encode:
+            with torch.cuda.device(dev):
+                enc = (torch.empty((S, 2 * H), dtype=torch.float32, device=dev), torch.empty((S, W), dtype=torch.float32, device=dev),
+                       torch.empty((S, W, H), dtype=torch.float32, device=dev) if call.path_state else None)
+        out = _PaggFunction._forward(ctx, call, X, ids, codes, sel, params, encode_out=enc)
+        ctx.want_weight = weights is not None
+        ctx.set_materialize_grads(False)
+        if not encode:
+            return out
+        return (out,) + tuple(t for t in enc if t is not None)
+
+    @staticmethod
+    def backward(ctx, g_out=None, g_embed=None, g_pw=None, g_ps=None):
+        n_in = 7 + len(ctx.present)
+        if g_out is None and g_embed is None and g_pw is None and g_ps is None:
+            return (None,) * n_in
+        call = ctx.call
+        gw = call.weight_grad_buffer() if (ctx.want_weight and ctx.needs_input_grad[2]) else None
+        # (_backward sees X's flag where _PaggFunction has it: the inputs here are shifted by two)
+        res = _PaggFunction._backward(ctx, g_out, g_embed, g_pw, g_ps, gw, want_gX=ctx.needs_input_grad[3])
+        if gw is not None and call.S == 0:
+            gw.zero_()
+        return (None, None, gw) + res[1:]
+
+
 class _PaggLossFunction(torch.autograd.Function):
     """loss, logits = one pn_pagg_train_step: forward, softmax cross entropy and backward in one library call (what it
     saves: the second forward of every micro-batch, include/pathnet_hip.h).  The gradients are computed here and handed
@@ -455,6 +508,11 @@ class _PaggLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, call, X, ids, codes, sel, target, *params):
+        return _PaggLossFunction._forward(ctx, call, X, ids, codes, sel, target, params, ctx.needs_input_grad[1], False)
+
+    @staticmethod
+    def _forward(ctx, call, X, ids, codes, sel, target, params, want_gX, want_gw):
+        """want_gw (_PaggPathLossFunction): the same library call also leaves d loss / d path weights in ctx.g_weight"""
         p = _split_params(params, call.L)
         dev = X.device
         with torch.cuda.device(dev):
@@ -463,9 +521,20 @@ class _PaggLossFunction(torch.autograd.Function):
             loss = (torch.empty if call.S > 0 else torch.zeros)((), dtype=torch.float32, device=dev)
             # every parameter gradient is a view of one flat buffer: backward() scales them by the upstream gradient of
             # the loss with one launch instead of one per tensor
-            grads, gX, flat = call.grad_buffers(a, p, X if ctx.needs_input_grad[1] else None, flat=True)
+            grads, gX, flat = call.grad_buffers(a, p, X if want_gX else None, flat=True)
             target = target.to(device=dev, dtype=torch.int64).contiguous()
-            if call.S > 0 and call.loss is not None:
+            ctx.g_weight = call.weight_grad_buffer() if want_gw else None
+            if call.S > 0 and want_gw:
+                spec = None
+                if call.loss is not None:
+                    loss_fn, scale = call.loss
+                    spec, ctx.loss_keep = loss_fn.spec(dev, call.C, scale)
+                pg = _lib.PathGrads(None, None, ctx.g_weight.data_ptr())
+                _lib.check(_lib.load().pn_pagg_train_step_paths(
+                    _lib.context(dev), ctypes.byref(a), call.features_ref(), ctypes.byref(spec) if spec is not None else None,
+                    call.weights_ref(), ctypes.byref(pg), target.data_ptr(), float(call.grad_scale), loss.data_ptr(),
+                    _lib.stream_ptr(dev)))
+            elif call.S > 0 and call.loss is not None:
                 # (the spec's weight and denominator tensors live on the context until backward(); under capture they are the
                 #  graph's pool's, like every other tensor of the step)
                 loss_fn, scale = call.loss
@@ -492,6 +561,11 @@ class _PaggLossFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_loss, _g_out):
+        return _PaggLossFunction._backward(ctx, g_loss)
+
+    @staticmethod
+    def _backward(ctx, g_loss, g_weight=None):
+        """g_weight (_PaggPathLossFunction): d loss / d path weights of the same step, scaled with the others"""
         # (the context lets go of the tensors: with a second owner alive autograd's AccumulateGrad would copy every
         #  gradient into a fresh tensor instead of adopting it -- 18 copy launches per step)
         grads, flat = ctx.grads, ctx.flat
@@ -508,7 +582,25 @@ class _PaggLossFunction(torch.autograd.Function):
             flat.mul_(g_loss)
             if grads[0] is not None:
                 grads[0].mul_(g_loss)
+            if g_weight is not None:
+                g_weight.mul_(g_loss)
         return (None, grads[0], None, None, None, None) + tuple(grads[1:])
+
+
+class _PaggPathLossFunction(torch.autograd.Function):
+    """_PaggLossFunction with path_grad=True: `weights` (the tensor call.path_weights was detached from) is a differentiable
+    input, its gradient comes out of the same pn_pagg_train_step_paths call as every other gradient of the step."""
+
+    @staticmethod
+    def forward(ctx, call, weights, X, ids, codes, sel, target, *params):
+        return _PaggLossFunction._forward(ctx, call, X, ids, codes, sel, target, params, ctx.needs_input_grad[2], True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_out):
+        gw, ctx.g_weight = ctx.g_weight, None
+        res = _PaggLossFunction._backward(ctx, g_loss, gw)
+        return (None, gw if g_loss is not None else None) + res[1:]
 
 
 def _as_index_tensors(neis, layer_type, indices, num_w, walk_len, device, n_nodes=None):
@@ -779,7 +871,7 @@ class _Aggregator(nn.Module):
         return fw, fb, head + tuple(ws) + tuple(bs)
 
     def forward_loss(self, X, neis, num_w, walk_len, indices, layer_type, target, indxx=None, grad_scale=None, fused=None,
-                     loss=None, *, path_weights=None, path_weight_norm="sum", check_weights=False):
+                     loss=None, *, path_weights=None, path_weight_norm="sum", check_weights=False, path_grad=False):
         """(loss, logits) of a training step's forward + torch.nn.CrossEntropyLoss() (PathNet_run.py:343-346); loss.backward()
         yields the parameter gradients.  target: class index of every masked node, in the order of the logits' rows.
         grad_scale: weight of a row's loss (default 1 / rows = the mean).
@@ -794,12 +886,15 @@ class _Aggregator(nn.Module):
         device over the whole batch, so a captured step follows targets whose ignored count changes.  With a loss, grad_scale
         (default 1 / rows) times rows multiplies the reduced loss: the default is torch's value.
         path_weights / path_weight_norm / check_weights: forward()'s.  A weighted fused step runs the pooling as three kernel
-        bodies in one launch; the register-resident pooling step is the unweighted call's."""
+        bodies in one launch; the register-resident pooling step is the unweighted call's.
+        path_grad=True: path_weights may require grad (forward()'s keyword); the fused step computes their gradient inside its
+        one library call, and backward() scales it by the loss's upstream gradient with the others."""
         return self._run(X, neis, num_w, walk_len, indices, layer_type, target=target, grad_scale=grad_scale, fused=fused,
-                         loss=loss, path_weights=path_weights, path_weight_norm=path_weight_norm, check_weights=check_weights)
+                         loss=loss, path_weights=path_weights, path_weight_norm=path_weight_norm, check_weights=check_weights,
+                         path_grad=path_grad)
 
     def forward(self, X, neis, num_w, walk_len, indices, layer_type, indxx=None, reuse_tables=False, group_slice=None, *,
-                path_weights=None, path_weight_norm="sum", check_weights=False):
+                path_weights=None, path_weight_norm="sum", check_weights=False, path_grad=False):
         """path_weights (extension; None: the reference's pooling, bit for bit): a weight per path, float [S, W] or [S * W] on
         any device, S the masked nodes of neis (the whole batch also with group_slice).  PathNet_homo / PAGG: entry [s, w]
         weighs path w of masked node s.  PathNet: entry [s, w] weighs sequence slot q = s * W + w of the reference's scrambled
@@ -807,13 +902,19 @@ class _Aggregator(nn.Module):
         An entry that is no finite positive number counts as 0: the path is left out of the row.  path_weight_norm="sum"
         scales a row's weights to sum to W, so integer weights are repeated paths and pathnet_amd.importance_weights are a
         self-normalised estimate; "count" applies them as given.  A row without a live path pools zeros and passes no
-        gradient to its paths.  The weights are data: no gradient is returned for them, a tensor that requires grad is
-        refused.  check_weights=True raises on a negative or non-finite entry (one host read)."""
+        gradient to its paths.  By default the weights are data: no gradient is returned for them, a tensor that requires grad
+        is refused.  check_weights=True raises on a negative or non-finite entry (one host read).
+        path_grad=True (extension; with grad enabled): path_weights may require grad and gets its gradient in its own shape,
+        dtype and device -- 0 at every entry that counts as 0, in a row without a live path and, with group_slice, in the rows
+        outside the slice (pn_pagg_backward_paths; the closed form: INTEGRATION.md section 1).  Under torch.no_grad() the
+        keyword changes nothing.  Not covered: the aggregators of pathnet_amd.dist, predict() / explain() / the trainer's
+        fixed-index steps (their weights stay data), and a step that is being captured into a hipGraph, which raises."""
         return self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=reuse_tables, group_slice=group_slice,
-                         path_weights=path_weights, path_weight_norm=path_weight_norm, check_weights=check_weights)
+                         path_weights=path_weights, path_weight_norm=path_weight_norm, check_weights=check_weights,
+                         path_grad=path_grad)
 
     def encode(self, X, neis, num_w, walk_len, indices, layer_type, indxx=None, *, path_state=False, group_slice=None,
-               reuse_tables=False, seed=None, path_weights=None, path_weight_norm="sum", check_weights=False):
+               reuse_tables=False, seed=None, path_weights=None, path_weight_norm="sum", check_weights=False, path_grad=False):
         """The model's internals next to its logits, from the same single forward: ``Encoded(logits, embedding, path_weight,
         path_state)``, every tensor fp32 on X's device, one row per masked node (of the group_slice, when given).
 
@@ -823,9 +924,9 @@ class _Aggregator(nn.Module):
                                  it holds the sequence dropout of the same call.  Differentiable w.r.t. every parameter and X.
           path_weight [S, W]     the coefficient that multiplies member j's final hidden state in row s's mean: the softmax
                                  weight (PathNet), 1 + att (PathNet_homo), 1 (PAGG); with path_weights (forward()'s) the
-                                 coefficient actually applied, kappa * weight * that.  Not differentiable.
+                                 coefficient actually applied, kappa * weight * that.  Differentiable with path_grad=True.
           path_state  [S, W, H]  member j's final hidden state h_n; only with path_state=True (it is large), else None.
-                                 Not differentiable.
+                                 Differentiable with path_grad=True.
 
         Member order is the reference's: for PathNet_homo / PAGG member j of row s is path j of masked node s.  For PathNet
         it is sequence slot q = j * S + s of the reference's scrambled LSTM batch (S: masked nodes of the whole batch; the
@@ -834,11 +935,13 @@ class _Aggregator(nn.Module):
 
         A loss over any mix of logits and embedding runs ONE backward of the library.  group_slice, reuse_tables and the
         dropout handling are forward()'s; seed (training only) fixes the dropout seed instead of drawing it from torch's
-        generator.  Not covered: gradients through path_weight / path_state, the node-sharded and replicated aggregators
-        of pathnet_amd.dist, and the fused training step (forward_loss(fused=True))."""
+        generator.  path_grad=True (with grad enabled): path_weight and path_state are differentiable too, and path_weights
+        may require grad (forward()'s keyword) -- a loss over any mix of the four outputs still runs ONE backward of the
+        library (pn_pagg_backward_paths), an output the loss does not use costs nothing.  Not covered: the node-sharded and
+        replicated aggregators of pathnet_amd.dist, and the fused training step (forward_loss(fused=True))."""
         res = self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=reuse_tables, group_slice=group_slice,
                         seed=seed, _encode=bool(path_state), path_weights=path_weights, path_weight_norm=path_weight_norm,
-                        check_weights=check_weights)
+                        check_weights=check_weights, path_grad=path_grad)
         logits, emb, pw = res[:3]
         ps = res[3] if path_state else None
         H = self.hidden_size
@@ -995,7 +1098,7 @@ class _Aggregator(nn.Module):
 
     def _run(self, X, neis, num_w, walk_len, indices, layer_type, reuse_tables=False, group_slice=None, target=None,
              grad_scale=None, fused=None, batch_position=None, seed=None, _math=None, _encode=None, loss=None,
-             path_weights=None, path_weight_norm="sum", check_weights=False):
+             path_weights=None, path_weight_norm="sum", check_weights=False, path_grad=False):
         """reuse_tables (extension, inference only): X and the weights are those of the previous no-grad forward of this
         module -- the validation and the test forward of an epoch (PathNet_run.py:362, :378) -- so the projected
         feature matrix and the distance bank still sitting in the module's workspace are used again.
@@ -1008,7 +1111,17 @@ class _Aggregator(nn.Module):
             raise ValueError("path_weight_norm=%r: 'sum' or 'count'" % (path_weight_norm,))
         if path_weights is not None:
             rows = int(torch.as_tensor(neis).numel()) // max(int(num_w) * int(walk_len), 1)       # the masked nodes neis describes
-            path_weights = as_path_weights(path_weights, rows, int(num_w), check=check_weights)
+            path_weights = as_path_weights(path_weights, rows, int(num_w), check=check_weights, path_grad=bool(path_grad))
+        # path_grad counts with grad enabled only (under no_grad the call is the one without it); wgrad: the weights as the
+        # differentiable input of the path Functions, or None when they ask for no gradient
+        path_grad = bool(path_grad) and torch.is_grad_enabled()
+        if path_grad and dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("path_grad=True is not available while a hipGraph is being captured: the captured training "
+                               "steps treat the path weights as data")
+        wgrad = None
+        if path_weights is not None and path_weights.requires_grad:
+            wgrad = path_weights.to(dev).contiguous() if path_grad else None
+            path_weights = (wgrad if wgrad is not None else path_weights).detach()
         if dev.type != "cuda":
             raise RuntimeError("pathnet_amd aggregators run on the GPU only (X is on %s); no CPU fallback" % dev)
         X_given = X
@@ -1098,16 +1211,25 @@ class _Aggregator(nn.Module):
                 call.loss = (loss_fn, 1.0 if grad_scale is None else float(grad_scale) * max(S, 1))
             if fused is None:
                 fused = call.batch_groups > 0
-            if fused:
+            if fused and wgrad is not None:
+                res = _PaggPathLossFunction.apply(call, wgrad, X, ids, codes, sel, target, *params)
+            elif fused:
                 res = _PaggLossFunction.apply(call, X, ids, codes, sel, target, *params)
             else:
-                out = _PaggFunction.apply(call, X, ids, codes, sel, *params)
+                if wgrad is not None:
+                    out = _PaggPathFunction.apply(call, False, wgrad, X, ids, codes, sel, *params)
+                else:
+                    out = _PaggFunction.apply(call, X, ids, codes, sel, *params)
                 value = (loss_fn or optim.CrossEntropyLoss())(out, target.to(device=dev, dtype=torch.int64))
                 if grad_scale is not None:      # (the plain loss: the mean over the S rows)
                     value = value * (float(grad_scale) * max(S, 1))
                 res = (value, out)
+        elif _encode is not None and path_grad:     # (the per-path outputs are differentiable, whatever the weights ask for)
+            res = _PaggPathFunction.apply(call, True, wgrad, X, ids, codes, sel, *params)
         elif _encode is not None:       # (encode(): _encode = whether the paths' final hidden states are wanted)
             res = _PaggEncodeFunction.apply(call, X, ids, codes, sel, *params)
+        elif wgrad is not None:
+            res = _PaggPathFunction.apply(call, False, wgrad, X, ids, codes, sel, *params)
         else:
             res = _PaggFunction.apply(call, X, ids, codes, sel, *params)
         if guard and S > 0:
@@ -1119,7 +1241,8 @@ class _Aggregator(nn.Module):
                     return self._run(X, neis, num_w, walk_len, indices, layer_type, reuse_tables=False, group_slice=group_slice,
                                      target=target, grad_scale=grad_scale, fused=fused, batch_position=batch_position,
                                      seed=seed, _math=_lib.SEQ_MATH_BF16X3, _encode=_encode, loss=loss,
-                                     path_weights=path_weights, path_weight_norm=path_weight_norm)
+                                     path_weights=wgrad if wgrad is not None else path_weights,
+                                     path_weight_norm=path_weight_norm, path_grad=path_grad)
         return res
 
 
