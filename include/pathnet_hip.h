@@ -1175,6 +1175,61 @@ int pn_explain_totals(pn_context *ctx, int64_t S, int32_t G, const float *drop_d
                       const uint8_t *flip, const int32_t *present, const int32_t *rows /* dev [n_rows] or NULL */,
                       int64_t n_rows, void *totals, void *stream);
 
+/* ---- explanations by node and by edge: overlapping-group occlusion (pn_explain_units.hip, pn_explain.hip) ------------------
+ * Paths are redrawn every epoch; what stays is the graph.  Removing node u from a row means removing every member that
+ * passed through u, and nothing in the closed form above needs the groups to be disjoint.  Added without an ABI bump: three
+ * new symbols, no struct or signature changed, pn_abi_version keeps answering 12.
+ *
+ * pn_explain_units turns a row's ids into its units and every step's label.  node [S, W, L] int32 is in MEMBER order: the
+ * node whose table row member j of row s consumed at step t (HOMO / PAGG: the path array itself; HETERO: slot q = j S + s
+ * reads ids_flat[(q L + t) % P, L - 1 - (q L + t) / P], P = S W of the whole batch).
+ *   PN_UNIT_NODE  M = L.  The key of step t is the node id.  No unit (label -1) when the id is negative, or equals
+ *                 exclude[s] (dev int32 [S] or NULL: the row's own node, which sits on every path of a HOMO / PAGG row and
+ *                 also enters through the ego half of the embedding).
+ *   PN_UNIT_EDGE  M = L - 1.  The key of step t >= 1 (label column t - 1) is the undirected pair of the ids of steps t - 1
+ *                 and t: ((int64)min << 32) | max.  No unit when either end is negative.  A stay step (u, u) is a unit like
+ *                 any other (the shipped tables have self loops).  exclude must be NULL.
+ *   unit  [S, G] int64, G = W M    unit[s, 0 .. count[s]) the row's distinct keys in ascending order, the rest -1
+ *   count [S] int32
+ *   label [S, W, M] int32          the position of the step's key in unit[s], or -1
+ * Exact integers, a function of the row alone (not of S or the grid).  One workgroup owns a row and sorts its keys in LDS:
+ * no workspace.  Limits: 1 <= W, 1 <= L <= 16 (L >= 2 for edges), W M <= 1024, 0 <= S < 2^31.
+ *
+ * pn_explain_overlap is pn_explain_groups, definition, edge rules, bad rows, target, status, rounding and sum orders, with
+ * ONE line changed:
+ *   R = the live members j with label[s, j, m] == g for some m      (label [S, W, M] int32)
+ * A label outside [0, G) is no membership; a member with no valid label is never removed and never kept alone.  A label
+ * repeated within a member counts once: present[s, g] counts members, not steps.  The sum orders are fixed by
+ * (W, H, C, G, M) alone.  With M = 1 and label = group every output has pn_explain_groups' bits.  It follows
+ * pn_explain_route's route.  Limits: those of pn_explain_groups, and 1 <= M <= 16, W M <= 1024.
+ *
+ * pn_explain_node_totals adds a call's rows (all S, or rows [n_rows] int32; an entry outside [0, S) is skipped) into a
+ * caller-zeroed table int64 [4, N]: rows_present[N], members[N], flips[N], top[N].  A unit (s, g) qualifies when
+ * present > 0, drop_delta and keep_gain are finite (pn_explain_totals' rule) and its key u = unit[s, g] lies in [0, N); it
+ * adds 1 to rows_present[u], present to members[u] and (flip != 0) to flips[u].  top[u] += 1 for the one qualifying unit of
+ * the row with the largest drop_delta, the lowest position among equals.  64-bit integer atomics: the table is exact and
+ * independent of order, which is why it holds counts only -- per-node sums of scores would need floating-point atomics or a
+ * global sort (the caller has unit and drop_delta on the device).  There are no per-edge totals: an edge has no dense index.
+ * Limits: 1 <= G <= 1024, N >= 1, rows / n_rows as pn_explain_totals.
+ *
+ * All three: refused with PN_ERR_ARG before any device call (NULL where something would be read included), S == 0 launches
+ * nothing, asynchronous on `stream`, nothing read back, nothing allocated. */
+#define PN_UNIT_NODE 0
+#define PN_UNIT_EDGE 1
+int pn_explain_units(pn_context *ctx, int64_t S, int32_t W, int32_t L, int32_t kind,
+                     const int32_t *node /* dev [S, W, L] */, const int32_t *exclude /* dev [S] or NULL; PN_UNIT_NODE only */,
+                     int64_t *unit /* dev [S, G], G = W * M */, int32_t *count /* dev [S] */,
+                     int32_t *label /* dev [S, W, M] */, void *stream);
+int pn_explain_overlap(pn_context *ctx, int64_t S, int32_t W, int32_t H, int32_t C, int32_t G, int32_t M, const float *state,
+                       int64_t ld_state, const float *coef, const float *ego, int64_t ld_ego, const float *fc2_w, int64_t ld_w,
+                       const float *fc2_b, const float *weight /* or NULL */, const int32_t *label /* dev [S, W, M] */,
+                       int32_t norm, int32_t renorm, const int64_t *target /* or NULL */, const pn_explain_out *out,
+                       int32_t *status /* dev [2] or NULL */, void *stream);
+int pn_explain_node_totals(pn_context *ctx, int64_t S, int32_t G, int32_t N, const int64_t *unit /* dev [S, G] */,
+                           const float *drop_delta, const float *keep_gain, const uint8_t *flip, const int32_t *present,
+                           const int32_t *rows /* dev [n_rows] or NULL */, int64_t n_rows,
+                           int64_t *table /* dev [4, N], caller-zeroed, added to */, void *stream);
+
 /* Byte offsets inside the aggregator workspace of the intermediates tests look at:
  * out[0] Xh [N,H], out[1] Z [N,L,H], out[2] hn [P,H] (pooling-group order), out[3] layer1 [S,2H]. */
 int pn_pagg_debug_offsets(const pn_pagg_shape *shape, int64_t out[4]);

@@ -107,6 +107,7 @@ class ExplainOut(ctypes.Structure):
 
 
 EXPLAIN_ROUTE_NONE, EXPLAIN_ROUTE_ROW, EXPLAIN_ROUTE_CHUNKED = 0, 1, 2      # pn_explain_route, route[0]
+UNIT_NODE, UNIT_EDGE = 0, 1                                                 # pn_explain_units, kind
 
 
 class PathWeights(ctypes.Structure):
@@ -296,6 +297,13 @@ SIGNATURES = {
                                          vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, vp,
                                          ctypes.c_int32, ctypes.c_int32, vp, ctypes.POINTER(ExplainOut), vp, vp]),
     "pn_explain_totals": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int64, vp, vp]),
+    "pn_explain_units": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp,
+                                        vp]),
+    "pn_explain_overlap": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_int32, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp,
+                                          vp, ctypes.c_int32, ctypes.c_int32, vp, ctypes.POINTER(ExplainOut), vp, vp]),
+    "pn_explain_node_totals": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp, vp, vp, vp, vp, vp,
+                                              ctypes.c_int64, vp, vp]),
 }
 
 _lib = None

@@ -1,10 +1,11 @@
-// pn_explain.hip -- exact path and group occlusion of a prediction (pn_explain_groups / pn_explain_totals).
+// pn_explain.hip -- exact path and group occlusion of a prediction (pn_explain_groups / pn_explain_overlap /
+// pn_explain_totals).
 //
 // The recurrence never sees the pooling, and the classifier is linear after it: what the model would say without a set of a
 // row's members, or with that set alone, is a closed form over the members' final hidden states (include/pathnet_hip.h has
 // the definition).  This file evaluates it for all groups of all rows in one pass over `state`.
 //
-//   explain_kernel<LANES>     one workgroup owns a row.  Per class chunk: the row's [W, H] states, its ego row and the two
+//   explain_kernel<LANES, OVERLAP>  one workgroup owns a row.  Per class chunk: the row's [W, H] states, its ego row and the two
 //                             halves of fc2's rows go through LDS in tiles of Ht hidden units (16-byte loads where the
 //                             addresses allow), and thread (j, c) adds its products in ascending h into con[j, c] (fp64, LDS;
 //                             row W is the ego's e[c]).  Then LANES threads own one logit vector at a time -- drop_g, keep_g,
@@ -21,7 +22,20 @@
 //                values are carried from chunk to chunk in LDS.
 //   H tile       the largest Ht with (W + 1 + 2 Cc) * (Ht | 1) <= 7168 floats, a multiple of 4 when it is below H; rows of the
 //                tile are Ht | 1 floats apart, so that neighbouring threads' rows start in different banks.
-// Every sum's order is a function of (W, H, C, G) alone -- not of S, the grid, or the rows next to it -- and there is no
+// Overlapping groups (pn_explain_overlap): the same kernel body with OVERLAP = true.  A member then carries M labels instead of
+// one group id, and "member j is in group g" is M compares against label[j, 0 .. M) in LDS (W * M <= 1024 ints, 4 KB) where
+// the partition kernel makes one.  The alternative, a bit table [W, G / 32] in LDS, was not taken: at the cap (W = 1024,
+// M = 1, G = 1024) it is 128 KB and does not fit beside the 152 KB plan below, so it could only ever be a second path with a
+// size threshold; and the compares cost no LDS bandwidth worth saving -- every lane of a wave reads the SAME label word (the
+// lanes differ in g and c only), which the LDS serves as one broadcast per instruction, conflict-free, and the loop's other
+// read (con[j, cc], 8 bytes a lane) dominates.  The work per row is (2 G + 2) C W M compares: 3.6e5 at the hot node shape
+// (W = 40, M = 4, G = 160, C = 7).  OVERLAP = false keeps pn_explain_groups' instructions: the predicate is a template
+// parameter, not a run-time branch.
+// LDS at G = 1024 (NV = 2050 vectors): rho, vm, vz, vx 4 * 16400 + vb, mode 2 * 8208 + con <= 32768 + grp <= 4096 + pres 4096
+// + label <= 4096 + tile <= 28672 = at most 155744 bytes (+ 256 static; the largest plan_of found over the shapes on both
+// sides of every boundary is 152480) of gfx950's 163840 (160 KiB) per workgroup; one workgroup a CU there, which the partition
+// kernel at G = 1024 already is.
+// Every sum's order is a function of (W, H, C, G, M) alone -- not of S, the grid, or the rows next to it -- and there is no
 // floating-point atomic.  A product of two converted fp32 values is exact in fp64, so the dot products round in their
 // additions only.  Plain C++ and vector stores only.
 #include <hip/hip_runtime.h>
@@ -38,6 +52,7 @@ constexpr int kMaxBlocks = 1 << 16;      // rows (groups) beyond that are taken 
 constexpr int kMaxCon = 4096;            // doubles of con: (W + 1) * Cc
 constexpr int kTileFloats = 7168;        // floats of one H tile: (W + 1 + 2 Cc) * (Ht | 1)
 constexpr int kMaxW = 1024, kMaxG = 1024, kMaxH = 4096, kMaxC = 1024;
+constexpr int kMaxM = 16, kMaxLabels = 1024;      // pn_explain_overlap: labels per member, and per row (W * M)
 
 // how a logit vector picks its members
 constexpr int kModeZero = 0;             // pooled part zero: x = e
@@ -47,12 +62,12 @@ constexpr int kModeAll = 3;              // every member (full; drop of an empty
 
 struct Plan {
     int32_t route, lanes, Cc, Ht, ldt;
-    int32_t off_con, off_rho, off_vm, off_vz, off_vx, off_vb, off_mode, off_grp, off_pres, off_tile, bytes;
+    int32_t off_con, off_rho, off_vm, off_vz, off_vx, off_vb, off_mode, off_grp, off_pres, off_lab, off_tile, bytes;
 };
 
 struct Params {
     int64_t S;
-    int32_t W, H, C, G;
+    int32_t W, H, C, G, M;       // M: labels per member (pn_explain_overlap), 0 for a partition
     const float *state;
     int64_t ld_state;
     const float *coef, *ego;
@@ -60,7 +75,7 @@ struct Params {
     const float *w;
     int64_t ld_w;
     const float *b, *weight;
-    const int32_t *group;
+    const int32_t *group;       // [S, W], or [S, W, M] labels
     int32_t norm, renorm;
     const int64_t *target;
     pn_explain_out o;
@@ -114,7 +129,17 @@ __device__ inline void merge(double &m, double &z, double &x, int32_t &b, double
     x += x2;
 }
 
-template <int LANES>
+// is live member j in group g?  A partition: its one id.  Overlapping groups: any of its M labels (a repeated label counts
+// once; a label outside [0, G) equals no g).  grp[j] is >= 0 for a live member in both.
+template <bool OVERLAP>
+__device__ inline int member_in(const int32_t *grp, const int32_t *lab, int32_t M, int32_t j, int32_t g) {
+    if (!OVERLAP) return grp[j] == g;
+    int in = 0;
+    for (int32_t m = 0; m < M; m++) in |= lab[j * M + m] == g;
+    return in;
+}
+
+template <int LANES, bool OVERLAP>
 __global__ __launch_bounds__(kThreads) void explain_kernel(Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const Plan &pl = p.pl;
@@ -127,9 +152,10 @@ __global__ __launch_bounds__(kThreads) void explain_kernel(Params p) {
     int32_t *mode = (int32_t *)(smem + pl.off_mode);
     int32_t *grp = (int32_t *)(smem + pl.off_grp);      // [W]: -1 dead, g, or G for a live member of no group
     int32_t *pres = (int32_t *)(smem + pl.off_pres);    // [G]
+    int32_t *lab = (int32_t *)(smem + pl.off_lab);      // [W, M] with OVERLAP: a dead member's are -1
     float *tile = (float *)(smem + pl.off_tile);
     double *wl = (double *)tile, *cf = wl + p.W;        // live weights and coefficients: done with before the first tile
-    const int32_t W = p.W, H = p.H, C = p.C, G = p.G, Cc = pl.Cc, Ht = pl.Ht, ldt = pl.ldt;
+    const int32_t W = p.W, H = p.H, C = p.C, G = p.G, M = p.M, Cc = pl.Cc, Ht = pl.Ht, ldt = pl.ldt;
     const int32_t NV = 2 * G + 2, VFULL = 2 * G;
     const int32_t nchunks = (C + Cc - 1) / Cc;
     const int tid = threadIdx.x;
@@ -145,8 +171,13 @@ __global__ __launch_bounds__(kThreads) void explain_kernel(Params p) {
             bad |= !finite32(c);
             const float wv = p.weight ? p.weight[s * W + j] : 1.0f;
             const bool live = finite32(wv) && wv > 0.0f;
-            const int32_t gi = p.group[s * W + j];
-            grp[j] = live ? (gi >= 0 && gi < G ? gi : G) : -1;
+            if (OVERLAP) {
+                grp[j] = live ? 0 : -1;
+                for (int32_t m = 0; m < M; m++) lab[j * M + m] = live ? p.group[(s * W + j) * M + m] : -1;
+            } else {
+                const int32_t gi = p.group[s * W + j];
+                grp[j] = live ? (gi >= 0 && gi < G ? gi : G) : -1;
+            }
             wl[j] = live ? (double)wv : 0.0;
             cf[j] = live ? (double)c : 0.0;
         }
@@ -162,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void explain_kernel(Params p) {
             for (int32_t j = 0; j < W; j++) {
                 const int32_t gj = grp[j];
                 const double wj = wl[j], cj = cf[j];
-                const bool in = gj == g, out = gj >= 0 && gj != g;
+                const bool in = member_in<OVERLAP>(grp, lab, M, j, g), out = gj >= 0 && !in;
                 Om += wj;
                 K += cj;
                 OmR += in ? wj : 0.0;
@@ -263,7 +294,7 @@ __global__ __launch_bounds__(kThreads) void explain_kernel(Params p) {
                             for (int32_t j = 0; j < W; j++) {
                                 const int32_t gj = grp[j];
                                 const double term = con[j * cc_n + cc];
-                                const int in = gj == g, live = gj >= 0;
+                                const int in = member_in<OVERLAP>(grp, lab, M, j, g), live = gj >= 0;
                                 const int take = f_all | (f_grp & in) | (f_rest & live & (in ^ 1));
                                 sum += take ? term : 0.0;
                             }
@@ -446,7 +477,8 @@ int check_shape(const char *who, int64_t S, int32_t W, int32_t H, int32_t C, int
 
 int32_t align16(int32_t v) { return (v + 15) & ~15; }
 
-Plan plan_of(int64_t S, int32_t W, int32_t H, int32_t C, int32_t G) {
+// M: labels per member, 0 for a partition (no label array: pn_explain_groups' plan to the byte)
+Plan plan_of(int64_t S, int32_t W, int32_t H, int32_t C, int32_t G, int32_t M = 0) {
     Plan pl{};
     pl.lanes = C <= 8 ? 8 : C <= 16 ? 16 : 64;
     const int32_t fit = kMaxCon / (W + 1);
@@ -478,6 +510,8 @@ Plan plan_of(int64_t S, int32_t W, int32_t H, int32_t C, int32_t G) {
     off = align16(off + 4 * W);
     pl.off_pres = off;
     off = align16(off + 4 * G);
+    pl.off_lab = off;
+    off = align16(off + 4 * W * M);
     pl.off_tile = off;
     const int32_t tile_bytes = 4 * per * pl.ldt, member_bytes = 16 * W;
     pl.bytes = align16(off + (tile_bytes > member_bytes ? tile_bytes : member_bytes));
@@ -485,6 +519,68 @@ Plan plan_of(int64_t S, int32_t W, int32_t H, int32_t C, int32_t G) {
 }
 
 unsigned blocks_for(int64_t n) { return (unsigned)(n < kMaxBlocks ? n : kMaxBlocks); }
+
+template <bool OVERLAP>
+int launch_explain(pn_context *ctx, const Params &p, hipStream_t stream) {
+    const void *kernel = p.pl.lanes == 8 ? (const void *)explain_kernel<8, OVERLAP>
+                                         : p.pl.lanes == 16 ? (const void *)explain_kernel<16, OVERLAP>
+                                                            : (const void *)explain_kernel<64, OVERLAP>;
+    if (p.pl.bytes > 65536)
+        if (int rc = pn::ensure_dynamic_lds(ctx, kernel, p.pl.bytes)) return rc;
+    const dim3 grid(blocks_for(p.S)), block(kThreads);
+    if (p.pl.lanes == 8)
+        hipLaunchKernelGGL((explain_kernel<8, OVERLAP>), grid, block, p.pl.bytes, stream, p);
+    else if (p.pl.lanes == 16)
+        hipLaunchKernelGGL((explain_kernel<16, OVERLAP>), grid, block, p.pl.bytes, stream, p);
+    else
+        hipLaunchKernelGGL((explain_kernel<64, OVERLAP>), grid, block, p.pl.bytes, stream, p);
+    PN_CHECK_HIP(hipGetLastError());
+    return PN_OK;
+}
+
+// pn_explain_groups (M == 0: `group` is [S, W]) and pn_explain_overlap (M >= 1: [S, W, M] labels): the same checks, the same
+// route, the same kernel body
+int run_explain(const char *who, pn_context *ctx, int64_t S, int32_t W, int32_t H, int32_t C, int32_t G, int32_t M,
+                const float *state, int64_t ld_state, const float *coef, const float *ego, int64_t ld_ego, const float *fc2_w,
+                int64_t ld_w, const float *fc2_b, const float *weight, const int32_t *group, int32_t norm, int32_t renorm,
+                const int64_t *target, const pn_explain_out *out, int32_t *status, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = check_shape(who, S, W, H, C, G)) return rc;
+    if (!out) PN_FAIL(PN_ERR_ARG, "%s: null output description", who);
+    if (norm != PN_PATH_NORM_SUM && norm != PN_PATH_NORM_COUNT) PN_FAIL(PN_ERR_ARG, "%s: norm %d", who, norm);
+    if (renorm != 0 && renorm != 1) PN_FAIL(PN_ERR_ARG, "%s: renorm %d, 0 or 1", who, renorm);
+    if (ld_state < H || ld_ego < H || ld_w < 2 * (int64_t)H)
+        PN_FAIL(PN_ERR_ARG, "%s: leading dimensions %lld / %lld / %lld, at least %d / %d / %d", who, (long long)ld_state,
+                (long long)ld_ego, (long long)ld_w, H, H, 2 * H);
+    if (S > 0 && (!state || !coef || !ego || !fc2_w || !fc2_b || !group))
+        PN_FAIL(PN_ERR_ARG, "%s: null state, coef, ego, fc2_w, fc2_b or %s", who, M ? "label" : "group");
+    if (int rc = pn::context_check_device(ctx)) return rc;
+    if (S == 0) return PN_OK;
+    Params p{};
+    p.S = S;
+    p.W = W;
+    p.H = H;
+    p.C = C;
+    p.G = G;
+    p.M = M;
+    p.state = state;
+    p.ld_state = ld_state;
+    p.coef = coef;
+    p.ego = ego;
+    p.ld_ego = ld_ego;
+    p.w = fc2_w;
+    p.ld_w = ld_w;
+    p.b = fc2_b;
+    p.weight = weight;
+    p.group = group;
+    p.norm = norm;
+    p.renorm = renorm;
+    p.target = target;
+    p.o = *out;
+    p.status = status;
+    p.pl = plan_of(S, W, H, C, G, M);
+    return M ? launch_explain<true>(ctx, p, stream) : launch_explain<false>(ctx, p, stream);
+}
 
 }  // namespace
 
@@ -504,54 +600,20 @@ int pn_explain_route(int64_t S, int32_t W, int32_t H, int32_t C, int32_t G, int3
 int pn_explain_groups(pn_context *ctx, int64_t S, int32_t W, int32_t H, int32_t C, int32_t G, const float *state,
                       int64_t ld_state, const float *coef, const float *ego, int64_t ld_ego, const float *fc2_w, int64_t ld_w,
                       const float *fc2_b, const float *weight, const int32_t *group, int32_t norm, int32_t renorm,
-                      const int64_t *target, const pn_explain_out *out, int32_t *status, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = check_shape("pn_explain_groups", S, W, H, C, G)) return rc;
-    if (!out) PN_FAIL(PN_ERR_ARG, "pn_explain_groups: null output description");
-    if (norm != PN_PATH_NORM_SUM && norm != PN_PATH_NORM_COUNT) PN_FAIL(PN_ERR_ARG, "pn_explain_groups: norm %d", norm);
-    if (renorm != 0 && renorm != 1) PN_FAIL(PN_ERR_ARG, "pn_explain_groups: renorm %d, 0 or 1", renorm);
-    if (ld_state < H || ld_ego < H || ld_w < 2 * (int64_t)H)
-        PN_FAIL(PN_ERR_ARG, "pn_explain_groups: leading dimensions %lld / %lld / %lld, at least %d / %d / %d", (long long)ld_state,
-                (long long)ld_ego, (long long)ld_w, H, H, 2 * H);
-    if (S > 0 && (!state || !coef || !ego || !fc2_w || !fc2_b || !group))
-        PN_FAIL(PN_ERR_ARG, "pn_explain_groups: null state, coef, ego, fc2_w, fc2_b or group");
-    if (int rc = pn::context_check_device(ctx)) return rc;
-    if (S == 0) return PN_OK;
-    Params p{};
-    p.S = S;
-    p.W = W;
-    p.H = H;
-    p.C = C;
-    p.G = G;
-    p.state = state;
-    p.ld_state = ld_state;
-    p.coef = coef;
-    p.ego = ego;
-    p.ld_ego = ld_ego;
-    p.w = fc2_w;
-    p.ld_w = ld_w;
-    p.b = fc2_b;
-    p.weight = weight;
-    p.group = group;
-    p.norm = norm;
-    p.renorm = renorm;
-    p.target = target;
-    p.o = *out;
-    p.status = status;
-    p.pl = plan_of(S, W, H, C, G);
-    const void *kernel = p.pl.lanes == 8 ? (const void *)explain_kernel<8>
-                                         : p.pl.lanes == 16 ? (const void *)explain_kernel<16> : (const void *)explain_kernel<64>;
-    if (p.pl.bytes > 65536)
-        if (int rc = pn::ensure_dynamic_lds(ctx, kernel, p.pl.bytes)) return rc;
-    const dim3 grid(blocks_for(S)), block(kThreads);
-    if (p.pl.lanes == 8)
-        hipLaunchKernelGGL(explain_kernel<8>, grid, block, p.pl.bytes, stream, p);
-    else if (p.pl.lanes == 16)
-        hipLaunchKernelGGL(explain_kernel<16>, grid, block, p.pl.bytes, stream, p);
-    else
-        hipLaunchKernelGGL(explain_kernel<64>, grid, block, p.pl.bytes, stream, p);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
+                      const int64_t *target, const pn_explain_out *out, int32_t *status, void *stream) {
+    return run_explain("pn_explain_groups", ctx, S, W, H, C, G, 0, state, ld_state, coef, ego, ld_ego, fc2_w, ld_w, fc2_b, weight,
+                       group, norm, renorm, target, out, status, stream);
+}
+
+int pn_explain_overlap(pn_context *ctx, int64_t S, int32_t W, int32_t H, int32_t C, int32_t G, int32_t M, const float *state,
+                       int64_t ld_state, const float *coef, const float *ego, int64_t ld_ego, const float *fc2_w, int64_t ld_w,
+                       const float *fc2_b, const float *weight, const int32_t *label, int32_t norm, int32_t renorm,
+                       const int64_t *target, const pn_explain_out *out, int32_t *status, void *stream) {
+    if (M < 1 || M > kMaxM) PN_FAIL(PN_ERR_ARG, "pn_explain_overlap: %d labels per member, 1 .. %d", M, kMaxM);
+    if (W >= 1 && (int64_t)W * M > kMaxLabels)
+        PN_FAIL(PN_ERR_ARG, "pn_explain_overlap: W * M = %lld labels per row, at most %d", (long long)W * M, kMaxLabels);
+    return run_explain("pn_explain_overlap", ctx, S, W, H, C, G, M, state, ld_state, coef, ego, ld_ego, fc2_w, ld_w, fc2_b, weight,
+                       label, norm, renorm, target, out, status, stream);
 }
 
 int pn_explain_totals(pn_context *ctx, int64_t S, int32_t G, const float *drop_delta, const float *keep_gain,

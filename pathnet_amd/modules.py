@@ -988,8 +988,9 @@ class _Aggregator(nn.Module):
                                 reuse_tables=reuse_tables)
 
     def explain(self, X, neis, num_w, walk_len, indices, layer_type, *, groups="path", num_groups=None, target=None,
-                path_weights=None, path_weight_norm="sum", batch_nodes=None, logits=False, contribution=False, totals=None):
-        """Which paths the prediction of every masked node rests on -> ``pathnet_amd.Explanation`` of device tensors (logits,
+                path_weights=None, path_weight_norm="sum", batch_nodes=None, logits=False, contribution=False, totals=None,
+                exclude_self=True):
+        """Which paths, nodes or edges the prediction of every masked node rests on -> ``pathnet_amd.Explanation`` of device tensors (logits,
         drop_delta, keep_gain, flip, present, target, drop_logits / keep_logits with logits=True, contribution with
         contribution=True, totals), one row per masked node, one column per group.
 
@@ -1008,6 +1009,18 @@ class _Aggregator(nn.Module):
                 device.  PathNet_homo / PAGG only; PathNet raises.
                 an int tensor [S, W] in member order, G = num_groups or max + 1 (inferred: one host read); an entry outside
                 [0, G) belongs to no group and is never removed.
+                "node" -- a group per distinct node the row's members consumed (pathnet_amd.member_nodes): removing node u
+                removes every member that passed through u, so the groups overlap (pn_explain_units, pn_explain_overlap).
+                G = W * walk_len columns, no host read: Explanation.unit [S, G] holds the row's node ids in ascending order,
+                then -1, unit_count [S] how many; units() / top_units(k) read them.  exclude_self (default True) leaves out
+                the row's own node, which sits on every path of a PathNet_homo / PAGG row and also enters through the ego
+                half of the embedding.  totals is a pathnet_amd.NodeTotals over the graph's nodes (rows_present, members,
+                flips, top; summary(k) reads it).  For PathNet this is the readable unit: which nodes' rows a slot's
+                recurrence consumed.  walk_len <= 16 and W * walk_len <= 1024, else ValueError.
+                "edge" -- a group per distinct undirected edge between consecutive steps (a stay step (u, u) included),
+                G = W * (walk_len - 1); unit holds (min << 32) | max, units() the two ends [S, G, 2]; totals is None (an edge
+                has no dense index).  PathNet_homo / PAGG only: consecutive consumed nodes are not edges in PathNet's
+                scrambled batch, which raises as "reach" does.
         target (int [S]): the class the scores refer to; default the argmax of the row's logits.
         path_weights / path_weight_norm: forward()'s, by sequence slot; a member of weight 0 is in no group's count, and
                 "sum" renormalises what remains.  (PathNet: re-ordered to member order for the kernel, w.reshape(W, S).t().)
@@ -1019,12 +1032,13 @@ class _Aggregator(nn.Module):
         totals: an earlier Explanation.totals to continue (added into, e.g. over epochs of resampled paths); summary() reads it.
 
         Runs under no_grad in eval mode (no dropout, torch's generator untouched) and restores the training flag.  Not
-        covered: the attribution of single steps or nodes inside a path (the recurrence is not linear), the aggregators of
-        pathnet_amd.dist, and training mode."""
+        covered: the attribution of single steps inside a path (the recurrence is not linear; node and edge groups remove
+        whole members), per-node sums of scores, the aggregators of pathnet_amd.dist, and training mode."""
         from .explain import explain as explain_with       # (the package attribute `explain` is this function, not the module)
         return explain_with(self, X, neis, num_w, walk_len, indices, layer_type, groups=groups, num_groups=num_groups,
                             target=target, path_weights=path_weights, path_weight_norm=path_weight_norm,
-                            batch_nodes=batch_nodes, logits=logits, contribution=contribution, totals=totals)
+                            batch_nodes=batch_nodes, logits=logits, contribution=contribution, totals=totals,
+                            exclude_self=exclude_self)
 
     def paths_stream(self):
         """The torch stream on which this module's NEXT call will read its path arrays (neis / layer_type), judged by the
