@@ -1089,6 +1089,88 @@ int pn_ensemble_finish(pn_context *ctx, int64_t rows, int32_t C, const void *sta
                        const int32_t *subset /* dev [subset_rows] or NULL */, int64_t subset_rows,
                        const int64_t *target /* dev [rows] or NULL */, const pn_ensemble_out *out, void *stream);
 
+/* ---- calibration of ensemble predictions (pn_calib.hip; pn_ensemble_add_scaled in pn_ensemble.hip) ---------------------------
+ * Does a confidence of 0.9 mean "right nine times out of ten"?  These calls fit one temperature on validation logits, apply
+ * it inside the ensemble and measure the result, all on the device.  Added without an ABI bump: five new symbols and two
+ * new structs, no existing struct or signature changed, so pn_abi_version keeps answering 12.
+ *
+ * pn_ensemble_add_scaled is pn_ensemble_add with e_c = exp((x_c - m) * inv), inv = 1 / *tau (dev fp64 [1], read on the
+ * device: a fitted temperature never visits the host).  Votes still use the logits themselves.  (x_c - m) * 1.0 is exact,
+ * so *tau == 1.0 leaves the bits pn_ensemble_add leaves.  A *tau that is not a finite positive number touches nothing and
+ * adds R * S (saturating at 2^31 - 1) to status[0].  Limits as for pn_ensemble_add, and tau must not be NULL.
+ *
+ * pn_calib_sweep: logits dev fp32 [R, S, C] as for pn_ensemble_add, target dev int64 [S], temps dev fp64 [T], 1 <= T <= 256.
+ * For every (row s, temperature t), by the one thread group that owns the pair (G by C alone as in pn_ensemble_route, and
+ * the same order of the class sums), in fp64:
+ *   per sample r whose C logits are all finite (n_ok of them), in ascending r:
+ *       m = max_c x_c, inv = 1 / temps[t], e_c = exp((x_c - m) * inv), p_y = e_y / sum_c e_c        (y = target[s])
+ *   row_nll[s, t] = -log((sum_r p_y) / n_ok)
+ * A row with a target outside [0, C) (checked first; its logits are not read) or with n_ok == 0 is unused: row_nll = 0.
+ * counts (int64 [3], WRITTEN) = {rows used, rows with a bad target, rows without a finite sample}.  A temps[t] that is not a
+ * finite positive number is refused: its row_nll entries are 0 and nll[t] = +inf.
+ * The workspace (caller-owned, 8-byte aligned, pn_calib_sweep_workspace_bytes(S, T) bytes) starts with row_nll, fp64 [S, T],
+ * which the caller may read; the rest is private.  Column sums: the rows are cut into partials of 256 (rows 256 p ..
+ * 256 p + 255); a partial adds its rows in ascending s starting from 0.0, and nll[t] adds the partials in ascending p
+ * starting from 0.0: an order that depends on S alone.  Then
+ *   best (int32 [1])  argmin_t nll[t] over the finite entries, lowest t on ties; -1 when none is finite or no row is used
+ *   tau  (fp64 [1])   temps[best], or 1.0 for best == -1
+ * so tau is always a member of the grid: a discrete output.  Refinement is a second sweep over a finer grid.
+ * S == 0 launches no kernel: best = -1, tau = 1.0, nll and counts zero (memsets on the stream).
+ *
+ * pn_calib_stats: confidence dev fp32 [n], label and target dev int64 [n], prob dev fp32 [n, C] or NULL, 1 <= B <= 1024 bins.
+ * A row is used when label >= 0, 0 <= target < C and confidence is in [0, 1] (NaN is not).  counts (int64 [5], added to,
+ * may be NULL) = {used, label < 0, target out of range, confidence refused, prob[target] == 0}; an unused row counts in the
+ * first of the three reasons that holds, in that order; the last entry counts the used rows that sums[0] leaves out (with
+ * prob only; they stay used everywhere else).  For a used row:
+ *   b = min(B - 1, floor((double)conf * B));  bin_count[b] += 1;  bin_correct[b] += (label == target);
+ *   bin_conf[b] += llrint((double)conf * 2^32)                    fixed point, 2^-32 units
+ * all int64 [B], ADDED to with integer atomics (exact, order-free): the caller zeroes them or keeps them across calls.
+ * With prob, for the used rows (sums fp64 [2], added to by one thread):
+ *   sums[0] += sum of -log((double)prob[i, target]) over the rows with prob[i, target] > 0
+ *   sums[1] += sum of  sum_c ((double)prob[i, c] - [c == target])^2        (classes in ascending c)
+ * Rows are cut into partials of 256; a partial is the halving tree (slot j += slot j + h for h = 128, 64, ..., 1) over its
+ * 256 row terms, rows past n and unused rows holding 0.0; the partials are added in ascending order starting from 0.0, and
+ * that total is added to sums: an order that depends on n alone.
+ * With out->order (risk-coverage; err_prefix and aurc need it):
+ *   order      int32 [n]  the used rows by descending confidence, ties by ascending row, then the unused rows by ascending
+ *                         row (a stable radix sort of key 0x3F800000 - bits(conf), INT32_MAX for an unused row)
+ *   err_prefix int32 [n]  rows with label != target among order[0 .. k]
+ *   aurc       fp64 [1]   (1 / m) sum_{k = 1 .. m} err_prefix[k - 1] / k over the m used rows (written; 0 for m == 0); the
+ *                         terms meet in partials of 256 positions as above
+ * The workspace is pn_calib_stats_workspace_bytes(n, B) bytes, 8-byte aligned, private.  n == 0 launches no kernel (aurc = 0).
+ *
+ * Limits, refused with PN_ERR_ARG before any device call: 1 <= C <= 4096, 0 <= S < 2^31, 0 <= n <= 2 000 000 000, R >= 1, T
+ * and B as above, a workspace that is too small or misaligned, NULL where something would be read or must be written (the
+ * three bin arrays; sums with prob; order with err_prefix or aurc).  Asynchronous on `stream`, nothing read back, nothing
+ * allocated.  The *_workspace_bytes calls need no device. */
+typedef struct pn_calib_sweep_out { /* device pointers, caller-owned, each may be NULL */
+    double *nll;                    /* [T] */
+    int32_t *best;                  /* [1] */
+    double *tau;                    /* [1] */
+    int64_t *counts;                /* [3], written */
+} pn_calib_sweep_out;
+typedef struct pn_calib_stats_out { /* device pointers, caller-owned */
+    int64_t *bin_count;             /* [B], added to */
+    int64_t *bin_correct;           /* [B], added to */
+    int64_t *bin_conf;              /* [B], added to */
+    int64_t *counts;                /* [5], added to; may be NULL */
+    double *sums;                   /* [2], added to; needed with prob */
+    int32_t *order;                 /* [n] or NULL */
+    int32_t *err_prefix;            /* [n] or NULL; needs order */
+    double *aurc;                   /* [1] or NULL; needs order */
+} pn_calib_stats_out;
+int pn_ensemble_add_scaled(pn_context *ctx, const float *logits /* dev [R, S, C] */, int32_t R, int64_t S, int32_t C,
+                           const int32_t *index /* dev [S] or NULL */, int64_t rows, void *state,
+                           int32_t *status /* dev or NULL */, const double *tau /* dev [1] */, void *stream);
+int pn_calib_sweep_workspace_bytes(int64_t S, int32_t T, int64_t *bytes);
+int pn_calib_sweep(pn_context *ctx, const float *logits /* dev [R, S, C] */, int32_t R, int64_t S, int32_t C,
+                   const int64_t *target /* dev [S] */, const double *temps /* dev [T] */, int32_t T, void *workspace,
+                   int64_t workspace_bytes, const pn_calib_sweep_out *out, void *stream);
+int pn_calib_stats_workspace_bytes(int64_t n, int32_t B, int64_t *bytes);
+int pn_calib_stats(pn_context *ctx, const float *confidence, const int64_t *label, const int64_t *target,
+                   const float *prob /* dev [n, C] or NULL */, int64_t n, int32_t C, int32_t B, void *workspace,
+                   int64_t workspace_bytes, const pn_calib_stats_out *out, void *stream);
+
 /* ---- explanations: exact path and group occlusion (pn_explain.hip) --------------------------------------------------------
  * What would the model say without some of a node's paths, or with those paths alone?  pn_path_weights answers with one
  * forward per question.  None of that is needed: the recurrence never sees the pooling, leaving members out of a row changes

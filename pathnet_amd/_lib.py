@@ -97,6 +97,18 @@ class EnsembleOut(ctypes.Structure):
     _fields_ = [(k, vp) for k in FIELDS]
 
 
+class CalibSweepOut(ctypes.Structure):
+    """struct pn_calib_sweep_out: device pointers, None = not wanted"""
+    FIELDS = ("nll", "best", "tau", "counts")
+    _fields_ = [(k, vp) for k in FIELDS]
+
+
+class CalibStatsOut(ctypes.Structure):
+    """struct pn_calib_stats_out: device pointers; counts and the curve members may be None"""
+    FIELDS = ("bin_count", "bin_correct", "bin_conf", "counts", "sums", "order", "err_prefix", "aurc")
+    _fields_ = [(k, vp) for k in FIELDS]
+
+
 ENSEMBLE_ROUTE_NONE, ENSEMBLE_ROUTE_THREAD, ENSEMBLE_ROUTE_WAVE, ENSEMBLE_ROUTE_BLOCK = 0, 1, 2, 3   # pn_ensemble_route
 
 
@@ -291,6 +303,14 @@ SIGNATURES = {
                                        vp]),
     "pn_ensemble_finish": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, vp, vp, ctypes.c_int64, vp,
                                           ctypes.POINTER(EnsembleOut), vp]),
+    "pn_ensemble_add_scaled": (ctypes.c_int, [vp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int64, vp,
+                                              vp, vp, vp]),
+    "pn_calib_sweep_workspace_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, c_i64p]),
+    "pn_calib_sweep": (ctypes.c_int, [vp, vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, vp, vp, ctypes.c_int32, vp,
+                                      ctypes.c_int64, ctypes.POINTER(CalibSweepOut), vp]),
+    "pn_calib_stats_workspace_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, c_i64p]),
+    "pn_calib_stats": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int64,
+                                      ctypes.POINTER(CalibStatsOut), vp]),
     "pn_explain_route": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         c_i32p]),
     "pn_explain_groups": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

@@ -1,37 +1,29 @@
-// pn_ensemble.hip -- ensemble prediction over resampled paths (pn_ensemble_add / pn_ensemble_finish).
+// pn_ensemble.hip -- ensemble prediction over resampled paths (pn_ensemble_add / pn_ensemble_add_scaled / pn_ensemble_finish).
 //
 // A PathNet prediction depends on the W paths the sampler drew for the node.  K independent draws give K logit rows per
 // node; this file averages their class probabilities where they are and says how much the draws disagree.
 //
-//   ensemble_add_kernel<G>     logits [R, S, C] fp32 -> the caller's state (psum, hsum, votes, count, bad).  ONE group of G
+//   ensemble_add_kernel<G, false>  logits [R, S, C] fp32 -> the caller's state (psum, hsum, votes, count, bad).  ONE group of G
 //                              threads owns state row index[s] and takes its R samples in ascending r, so no floating-point
 //                              atomic exists and one [R, S, C] call leaves the bits of R calls of [1, S, C].
+//   ensemble_add_kernel<G, true>  the same body with exp((x_c - m) / tau), tau read on the device (pn_ensemble_add_scaled)
 //   ensemble_finish_kernel<G>  state -> prob, label, vote_label, confidence, entropy, mutual_info, agreement, and with a
 //                              target the confusion matrix (integer atomics: exact, order-free).
 //
-// Work split (pn_ensemble_route): G depends on C alone.
-//   C <= 16           G = 1    a thread per row: the class loop is the ascending serial sum
-//   16 < C <= 1024    G = 64   a wave per row, four rows per workgroup: lane l holds classes l, l + 64, ...
-//   1024 < C <= 4096  G = 256  a workgroup per row
-// Order of a sum over classes: every lane adds its own classes in ascending c, the 64 lane sums meet in a butterfly
-// (xor 32, 16, ..., 1: fp addition commutes, so every lane holds the same bits), the four wave sums of a workgroup are added
-// as (w0 + w1) + (w2 + w3).  That order is a function of C and nothing else -- not of S, R, rows, the grid or the index --
-// and for G = 1 it is the plain ascending sum.  All arithmetic after the fp32 -> fp64 conversion of a logit is fp64.
+// Work split (pn_ensemble_route) and the order of a sum over classes: pn_group.h.  G depends on C alone, and so does the
+// order -- not on S, R, rows, the grid or the index.  All arithmetic after the fp32 -> fp64 conversion of a logit is fp64.
 // Plain C++ and vector stores only.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
+#include "pn_group.h"
 #include "pn_internal.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 1 << 16;          // rows beyond that are taken in a grid-stride loop
-constexpr int kThreadMaxC = 16;              // C <= 16: a thread per row
-constexpr int kWaveMaxC = 1024;              // C <= 1024: a wave per row
-constexpr int kMaxC = 4096;
+using namespace pn::group;        // kThreads, group_of, group_sum, group_best, Best, RedSlots (pn_group.h)
 
 // the state: one allocation, see include/pathnet_hip.h
 struct State {
@@ -57,75 +49,29 @@ __host__ __device__ inline State state_of(void *base, int64_t rows, int32_t C) {
     return st;
 }
 
-// ---- reductions over the G threads that own a row; every thread returns the same bits -------------------------------------
-// G = 256 goes through LDS: `red` holds one slot per wave, and every thread of the workgroup must make the call.
-template <int G>
-__device__ inline double group_sum(double v, double *red) {
-    if (G == 1) return v;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if (G == 256) {
-        __syncthreads();        // (the previous reduction's readers are done with `red`)
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-        __syncthreads();
-        v = (red[0] + red[1]) + (red[2] + red[3]);
-    }
-    return v;
-}
-
-// the largest key and the lowest class that holds it, with a flag OR-ed alongside
-template <typename T>
-struct Best {
-    T key;
-    int32_t c;
-    int32_t flag;
-};
-
-template <typename T>
-__device__ inline void best_merge(Best<T> &a, T key, int32_t c, int32_t flag) {
-    if (key > a.key || (key == a.key && c < a.c)) {
-        a.key = key;
-        a.c = c;
-    }
-    a.flag |= flag;
-}
-
-template <int G, typename T>
-__device__ inline Best<T> group_best(Best<T> b, Best<T> *red) {
-    if (G == 1) return b;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const T key = __shfl_xor(b.key, m, 64);
-        const int32_t c = __shfl_xor(b.c, m, 64);
-        const int32_t flag = __shfl_xor(b.flag, m, 64);
-        best_merge(b, key, c, flag);
-    }
-    if (G == 256) {
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-        __syncthreads();
-        b = red[0];
-#pragma unroll
-        for (int w = 1; w < 4; w++) best_merge(b, red[w].key, red[w].c, red[w].flag);
-    }
-    return b;
-}
-
-union RedSlots {            // the LDS of one workgroup: four slots, reused by every reduction
-    double d[4];
-    Best<float> bf[4];
-    Best<double> bd[4];
-    Best<int32_t> bi[4];
-};
-
 __device__ inline double plogp(double p) { return p > 0.0 ? p * log(p) : 0.0; }
 
 // ---- add ---------------------------------------------------------------------------------------------------------------------
-template <int G>
+// Scaled: e_c = exp((x_c - m) * inv) with inv = 1 / *tau; a *tau that is not finite and positive touches nothing and adds
+// R * S (saturated) to status[0].  (x - m) * 1.0 is exact, so *tau == 1.0 leaves the bits of the plain kernel.
+template <int G, bool Scaled>
 __global__ __launch_bounds__(kThreads) void ensemble_add_kernel(const float *__restrict__ logits, int32_t R, int64_t S,
                                                                  int32_t C, const int32_t *__restrict__ index, int64_t rows,
-                                                                 void *state, int32_t *status) {
+                                                                 void *state, int32_t *status,
+                                                                 const double *__restrict__ tau) {
     __shared__ RedSlots red;
+    double inv = 1.0;
+    if (Scaled) {
+        const double t = *tau;
+        if (!(t > 0.0 && t <= 1.7976931348623157e308)) {       // false for NaN, +inf, zero and negatives
+            if (blockIdx.x == 0 && threadIdx.x == 0 && status) {
+                const int64_t skipped = (int64_t)R * S;
+                atomicAdd(status, (int32_t)(skipped < 2147483647LL ? skipped : 2147483647LL));
+            }
+            return;
+        }
+        inv = 1.0 / t;
+    }
     const State st = state_of(state, rows, C);
     const int lane = G == 1 ? 0 : (int)(threadIdx.x % G);
     const int64_t per_block = kThreads / G;
@@ -155,11 +101,11 @@ __global__ __launch_bounds__(kThreads) void ensemble_add_kernel(const float *__r
             }
             const double m = (double)b.key;
             double z = 0.0;
-            for (int32_t c = lane; c < C; c += G) z += exp((double)x[c] - m);
+            for (int32_t c = lane; c < C; c += G) z += exp(Scaled ? ((double)x[c] - m) * inv : (double)x[c] - m);
             z = group_sum<G>(z, red.d);
             double h = 0.0;
             for (int32_t c = lane; c < C; c += G) {
-                const double p = exp((double)x[c] - m) / z;
+                const double p = exp(Scaled ? ((double)x[c] - m) * inv : (double)x[c] - m) / z;
                 st.psum[row * C + c] += p;
                 h += plogp(p);
             }
@@ -244,18 +190,37 @@ __global__ __launch_bounds__(kThreads) void ensemble_finish_kernel(FinishParams 
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
-int group_of(int32_t C) { return C <= kThreadMaxC ? 1 : C <= kWaveMaxC ? 64 : 256; }
-
 int check_shape(const char *who, int64_t rows, int32_t C) {
     if (C < 1 || C > kMaxC) PN_FAIL(PN_ERR_ARG, "%s: %d classes, 1 .. %d", who, C, kMaxC);
     if (rows < 0 || rows > 2147483647LL) PN_FAIL(PN_ERR_ARG, "%s: %lld rows, 0 .. 2^31 - 1", who, (long long)rows);
     return PN_OK;
 }
 
-unsigned blocks_for(int64_t n, int G) {
-    const int64_t per_block = kThreads / G;
-    const int64_t need = (n + per_block - 1) / per_block;
-    return (unsigned)(need < kMaxBlocks ? need : kMaxBlocks);
+template <bool Scaled>
+int launch_add(const char *who, pn_context *ctx, const float *logits, int32_t R, int64_t S, int32_t C, const int32_t *index,
+               int64_t rows, void *state, int32_t *status, const double *tau, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = check_shape(who, rows, C)) return rc;
+    if (R < 1) PN_FAIL(PN_ERR_ARG, "%s: %d samples, at least 1", who, R);
+    if (S < 0 || S > 2147483647LL) PN_FAIL(PN_ERR_ARG, "%s: %lld logits rows, 0 .. 2^31 - 1", who, (long long)S);
+    if (!index && S > rows)
+        PN_FAIL(PN_ERR_ARG, "%s: %lld logits rows for a state of %lld and no index", who, (long long)S, (long long)rows);
+    if (S > 0 && rows > 0 && (!logits || !state)) PN_FAIL(PN_ERR_ARG, "%s: null logits or state", who);
+    if (int rc = pn::context_check_device(ctx)) return rc;
+    if (S == 0 || rows == 0) return PN_OK;
+    const int G = group_of(C);
+    const dim3 grid(blocks_for(S, G)), block(kThreads);
+    if (G == 1)
+        hipLaunchKernelGGL((ensemble_add_kernel<1, Scaled>), grid, block, 0, stream, logits, R, S, C, index, rows, state,
+                           status, tau);
+    else if (G == 64)
+        hipLaunchKernelGGL((ensemble_add_kernel<64, Scaled>), grid, block, 0, stream, logits, R, S, C, index, rows, state,
+                           status, tau);
+    else
+        hipLaunchKernelGGL((ensemble_add_kernel<256, Scaled>), grid, block, 0, stream, logits, R, S, C, index, rows, state,
+                           status, tau);
+    PN_CHECK_HIP(hipGetLastError());
+    return PN_OK;
 }
 
 }  // namespace
@@ -280,25 +245,13 @@ int pn_ensemble_route(int64_t rows, int32_t C, int32_t *route) {
 
 int pn_ensemble_add(pn_context *ctx, const float *logits, int32_t R, int64_t S, int32_t C, const int32_t *index, int64_t rows,
                     void *state, int32_t *status, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = check_shape("pn_ensemble_add", rows, C)) return rc;
-    if (R < 1) PN_FAIL(PN_ERR_ARG, "pn_ensemble_add: %d samples, at least 1", R);
-    if (S < 0 || S > 2147483647LL) PN_FAIL(PN_ERR_ARG, "pn_ensemble_add: %lld logits rows, 0 .. 2^31 - 1", (long long)S);
-    if (!index && S > rows)
-        PN_FAIL(PN_ERR_ARG, "pn_ensemble_add: %lld logits rows for a state of %lld and no index", (long long)S, (long long)rows);
-    if (S > 0 && rows > 0 && (!logits || !state)) PN_FAIL(PN_ERR_ARG, "pn_ensemble_add: null logits or state");
-    if (int rc = pn::context_check_device(ctx)) return rc;
-    if (S == 0 || rows == 0) return PN_OK;
-    const int G = group_of(C);
-    const dim3 grid(blocks_for(S, G)), block(kThreads);
-    if (G == 1)
-        hipLaunchKernelGGL(ensemble_add_kernel<1>, grid, block, 0, stream, logits, R, S, C, index, rows, state, status);
-    else if (G == 64)
-        hipLaunchKernelGGL(ensemble_add_kernel<64>, grid, block, 0, stream, logits, R, S, C, index, rows, state, status);
-    else
-        hipLaunchKernelGGL(ensemble_add_kernel<256>, grid, block, 0, stream, logits, R, S, C, index, rows, state, status);
-    PN_CHECK_HIP(hipGetLastError());
-    return PN_OK;
+    return launch_add<false>("pn_ensemble_add", ctx, logits, R, S, C, index, rows, state, status, nullptr, stream_);
+}
+
+int pn_ensemble_add_scaled(pn_context *ctx, const float *logits, int32_t R, int64_t S, int32_t C, const int32_t *index,
+                           int64_t rows, void *state, int32_t *status, const double *tau, void *stream_) {
+    if (!tau) PN_FAIL(PN_ERR_ARG, "pn_ensemble_add_scaled: null tau");
+    return launch_add<true>("pn_ensemble_add_scaled", ctx, logits, R, S, C, index, rows, state, status, tau, stream_);
 }
 
 int pn_ensemble_finish(pn_context *ctx, int64_t rows, int32_t C, const void *state, const int32_t *subset, int64_t subset_rows,

@@ -55,6 +55,13 @@ class Prediction(collections.namedtuple("Prediction", FIELDS)):
                        labels_out_of_range=int(flat[3 + C * C]), unlabelled_rows=int(flat[4 + C * C]))
         return out
 
+    def calibration(self, labels, bins=15, curve=True):
+        """How far the confidences can be trusted, against ``labels`` (int [rows of this Prediction]) -> a
+        ``pathnet_amd.Calibration`` of device tensors: reliability bins (``bins`` of them, 1 .. 1024), ece, mce, nll, brier
+        and, with curve=True, the risk-coverage order, err_prefix and aurc (pn_calib_stats; nothing read back)."""
+        from .calibration import calibration_of
+        return calibration_of(self, labels, bins=bins, curve=curve)
+
 
 class Ensemble:
     """Running ensemble of `rows` nodes over `num_classes` classes on `device` (1 <= num_classes <= 4096).
@@ -63,9 +70,12 @@ class Ensemble:
                               names the ensemble row of logits row s, default row s.
     result(labels=None, rows=None) -> Prediction
     reset()                   an empty ensemble again
+    temperature: None, or a float or 1-element fp64 device tensor (a ``Temperature.tau``): every add divides the logits'
+    distance to their maximum by it before the softmax (pn_ensemble_add_scaled; the tensor is read on the device).  A
+    temperature that is not finite and positive adds nothing and counts the refused logits rows in ``status``.
     Everything is enqueued on the current stream; nothing is read back except by check=True and Prediction.summary()."""
 
-    def __init__(self, rows, num_classes, device="cuda"):
+    def __init__(self, rows, num_classes, device="cuda", temperature=None):
         self.rows, self.num_classes = int(rows), int(num_classes)
         dev = torch.device(device)
         if dev.type != "cuda":
@@ -75,6 +85,15 @@ class Ensemble:
         _lib.check(_lib.load().pn_ensemble_state_bytes(self.rows, self.num_classes, ctypes.byref(need)))   # refuses a bad shape
         self.state = torch.zeros(max(need.value, 8), dtype=torch.uint8, device=self.device)    # (the allocator aligns it)
         self.status = torch.zeros(1, dtype=torch.int32, device=self.device)     # logits rows whose index was out of range
+        self.temperature = None
+        if temperature is not None:
+            if torch.is_tensor(temperature):
+                if temperature.numel() != 1:
+                    raise ValueError("Ensemble: temperature must hold one value, got %s" % (tuple(temperature.shape),))
+                tau = temperature.detach().reshape(1).to(device=self.device, dtype=torch.float64)
+            else:
+                tau = torch.tensor([float(temperature)], dtype=torch.float64, device=self.device)
+            self.temperature = tau.contiguous()
 
     # ---- views of the state (include/pathnet_hip.h: psum, hsum, votes, count, bad) ---------------------------------------
     def _views(self):
@@ -121,8 +140,14 @@ class Ensemble:
         elif S > self.rows:
             raise ValueError("Ensemble.add: %d logits rows for an ensemble of %d and no index" % (S, self.rows))
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().pn_ensemble_add(_lib.context(self.device), _lib.ptr(x), R, S, C, _lib.ptr(index), self.rows,
-                                                   _lib.ptr(self.state), _lib.ptr(self.status), _lib.stream_ptr(self.device)))
+            if self.temperature is None:
+                _lib.check(_lib.load().pn_ensemble_add(_lib.context(self.device), _lib.ptr(x), R, S, C, _lib.ptr(index),
+                                                       self.rows, _lib.ptr(self.state), _lib.ptr(self.status),
+                                                       _lib.stream_ptr(self.device)))
+            else:
+                _lib.check(_lib.load().pn_ensemble_add_scaled(_lib.context(self.device), _lib.ptr(x), R, S, C, _lib.ptr(index),
+                                                              self.rows, _lib.ptr(self.state), _lib.ptr(self.status),
+                                                              _lib.ptr(self.temperature), _lib.stream_ptr(self.device)))
         return self
 
     def result(self, labels=None, rows=None):
@@ -182,8 +207,11 @@ def _node_list(nodes, N, dev):
 
 
 def predict_with(model, X, paths, num_w, walk_len, nodes=None, *, samples=8, seed=0, first_epoch=0, batch_nodes=None,
-                 samples_per_call=None, labels=None, path_weights=None, path_weight_norm="sum", ensemble=None, reuse_tables=False):
-    """The body of ``model.predict`` (modules._Aggregator.predict carries the documentation)."""
+                 samples_per_call=None, labels=None, path_weights=None, path_weight_norm="sum", ensemble=None, reuse_tables=False,
+                 temperature=None, collect=None):
+    """The body of ``model.predict`` (modules._Aggregator.predict carries the documentation).
+    collect (``model.calibrate``): a callable ``collect(logits [R, cnt, C], k0, b0)`` that is handed every forward's logits --
+    samples k0 .. k0 + R - 1 of nodes b0 .. b0 + cnt - 1 of the node list -- in place of an ensemble; nothing is returned."""
     from . import modules
     from .sampler import DRAW_PHILOX
     dev = X.device
@@ -217,8 +245,13 @@ def predict_with(model, X, paths, num_w, walk_len, nodes=None, *, samples=8, see
         w = path_weights(ids, codes, sel32, k)
         return None if w is None else modules.as_path_weights(w, int(sel32.numel()), W).to(dev)
 
-    if ensemble is None:
-        ensemble = Ensemble(S, C, dev)
+    if collect is not None:
+        if ensemble is not None or temperature is not None or labels is not None:
+            raise ValueError("predict: collect= takes the logits as they are; no ensemble, temperature or labels")
+    elif ensemble is None:
+        ensemble = Ensemble(S, C, dev, temperature=temperature)
+    elif temperature is not None:
+        raise ValueError("predict: temperature= belongs to the ensemble that is passed in (Ensemble(temperature=))")
     elif ensemble.rows != S or ensemble.num_classes != C or ensemble.device != nodes32.device:
         raise ValueError("predict: ensemble of %d rows x %d classes on %s, the call has %d nodes x %d classes on %s"
                          % (ensemble.rows, ensemble.num_classes, ensemble.device, S, C, nodes32.device))
@@ -248,7 +281,10 @@ def predict_with(model, X, paths, num_w, walk_len, nodes=None, *, samples=8, see
                         out = model(X, ids, W, L, nodes32, codes, None, reuse_tables=not fresh, group_slice=(b0, cnt),
                                     path_weights=w, path_weight_norm=path_weight_norm)
                         fresh = False
-                        ensemble.add(out, index=torch.arange(b0, b0 + cnt, dtype=torch.int32, device=dev))
+                        if collect is not None:
+                            collect(out.view(1, cnt, C), k, b0)
+                        else:
+                            ensemble.add(out, index=torch.arange(b0, b0 + cnt, dtype=torch.int32, device=dev))
             else:
                 for b0 in range(0, S, batch_nodes):
                     sel = nodes32[b0:b0 + batch_nodes]
@@ -267,9 +303,14 @@ def predict_with(model, X, paths, num_w, walk_len, nodes=None, *, samples=8, see
                         out = model(X, ids, W, L, sel.repeat(R) if R > 1 else sel, codes, None, reuse_tables=not fresh,
                                     path_weights=w, path_weight_norm=path_weight_norm)
                         fresh = False
-                        ensemble.add(out.view(R, cnt, C), index=index)
+                        if collect is not None:
+                            collect(out.view(R, cnt, C), k0, b0)
+                        else:
+                            ensemble.add(out.view(R, cnt, C), index=index)
     finally:
         model.train(was_training)
+    if collect is not None:
+        return None
     if labels is not None:
         labels = torch.as_tensor(labels).reshape(-1).to(dev)
         if labels.numel() == N:

@@ -954,7 +954,7 @@ class _Aggregator(nn.Module):
 
     def predict(self, X, paths, num_w, walk_len, nodes=None, *, samples=8, seed=0, first_epoch=0, batch_nodes=None,
                 samples_per_call=None, labels=None, path_weights=None, path_weight_norm="sum", ensemble=None,
-                reuse_tables=False):
+                reuse_tables=False, temperature=None):
         """Ensemble prediction: ``samples`` independent path draws per node, their class probabilities averaged on the
         device (pathnet_amd.Ensemble: fp64 softmax and sums, no read-back) -> ``pathnet_amd.Prediction`` of device tensors
         (prob, label, vote_label, confidence, entropy, mutual_info, agreement, count, bad, confusion, skipped), one row per
@@ -969,6 +969,8 @@ class _Aggregator(nn.Module):
         averaged; the returned Prediction describes everything it holds.
         reuse_tables (extension, forward()'s): X and the weights are those of this module's previous no-grad forward, so
         the first forward of this call reuses the tables too (a test predict right after the validation predict).
+        temperature: a float or a 1-element fp64 device tensor (``model.calibrate(...).tau``) the new Ensemble divides the
+        logits by, on the device; None: the plain softmax, as before.  With ensemble= the ensemble's own temperature holds.
 
         The forwards run under no_grad in eval mode (no dropout, torch's generator untouched); the module's training flag is
         restored afterwards.  PathNet_homo / PAGG, where a row depends on its own paths only: the nodes are taken in chunks of
@@ -985,7 +987,18 @@ class _Aggregator(nn.Module):
         return ens.predict_with(self, X, paths, num_w, walk_len, nodes, samples=samples, seed=seed, first_epoch=first_epoch,
                                 batch_nodes=batch_nodes, samples_per_call=samples_per_call, labels=labels,
                                 path_weights=path_weights, path_weight_norm=path_weight_norm, ensemble=ensemble,
-                                reuse_tables=reuse_tables)
+                                reuse_tables=reuse_tables, temperature=temperature)
+
+    def calibrate(self, X, paths, num_w, walk_len, nodes, labels, *, samples=8, seed=0, first_epoch=0, max_bytes=1 << 30,
+                  **fit_kw):
+        """Fit one temperature on `nodes` (the validation nodes) -> ``pathnet_amd.Temperature`` of device tensors; pass its
+        ``tau`` to ``predict(temperature=)``.  Runs the forwards predict() would run with the same samples, seed and
+        first_epoch (same draws, same stacking), keeps the samples x nodes x classes fp32 logits on the device and hands them
+        to ``pathnet_amd.fit_temperature`` with fit_kw (grid=, rounds=).  labels: per node of X or per node of `nodes`.
+        Logits beyond max_bytes raise ValueError: use fewer nodes -- one scalar does not need the whole validation set."""
+        from . import calibration
+        return calibration.calibrate_with(self, X, paths, num_w, walk_len, nodes, labels, samples=samples, seed=seed,
+                                          first_epoch=first_epoch, max_bytes=max_bytes, **fit_kw)
 
     def explain(self, X, neis, num_w, walk_len, indices, layer_type, *, groups="path", num_groups=None, target=None,
                 path_weights=None, path_weight_norm="sum", batch_nodes=None, logits=False, contribution=False, totals=None,
