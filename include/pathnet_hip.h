@@ -1171,6 +1171,52 @@ int pn_calib_stats(pn_context *ctx, const float *confidence, const int64_t *labe
                    const float *prob /* dev [n, C] or NULL */, int64_t n, int32_t C, int32_t B, void *workspace,
                    int64_t workspace_bytes, const pn_calib_stats_out *out, void *stream);
 
+/* ---- self-supervised pretraining: the contrastive loss between two path draws (pn_contrast.hip) -----------------------------
+ * NT-Xent / InfoNCE between two views A, B (dev fp32 [S, D], row strides lda, ldb >= D) of the same S nodes, forward and
+ * backward, without an S x S array in memory.  Added without an ABI bump: four new symbols and one new struct, no existing
+ * struct or signature changed, so pn_abi_version keeps answering 12.
+ *
+ * Pair i is LIVE when valid[i] != 0 (valid dev uint8 [S], or NULL: all), every entry of a_i and b_i is finite and both norms,
+ * formed in fp64, are finite and > 0.  M = live pairs; bad = pairs that are not live only because of their data.  The unit
+ * rows stack as z_r = a_r / |a_r| for r < S and b_{r-S} / |b_{r-S}| otherwise (z = (float)((double)x / norm)); the partner is
+ * p(r) = r +- S, the logit s_rc = <z_r, z_c> / tau (fp32: one k-ordered fma chain per element on the fp32-input MFMA, then one
+ * multiplication by (float)(1 / tau)), and N(r) is every live c != r -- with intra == 0 only those of the other view (the
+ * symmetric cross-view form; intra != 0 is SimCLR / GRACE NT-Xent).
+ *   lse_r      = log sum_{c in N(r)} exp(s_rc)           an online softmax per lane in fp32, lse = m + log(sum) in fp64
+ *   row_loss_r = lse_r - s_{r,p(r)}                      fp32 [2S], 0 for a row that is not live
+ *   loss       = (1 / 2M) sum_{live r} row_loss_r        fp64 [1], 0 when M == 0
+ *   hits       = rows with s_{r,p(r)} >= s_rc for every c in N(r), on the kernel's own fp32 logits      int64 [1], written
+ *   counts     = {M, bad}                                int64 [2], written
+ * Order: one workgroup owns a row tile and walks the column tiles in ascending order; the lanes of a row meet in a fixed
+ * butterfly; the loss adds the fp64 row losses in partials of 256 rows (halving tree, absent rows 0.0) and the partials in
+ * ascending order.  All of it depends on (S, D, intra) alone, and there is no floating-point atomic: the same bits every run.
+ * pn_contrast_backward reads what the forward left in the SAME workspace (unit rows, norms, liveness, lse, M) and
+ * grad_loss (dev fp32 [1]) and writes every element of dA, dB (dev fp32 [S, D], contiguous) with plain stores:
+ *   dz_r = g / (2 M tau) [ sum_{c in N(r)} (P_rc + P_cr) z_c - 2 z_{p(r)} ],   P_rc = exp(s_rc - lse_r)
+ *   dx_r = (dz_r - z_r <z_r, dz_r>) / |x_r|              exactly 0 for a row that is not live, and when M == 0
+ * The bracket is one exact-fp32 MFMA product W Z per row tile (W_rc = P_rc + P_cr - 2 [c == p(r)], both terms from one pass:
+ * s is symmetric bit for bit); the projection and the scaling run in fp64.
+ * The workspace: pn_contrast_workspace_bytes(S, D) = 64 + 2 (2S D 4) + 24 (2S) + 8 ceil(2S / 256) bytes, 8-byte aligned,
+ * private; nothing in it is quadratic in S.  pn_contrast_tiles: {row tile, column tile, K chunk} of the kernels.
+ * Refused with PN_ERR_ARG before any device call: S < 0 or 2S >= 2^31, D outside 1 .. 8192, tau not finite and positive, a
+ * row stride below D, a workspace that is too small or misaligned, NULL A / B / workspace / out (S > 0), NULL grad_loss / dA /
+ * dB in the backward.  S == 0 launches no kernel: loss, hits and counts are zeroed.  Asynchronous on `stream`, nothing read
+ * back, nothing allocated; M is consumed on the device.  pn_contrast_workspace_bytes and pn_contrast_tiles need no device. */
+typedef struct pn_contrast_out {    /* device pointers, caller-owned, each may be NULL */
+    double *loss;                   /* [1] */
+    float *row_loss;                /* [2S] */
+    int64_t *hits;                  /* [1], written */
+    int64_t *counts;                /* [2] = {M, bad}, written */
+} pn_contrast_out;
+int pn_contrast_workspace_bytes(int64_t S, int32_t D, int64_t *bytes);
+int pn_contrast_tiles(int32_t out[3]);
+int pn_contrast_forward(pn_context *ctx, const float *A, int64_t lda, const float *B, int64_t ldb, int64_t S, int32_t D,
+                        double tau, int32_t intra, const uint8_t *valid /* dev [S] or NULL */, void *workspace,
+                        int64_t workspace_bytes, const pn_contrast_out *out, void *stream);
+int pn_contrast_backward(pn_context *ctx, const float *A, int64_t lda, const float *B, int64_t ldb, int64_t S, int32_t D,
+                         double tau, int32_t intra, void *workspace, int64_t workspace_bytes,
+                         const float *grad_loss /* dev [1] */, float *dA, float *dB, void *stream);
+
 /* ---- explanations: exact path and group occlusion (pn_explain.hip) --------------------------------------------------------
  * What would the model say without some of a node's paths, or with those paths alone?  pn_path_weights answers with one
  * forward per question.  None of that is needed: the recurrence never sees the pooling, leaving members out of a row changes

@@ -12,6 +12,8 @@
   pathnet_amd.ensemble  predictions averaged over resampled paths on the GPU: Ensemble, Prediction, model.predict()
   pathnet_amd.calibration  fit_temperature / model.calibrate(), Ensemble(temperature=), Prediction.calibration(): a temperature
                         fitted and applied on the GPU, reliability bins, ECE, NLL, Brier score and risk-coverage
+  pathnet_amd.contrast  contrastive_loss: NT-Xent between two path draws, tiled forward and backward with exact fp32
+                        products and no [2S, 2S] array; model.pretrain() / trainer.pretrain() for unlabelled nodes
   pathnet_amd.explain   which paths, nodes or edges a prediction rests on: exact occlusion of path groups (disjoint or
                         overlapping) on the GPU, model.explain(), NodeTotals
   pathnet_amd.synth     path-pattern census: the labels of the synthetic experiment (the gen_*_syn CLI)
@@ -26,6 +28,7 @@ from .sampler import (DRAW_GLIBC_REPLAY, DRAW_PHILOX, BiasedSampler, MerwSampler
                       PathReport, UniformSampler)
 from .ensemble import Ensemble, Prediction  # noqa: F401
 from .calibration import Calibration, Temperature, fit_temperature  # noqa: F401
+from .contrast import Contrast, contrastive_loss  # noqa: F401
 from .explain import (Explanation, NodeTotals, explain, explain_groups, explain_overlap, explain_units,  # noqa: F401
                       member_nodes)
 from .pathprob import PathProb, importance_weights  # noqa: F401

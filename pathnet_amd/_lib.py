@@ -109,6 +109,12 @@ class CalibStatsOut(ctypes.Structure):
     _fields_ = [(k, vp) for k in FIELDS]
 
 
+class ContrastOut(ctypes.Structure):
+    """struct pn_contrast_out: device pointers, None = not wanted"""
+    FIELDS = ("loss", "row_loss", "hits", "counts")
+    _fields_ = [(k, vp) for k in FIELDS]
+
+
 ENSEMBLE_ROUTE_NONE, ENSEMBLE_ROUTE_THREAD, ENSEMBLE_ROUTE_WAVE, ENSEMBLE_ROUTE_BLOCK = 0, 1, 2, 3   # pn_ensemble_route
 
 
@@ -311,6 +317,13 @@ SIGNATURES = {
     "pn_calib_stats_workspace_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, c_i64p]),
     "pn_calib_stats": (ctypes.c_int, [vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int64,
                                       ctypes.POINTER(CalibStatsOut), vp]),
+    "pn_contrast_workspace_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, c_i64p]),
+    "pn_contrast_tiles": (ctypes.c_int, [c_i32p]),
+    "pn_contrast_forward": (ctypes.c_int, [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                           ctypes.c_double, ctypes.c_int32, vp, vp, ctypes.c_int64,
+                                           ctypes.POINTER(ContrastOut), vp]),
+    "pn_contrast_backward": (ctypes.c_int, [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                            ctypes.c_double, ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp, vp]),
     "pn_explain_route": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         c_i32p]),
     "pn_explain_groups": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

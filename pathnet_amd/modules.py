@@ -1000,6 +1000,14 @@ class _Aggregator(nn.Module):
         return calibration.calibrate_with(self, X, paths, num_w, walk_len, nodes, labels, samples=samples, seed=seed,
                                           first_epoch=first_epoch, max_bytes=max_bytes, **fit_kw)
 
+    def pretrain(self, X, paths, num_w, walk_len, nodes=None, **kw):
+        """Self-supervised pretraining on unlabelled nodes: the contrastive loss (``pathnet_amd.contrastive_loss``) between
+        two path draws of every node of a batch -> ``pathnet_amd.trainer.Pretrained(loss, hits, pairs)`` of device tensors.
+        ``pathnet_amd.trainer.pretrain`` carries the keywords (epochs=, batch_nodes=, temperature=, intra=, head=,
+        optimizer=, lr=, seed=, first_epoch=) and the documentation."""
+        from . import trainer
+        return trainer.pretrain(self, X, paths, num_w, walk_len, nodes, **kw)
+
     def explain(self, X, neis, num_w, walk_len, indices, layer_type, *, groups="path", num_groups=None, target=None,
                 path_weights=None, path_weight_norm="sum", batch_nodes=None, logits=False, contribution=False, totals=None,
                 exclude_self=True):

@@ -11,6 +11,7 @@ What changes is only where the data lives: paths are int32/uint8 device tensors 
 text file, no per-epoch Python parse, PathNet_run.py:317-334) -- masks are index tensors on the device, and the
 metrics (sklearn in the reference, :384-389) are computed on the device as well.
 """
+import collections
 import os
 import time
 
@@ -185,3 +186,94 @@ def train_fixed_indices(X, Y, num_classes, data_name, train_indices, val_indices
         os.rename(ckpt, os.path.join(save_dir, data_name + time.strftime("%Y-%m-%d_%H:%M:%S", time.localtime())
                                      + str(round_i) + ".pth"))
     return result
+
+
+Pretrained = collections.namedtuple("Pretrained", ("loss", "hits", "pairs"))
+Pretrained.__doc__ = """Device tensors of a pretrain() run, one entry per step: loss float32 [steps], hits int64 [steps] (rows whose
+partner had the largest logit, of 2 * pairs), pairs int64 [steps] (live pairs of the step)."""
+
+
+def pretrain_seed(seed, step, view):
+    """the dropout seed of view `view` (0 / 1) of step `step` of a pretrain(seed=) run"""
+    return (int(seed) * 1000003 + 2 * int(step) + int(view)) & ((1 << 62) - 1)
+
+
+def pretrain(model, X, paths, num_w, walk_len, nodes=None, *, epochs, batch_nodes=None, temperature=0.5, intra=True,
+             head=None, optimizer=None, lr=1e-3, seed=0, first_epoch=0):
+    """Self-supervised pretraining of an aggregator on unlabelled nodes -> ``Pretrained(loss, hits, pairs)``.
+
+    Two independent path draws of a node are two views of it.  Every epoch takes `nodes` (a bool mask or node ids, default all
+    N) in batches of batch_nodes (default: all of them); step t over a batch
+      - draws view 1 as path draw first_epoch + 2t and view 2 as draw first_epoch + 2t + 1 -- `paths` follows predict()'s
+        convention: a sampler (``smp.biased(p, q)`` included; sampled with `seed` and ``nodes=``) or pre-sampled
+        ``(ids, codes)`` tensors [E, N, W, L], where draw k is epoch k % E;
+      - runs two ``model.encode(...)`` calls in training mode, so dropout differs between the views as well
+        (``seed=pretrain_seed(seed, t, view)``), both in one autograd graph;
+      - takes z = head(embedding) when a ``torch.nn.Module`` head is given (a 2-layer MLP, say), else the embedding itself;
+      - ``pathnet_amd.contrastive_loss(z1, z2, temperature, intra)``, ``pathnet_amd.backward``, the optimizer's step.
+    optimizer: a callable (parameters) -> optimizer; None: ``pathnet_amd.Adam(lr)`` over the model's and the head's parameters.
+    After the first step (whose sampler calls run the sampler's own check) the loop reads nothing back: loss, hits and
+    pairs are written into device tensors by index.
+    PathNet (the hetero class): a row pools sequences made of OTHER masked nodes' paths of its batch (encode()'s doc string),
+    so its embedding, and with it what is being pretrained, is a property of (node, batch).
+    Not supported: the aggregators of pathnet_amd.dist (no negatives across ranks), path_grad, and capturing the loop into a
+    hipGraph (the sampler and the workspaces allocate)."""
+    from . import contrast
+    from . import ensemble as ens
+    dev = X.device
+    if dev.type != "cuda":
+        raise RuntimeError("pathnet_amd aggregators run on the GPU only (X is on %s); no CPU fallback" % dev)
+    W, L, N = int(num_w), int(walk_len), int(X.shape[0])
+    nodes32 = ens._node_list(nodes, N, dev)
+    S = int(nodes32.numel())
+    if S < 1 or int(epochs) < 0:
+        raise ValueError("pretrain: %d nodes, %d epochs" % (S, int(epochs)))
+    batch = S if batch_nodes is None else max(1, min(int(batch_nodes), S))
+    from_sampler = hasattr(paths, "sample")
+    if from_sampler:
+        def paths_of(sel32, k, check):       # (the sampler's own check reads one word back: the first step alone asks for it)
+            i, c = paths.sample(W, seed, epoch_begin=k, epoch_count=1, draw_source=DRAW_PHILOX, check=check, nodes=sel32)
+            return i[0], c[0]
+    else:
+        ids_all, codes_all = (torch.as_tensor(t).to(dev) for t in paths)
+        E = int(ids_all.shape[0])
+        if E < 1 or tuple(ids_all.shape[1:]) != (N, W, L) or tuple(codes_all.shape) != tuple(ids_all.shape):
+            raise ValueError("pretrain: paths (ids, codes) of shape [E, %d, %d, %d] expected, got %s / %s"
+                             % (N, W, L, tuple(ids_all.shape), tuple(codes_all.shape)))
+
+        def paths_of(sel32, k, check):
+            idx = sel32.long()
+            return ids_all[k % E].index_select(0, idx), codes_all[k % E].index_select(0, idx)
+
+    params = list(model.parameters()) + (list(head.parameters()) if head is not None else [])
+    opt = optim.Adam(params, lr=lr) if optimizer is None else optimizer(params)
+    chunks = [nodes32[b0:b0 + batch] for b0 in range(0, S, batch)]
+    steps = int(epochs) * len(chunks)
+    loss_t = torch.zeros(steps, dtype=torch.float32, device=dev)
+    hits_t = torch.zeros(steps, dtype=torch.int64, device=dev)
+    pairs_t = torch.zeros(steps, dtype=torch.int64, device=dev)
+    was_training = model.training
+    head_training = head.training if head is not None else None
+    model.train()
+    if head is not None:
+        head.train()
+    try:
+        for t in range(steps):
+            sel = chunks[t % len(chunks)]
+            z = []
+            for view in (0, 1):
+                ids, codes = paths_of(sel, int(first_epoch) + 2 * t + view, t == 0)
+                emb = model.encode(X, ids, W, L, sel, codes, None, seed=pretrain_seed(seed, t, view)).embedding
+                z.append(head(emb) if head is not None else emb)
+            c = contrast.contrastive_loss(z[0], z[1], temperature=temperature, intra=intra)
+            opt.zero_grad(set_to_none=True)
+            optim.backward(c.loss)
+            opt.step()
+            loss_t[t:t + 1].copy_(c.loss.detach().reshape(1))
+            hits_t[t:t + 1].copy_(c.hits)
+            pairs_t[t:t + 1].copy_(c.counts[:1])
+    finally:
+        model.train(was_training)
+        if head is not None:
+            head.train(head_training)
+    return Pretrained(loss_t, hits_t, pairs_t)
