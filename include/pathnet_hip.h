@@ -1217,6 +1217,73 @@ int pn_contrast_backward(pn_context *ctx, const float *A, int64_t lda, const flo
                          double tau, int32_t intra, void *workspace, int64_t workspace_bytes,
                          const float *grad_loss /* dev [1] */, float *dA, float *dB, void *stream);
 
+/* ---- nearest neighbours: exact k best bank rows per query, and the weighted vote over their labels (pn_knn.hip) ---------------
+ * The k nearest rows of a bank X (dev fp32 [N, D], row stride ldx >= D) for every row of Q (dev fp32 [Sq, D], row stride ldq
+ * >= D) by cosine or dot product, without an Sq x N array in memory, and the weighted k-NN classifier over the result: the
+ * label-free monitor of contrastive pretraining.  Added without an ABI bump: four new symbols, one new struct and three
+ * constants, no existing struct or signature changed, so pn_abi_version keeps answering 12.
+ *
+ * A row is LIVE when every entry is finite and, for PN_KNN_COSINE, its norm, formed in fp64, is finite and > 0 (the rule of the
+ * contrastive loss).  A bank row must also pass bank_valid (dev uint8 [N], != 0; NULL: all).  exclude (dev int64 [Sq] or NULL)
+ * names one bank index per query that is no candidate of that query (-1 or anything outside [0, N): none): the leave-one-out
+ * case, where the queries sit inside the bank.  The candidates of a live query are the live bank rows but the excluded one; a
+ * dead query has none.  Score of (query r, bank row c), fp32:
+ *   PN_KNN_COSINE   s = <z_r, z_c>,  z = (float)((double)x / norm)
+ *   PN_KNN_DOT      s = <q_r, x_c>,  the operands as they are
+ * one k-ordered fma chain per pair on the fp32-input MFMA (K chunks of 16, zeros past D): the tile of the contrastive loss, so
+ * in pn_knn_search(X, X) cosine the score of (i, j) has the bits of (j, i).
+ * The order is TOTAL: the higher fp32 score first and, on equal bits, the lower bank index.  -0.0 is taken as +0.0 (they tie,
+ * and +0.0 is what is returned); a NaN score -- possible only with PN_KNN_DOT, when products overflow with both signs -- is
+ * taken, ranked and returned as -inf.  With n = min(k, candidates):
+ *   index  int64 [Sq, k]   slot j: the j-th neighbour's bank index; -1 for j >= n
+ *   score  fp32  [Sq, k]   its score; -inf for j >= n
+ *   count  int32 [Sq]      n; 0 for a dead query
+ *   counts int64 [2]       {dead queries, bank rows that pass bank_valid and are dead for their data's sake}; written
+ * How it runs: the grid is (row tiles of 64 queries, splits); a workgroup walks its contiguous share of the column tiles of 128
+ * bank rows, keeps every row's k best (score, index) keys in LDS and writes a partial list; a second kernel merges the
+ * `splits` partial lists of a query.  The k best of a set of distinct keys do not depend on how the set is cut: the outputs are
+ * bit-identical for every `splits`, for any Sq a row is queried within, and across runs.  splits = 0: the library chooses --
+ * enough for two workgroups per CU of an MI355X (512) where N allows -- and any value is lowered to one split per column
+ * tile at most.  pn_knn_plan: out = {splits used, workgroups of the search, row tile, column tile}.
+ * The workspace: pn_knn_workspace_bytes(Sq, N, D, k, splits) = 64 + 8 s Sq k + 4 (Sq + N) D + 4 (Sq + N) bytes, rounded up to
+ * 8, with s the splits used; 8-byte aligned, private; nothing in it is Sq x N.
+ *
+ * pn_knn_vote: the weighted vote of a search's neighbours.  bank_labels dev int64 [N]; for query q, slot j < count[q] whose
+ * index is inside [0, N) and whose label y_j is inside [0, C) VOTES with
+ *   w_j = exp(((double)s_j - (double)s_0) / T)        (s_0: the query's best score, so w_0 = 1 and nothing overflows; T = +inf: 1)
+ * and no memory is touched for a slot that does not.  One wave per query adds the slots in ascending j into its fp64 [C]:
+ *   prob  fp64  [Sq, C]    votes / sum of the voting weights (added in ascending j); all 0 when that sum is 0
+ *   label int64 [Sq]       argmax_c votes, the lowest class on ties; -1 when the sum is 0
+ * labels (dev int64 [Sq], the queries' own, or NULL) adds confusion[t, label] += 1 (int64 [C, C]) for 0 <= t < C and label >= 0
+ * and skipped[0] += 1 (int64 [1]) for every other query, with integer atomics (exact, order-free): the caller zeroes them or
+ * keeps them across calls, as with pn_ensemble_finish.
+ *
+ * Refused with PN_ERR_ARG before any device call: Sq or N outside [0, 2^31), D outside 1 .. 8192, k outside 1 .. PN_KNN_MAX_K,
+ * splits outside 0 .. 1024, an unknown metric, a row stride below D, a workspace that is NULL, too small or misaligned, NULL Q
+ * (Sq > 0) / X (N > 0) / out; in the vote C outside 1 .. 4096, T not > 0 (NaN included), NULL index / score / count (Sq > 0)
+ * or bank_labels (Sq, N > 0), confusion or skipped without labels.  Sq == 0 or N == 0 launch only what fills the outputs
+ * (every slot empty, counts still exact); the vote launches nothing for Sq == 0.  Asynchronous on `stream`, nothing read back,
+ * nothing allocated.  pn_knn_workspace_bytes and pn_knn_plan need no device. */
+#define PN_KNN_COSINE 0
+#define PN_KNN_DOT 1
+#define PN_KNN_MAX_K 64
+typedef struct pn_knn_out {         /* device pointers, caller-owned, each may be NULL */
+    int64_t *index;                 /* [Sq, k] */
+    float *score;                   /* [Sq, k] */
+    int32_t *count;                 /* [Sq] */
+    int64_t *counts;                /* [2] = {dead queries, dead bank rows}, written */
+} pn_knn_out;
+int pn_knn_workspace_bytes(int64_t Sq, int64_t N, int32_t D, int32_t k, int32_t splits, int64_t *bytes);
+int pn_knn_plan(int64_t Sq, int64_t N, int32_t D, int32_t k, int32_t splits_in, int64_t out[4]);
+int pn_knn_search(pn_context *ctx, const float *Q, int64_t ldq, int64_t Sq, const float *X, int64_t ldx, int64_t N, int32_t D,
+                  int32_t k, int32_t metric, const uint8_t *bank_valid /* dev [N] or NULL */,
+                  const int64_t *exclude /* dev [Sq] or NULL */, int32_t splits, void *workspace, int64_t workspace_bytes,
+                  const pn_knn_out *out, void *stream);
+int pn_knn_vote(pn_context *ctx, const int64_t *index, const float *score, const int32_t *count, int64_t Sq, int32_t k,
+                const int64_t *bank_labels /* dev [N] */, int64_t N, int32_t C, double T,
+                const int64_t *labels /* dev [Sq] or NULL */, double *prob, int64_t *label, int64_t *confusion, int64_t *skipped,
+                void *stream);
+
 /* ---- explanations: exact path and group occlusion (pn_explain.hip) --------------------------------------------------------
  * What would the model say without some of a node's paths, or with those paths alone?  pn_path_weights answers with one
  * forward per question.  None of that is needed: the recurrence never sees the pooling, leaving members out of a row changes

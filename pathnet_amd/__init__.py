@@ -14,6 +14,8 @@
                         fitted and applied on the GPU, reliability bins, ECE, NLL, Brier score and risk-coverage
   pathnet_amd.contrast  contrastive_loss: NT-Xent between two path draws, tiled forward and backward with exact fp32
                         products and no [2S, 2S] array; model.pretrain() / trainer.pretrain() for unlabelled nodes
+  pathnet_amd.neighbours  knn: exact k nearest neighbours of embeddings (cosine / dot) with a total order and no [Sq, N] array;
+                        knn_classify: the weighted k-NN vote; model.embed() / model.knn_probe(), the label-free monitor
   pathnet_amd.explain   which paths, nodes or edges a prediction rests on: exact occlusion of path groups (disjoint or
                         overlapping) on the GPU, model.explain(), NodeTotals
   pathnet_amd.synth     path-pattern census: the labels of the synthetic experiment (the gen_*_syn CLI)
@@ -29,6 +31,7 @@ from .sampler import (DRAW_GLIBC_REPLAY, DRAW_PHILOX, BiasedSampler, MerwSampler
 from .ensemble import Ensemble, Prediction  # noqa: F401
 from .calibration import Calibration, Temperature, fit_temperature  # noqa: F401
 from .contrast import Contrast, contrastive_loss  # noqa: F401
+from .neighbours import KnnVote, Neighbours, knn, knn_classify  # noqa: F401
 from .explain import (Explanation, NodeTotals, explain, explain_groups, explain_overlap, explain_units,  # noqa: F401
                       member_nodes)
 from .pathprob import PathProb, importance_weights  # noqa: F401

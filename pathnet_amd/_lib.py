@@ -115,6 +115,14 @@ class ContrastOut(ctypes.Structure):
     _fields_ = [(k, vp) for k in FIELDS]
 
 
+class KnnOut(ctypes.Structure):
+    """struct pn_knn_out: device pointers, None = not wanted"""
+    FIELDS = ("index", "score", "count", "counts")
+    _fields_ = [(k, vp) for k in FIELDS]
+
+
+KNN_COSINE, KNN_DOT = 0, 1        # pn_knn_search, metric
+KNN_MAX_K = 64                    # PN_KNN_MAX_K
 ENSEMBLE_ROUTE_NONE, ENSEMBLE_ROUTE_THREAD, ENSEMBLE_ROUTE_WAVE, ENSEMBLE_ROUTE_BLOCK = 0, 1, 2, 3   # pn_ensemble_route
 
 
@@ -324,6 +332,14 @@ SIGNATURES = {
                                            ctypes.POINTER(ContrastOut), vp]),
     "pn_contrast_backward": (ctypes.c_int, [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                             ctypes.c_double, ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp, vp]),
+    "pn_knn_workspace_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              c_i64p]),
+    "pn_knn_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_i64p]),
+    "pn_knn_search": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                     ctypes.c_int32, ctypes.c_int32, vp, vp, ctypes.c_int32, vp, ctypes.c_int64,
+                                     ctypes.POINTER(KnnOut), vp]),
+    "pn_knn_vote": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int64, ctypes.c_int32,
+                                   ctypes.c_double, vp, vp, vp, vp, vp, vp]),
     "pn_explain_route": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         c_i32p]),
     "pn_explain_groups": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

@@ -208,10 +208,12 @@ def _node_list(nodes, N, dev):
 
 def predict_with(model, X, paths, num_w, walk_len, nodes=None, *, samples=8, seed=0, first_epoch=0, batch_nodes=None,
                  samples_per_call=None, labels=None, path_weights=None, path_weight_norm="sum", ensemble=None, reuse_tables=False,
-                 temperature=None, collect=None):
+                 temperature=None, collect=None, embedding=False):
     """The body of ``model.predict`` (modules._Aggregator.predict carries the documentation).
     collect (``model.calibrate``): a callable ``collect(logits [R, cnt, C], k0, b0)`` that is handed every forward's logits --
-    samples k0 .. k0 + R - 1 of nodes b0 .. b0 + cnt - 1 of the node list -- in place of an ensemble; nothing is returned."""
+    samples k0 .. k0 + R - 1 of nodes b0 .. b0 + cnt - 1 of the node list -- in place of an ensemble; nothing is returned.
+    embedding (``model.embed``; needs collect): the forwards are ``model.encode`` calls and collect is handed their
+    embeddings [R, cnt, 2H] in place of the logits."""
     from . import modules
     from .sampler import DRAW_PHILOX
     dev = X.device
@@ -244,6 +246,14 @@ def predict_with(model, X, paths, num_w, walk_len, nodes=None, *, samples=8, see
             return None
         w = path_weights(ids, codes, sel32, k)
         return None if w is None else modules.as_path_weights(w, int(sel32.numel()), W).to(dev)
+
+    if embedding and collect is None:
+        raise ValueError("predict: embedding= hands the embeddings to collect=")
+
+    def forward(ids, sel, codes, **kw):
+        if embedding:
+            return model.encode(X, ids, W, L, sel, codes, None, **kw).embedding
+        return model(X, ids, W, L, sel, codes, None, **kw)
 
     if collect is not None:
         if ensemble is not None or temperature is not None or labels is not None:
@@ -278,11 +288,11 @@ def predict_with(model, X, paths, num_w, walk_len, nodes=None, *, samples=8, see
                     w = weights_of(ids, codes, nodes32, k)
                     for b0 in range(0, S, batch_nodes):
                         cnt = min(batch_nodes, S - b0)
-                        out = model(X, ids, W, L, nodes32, codes, None, reuse_tables=not fresh, group_slice=(b0, cnt),
-                                    path_weights=w, path_weight_norm=path_weight_norm)
+                        out = forward(ids, nodes32, codes, reuse_tables=not fresh, group_slice=(b0, cnt), path_weights=w,
+                                      path_weight_norm=path_weight_norm)
                         fresh = False
                         if collect is not None:
-                            collect(out.view(1, cnt, C), k, b0)
+                            collect(out.reshape(1, cnt, -1) if embedding else out.view(1, cnt, C), k, b0)
                         else:
                             ensemble.add(out, index=torch.arange(b0, b0 + cnt, dtype=torch.int32, device=dev))
             else:
@@ -300,11 +310,11 @@ def predict_with(model, X, paths, num_w, walk_len, nodes=None, *, samples=8, see
                         ids = torch.cat([i for i, _ in drawn]) if R > 1 else drawn[0][0]
                         codes = torch.cat([c for _, c in drawn]) if R > 1 else drawn[0][1]
                         w = None if ws[0] is None else (torch.cat(ws) if R > 1 else ws[0])
-                        out = model(X, ids, W, L, sel.repeat(R) if R > 1 else sel, codes, None, reuse_tables=not fresh,
-                                    path_weights=w, path_weight_norm=path_weight_norm)
+                        out = forward(ids, sel.repeat(R) if R > 1 else sel, codes, reuse_tables=not fresh, path_weights=w,
+                                      path_weight_norm=path_weight_norm)
                         fresh = False
                         if collect is not None:
-                            collect(out.view(R, cnt, C), k0, b0)
+                            collect(out.reshape(R, cnt, -1) if embedding else out.view(R, cnt, C), k0, b0)
                         else:
                             ensemble.add(out.view(R, cnt, C), index=index)
     finally:

@@ -1008,6 +1008,96 @@ class _Aggregator(nn.Module):
         from . import trainer
         return trainer.pretrain(self, X, paths, num_w, walk_len, nodes, **kw)
 
+    def embed(self, X, paths, num_w, walk_len, nodes=None, *, samples=1, seed=0, first_epoch=0, batch_nodes=None, head=None):
+        """The embeddings of `nodes` (a bool mask or node ids, default all N) -> fp32 [S, 2H] on X's device, one row per node
+        in their order: ``encode(...).embedding`` in eval mode under no_grad (no dropout, torch's generator untouched; the
+        training flags are restored), averaged over ``samples`` path draws.
+
+        paths follows predict()'s convention: a sampler (``smp.biased(p, q)`` included; sampled with `seed` and ``nodes=``)
+        or pre-sampled ``(ids, codes)`` tensors [E, N, W, L].  Draw j is path draw ``first_epoch + j`` (tensors: epoch
+        ``(first_epoch + j) % E``); the draws of a node are added in ascending j, starting from draw 0's embedding, and the
+        sum is divided by ``samples`` once, in fp32.  The nodes are taken in chunks of batch_nodes (default: all of them),
+        one encode() per chunk and draw -- predict()'s loop with samples_per_call=1, so a chunk's rows have the bits of that
+        encode() call.  head (a ``torch.nn.Module``, as pretrain()'s): every draw's embedding passes through it, in eval
+        mode, before the average, and the result has the head's width.
+        PathNet (the hetero class): a row pools sequences made of OTHER masked nodes' paths of its batch (encode()'s doc
+        string), so an embedding belongs to (node, batch): the batch is the whole of `nodes`, and batch_nodes only cuts it
+        into group_slice pieces with the same values."""
+        from . import ensemble as ens
+        dev = X.device
+        if dev.type != "cuda":
+            raise RuntimeError("pathnet_amd aggregators run on the GPU only (X is on %s); no CPU fallback" % dev)
+        K = int(samples)
+        if K < 1:
+            raise ValueError("embed: samples=%d, at least 1" % K)
+        nodes32 = ens._node_list(nodes, int(X.shape[0]), dev)
+        S = int(nodes32.numel())
+        got = []
+
+        def collect(emb, k0, b0):           # (samples_per_call=1: emb is [1, cnt, 2H], draw k0 of rows b0 ..)
+            z = emb[0] if head is None else head(emb[0])
+            if not got:
+                got.append(torch.empty((S, int(z.shape[1])), dtype=torch.float32, device=dev))
+            rows = got[0][b0:b0 + int(z.shape[0])]
+            if k0 == 0:
+                rows.copy_(z)
+            else:
+                rows.add_(z.to(rows.dtype))
+
+        head_training = head.training if head is not None else None
+        if head is not None:
+            head.eval()
+        try:
+            ens.predict_with(self, X, paths, num_w, walk_len, nodes32, samples=K, seed=seed, first_epoch=first_epoch,
+                             batch_nodes=batch_nodes, samples_per_call=1, collect=collect, embedding=True)
+            if not got:                     # no node: the width is still the head's
+                with torch.no_grad():
+                    z = torch.empty((0, 2 * self.hidden_size), dtype=torch.float32, device=dev)
+                    got.append(z if head is None else head(z).float())
+        finally:
+            if head is not None:
+                head.train(head_training)
+        return got[0] / K if K > 1 else got[0]
+
+    def knn_probe(self, X, paths, num_w, walk_len, bank_nodes, bank_labels, query_nodes, query_labels=None, num_classes=None,
+                  *, k=20, temperature=0.07, metric="cosine", samples=1, seed=0, first_epoch=0, batch_nodes=None, head=None):
+        """The weighted k-NN classifier over this model's embeddings, the label-free monitor of contrastive pretraining ->
+        ``pathnet_amd.KnnVote(prob, label, confusion, skipped)`` of device tensors, one row per query node.
+
+        The bank is ``embed(bank_nodes)``, the queries ``embed(query_nodes)`` (one call when query_nodes IS bank_nodes, the
+        same object: the lists are not compared, which would be a host read; samples, seed, first_epoch, batch_nodes and head
+        are embed()'s), and the result is
+        ``knn_classify(knn(queries, bank, k, metric, bank_valid, exclude), bank_labels, num_classes, temperature,
+        labels=query_labels)``.  bank_labels / query_labels: per node of X or per node of the list; N labels are always read
+        as per node of X and picked by node id (predict()'s rule), also where the list itself has N entries.  num_classes
+        defaults to the model's out_size.  Nothing is read back.  bank_valid is formed on the device from the bank labels inside [0, num_classes): an
+        unlabelled bank node (label -1) is nobody's neighbour.  exclude is formed on the device from the node ids, so a
+        query node that is also a bank node never votes for itself (a node listed twice in the bank: its last position).
+        ``trainer.metrics_from_confusion(vote.confusion)`` gives accuracy and F1 when query_labels is given.  A caller
+        alternates ``pretrain(first_epoch=...)`` and ``knn_probe()``.  For PathNet (the hetero class) an embedding belongs to
+        (node, batch) -- embed()'s doc string -- so bank and queries are embedded within their own node lists."""
+        from . import ensemble as ens
+        from . import neighbours as nb
+        dev, N = X.device, int(X.shape[0])
+        bank32, query32 = ens._node_list(bank_nodes, N, dev), ens._node_list(query_nodes, N, dev)
+        C = int(self.out_size if num_classes is None else num_classes)
+
+        def labels_of(labels, nodes32, name):
+            labels = torch.as_tensor(labels).reshape(-1).to(dev)
+            if labels.numel() == N:
+                return labels.index_select(0, nodes32.long())
+            if labels.numel() != nodes32.numel():
+                raise ValueError("knn_probe: %d %s for %d nodes (of %d)" % (labels.numel(), name, nodes32.numel(), N))
+            return labels
+
+        bl = labels_of(bank_labels, bank32, "bank_labels").long()
+        ql = labels_of(query_labels, query32, "query_labels").long() if query_labels is not None else None
+        kw = dict(samples=samples, seed=seed, first_epoch=first_epoch, batch_nodes=batch_nodes, head=head)
+        zb = self.embed(X, paths, num_w, walk_len, bank32, **kw)
+        zq = zb if query_nodes is bank_nodes else self.embed(X, paths, num_w, walk_len, query32, **kw)
+        found = nb.knn(zq, zb, k, metric=metric, bank_valid=(bl >= 0) & (bl < C), exclude=nb.exclude_of(query32, bank32, N))
+        return nb.knn_classify(found, bl, C, temperature=temperature, labels=ql)
+
     def explain(self, X, neis, num_w, walk_len, indices, layer_type, *, groups="path", num_groups=None, target=None,
                 path_weights=None, path_weight_norm="sum", batch_nodes=None, logits=False, contribution=False, totals=None,
                 exclude_self=True):
