@@ -2,7 +2,8 @@
 on by default in that mode) against the generic one (wgrad3_kernel, pn_seq3.hip) on the same module, inputs and dropout seed,
 and against the CPU oracle.  It replaces autograd's weight gradient of nn.LSTM (/root/reference/PathNet_run.py:164,195,265,351):
 logits within 1e-5, gradients within 3e-5 of each tensor's largest element (tests/gradcheck.py).  (The 128-path forward and
-BPTT that shared the file were experiments that measured slower; removed in round 6, profiles/HISTORY_r1_r4.md.)"""
+BPTT that shared the file were experiments that measured slower; removed in round 6, profiles/HISTORY_r1_r4.md.)
+The kernel's K-tile, split-count, ragged-tail and micro-batch edges are held to the fp64 oracle by tests/test_gpu_wgrad_edges.py."""
 import os
 
 import numpy as np
