@@ -1284,6 +1284,146 @@ int pn_knn_vote(pn_context *ctx, const int64_t *index, const float *score, const
                 const int64_t *labels /* dev [Sq] or NULL */, double *prob, int64_t *label, int64_t *confusion, int64_t *skipped,
                 void *stream);
 
+/* ---- clustering: k-means of embeddings, and the scores of a grouping against labels (pn_kmeans.hip) -------------------------
+ * Lloyd's k-means with k-means++ seeding over rows X (dev fp32 [N, D], row stride ldx >= D) by cosine or squared euclidean
+ * distance, without an N x K array in memory, and NMI / ARI / purity of a grouping against labels: the third label-free
+ * judgement of contrastive pretraining beside the linear and the k-NN probe.  Added without an ABI bump: new symbols, two new
+ * structs and four constants, no existing struct or signature changed, so pn_abi_version keeps answering 12.
+ *
+ * Definitions.
+ * - Live row.  Every entry is finite.  For PN_KMEANS_COSINE, the norm formed in fp64 is also finite and > 0 (knn's rule, and
+ *   knn's order of additions: the same unit rows bit for bit).  The row must pass `valid` (dev uint8 [N] or NULL).  A dead row
+ *   gets label = -1, costs nothing and enters no mean.
+ * - Prepared rows z, written once per run into the workspace (zeros for a dead row).
+ *     Cosine: (float)((double)x / norm).
+ *     PN_KMEANS_EUCLIDEAN: x as it is, with q_r = sum_d (double)x_rd^2 kept beside it, added in ascending d.
+ * - Score.  s(r, c) = <z_r, m_c> in fp32, for centroids m fp32 [K, D]: logits_tile of pn_simtile.h over the stacked array
+ *   [z; m] in the workspace, row tiles from the rows, column tiles from the centroids -- knn's and the contrastive loss's
+ *   arithmetic (exact fp32 products, one k-ordered fma chain per pair, K chunks of 16, zeros past D).  A NaN score is possible
+ *   only for euclidean, when products overflow with both signs.  It counts as -inf, as in knn.
+ * - Key.  e(r, c) = (double)s(r, c) - h_c.  Cosine: h_c = 0.  Euclidean: h_c = 0.5 * sum_d (double)m_cd^2, in ascending d.
+ *   h_c = +inf, and e = -inf whatever the score, for a centroid that is itself not live (an entry not finite; cosine: all
+ *   zeros).  That happens only with caller-supplied centroids, so such a centroid wins nothing.
+ * - Assignment.  label(r) = argmax_c e(r, c), the lowest c on equal values.  -0.0 equals +0.0.
+ * - Row cost, fp64.  Cosine: d_r = max(0, 1 - e).  Euclidean: d_r = max(0, q_r - 2 e).
+ * - Inertia.  The fp64 sum of d_r over the live rows (a dead row adds 0.0): fixed blocks of 256 consecutive rows added in
+ *   ascending order, then the block sums in ascending order.  The order depends on N alone.
+ * - Moved.  The number of live rows whose label differs from prev_label (prev_label NULL: every live row); exact integers.
+ * - Update.  For every cluster with members: coordinate d of the sum is the fp64 sum of z_rd over the members in ascending
+ *   row index -- the cluster's sorted member list is cut into chunks of 64 (pn_kmeans_plan reports it), each chunk is added
+ *   in ascending order, then the chunk partials in ascending order -- so the order depends on the assignment alone, never on
+ *   the grid or timing, and there is no floating-point atomic.  mean = sum / count in fp64.  Euclidean: m = (float)mean.
+ *   Cosine: m = (float)(mean / ||mean||), ||mean||^2 in fp64 as mean_d^2 (rounded) added per residue of d mod 256 in
+ *   ascending d, the 256 residues then by a halving tree (t += t + 128, 64, .. 1).  A cluster keeps its previous centroid
+ *   and adds 1 to `empty` when it has no member, or when the cosine mean has no finite positive norm.  The member lists come
+ *   from the stable radix sort of (key = label, dead rows and labels outside [0, K) keyed K; value = row).
+ *
+ * The workspace carries a run: the prepared rows, liveness, q, the WORKING CENTROIDS (rows N .. N + K - 1 of the stacked
+ * array) and scratch.  pn_kmeans_prepare fills the rows; pn_kmeans_seed or pn_kmeans_set_centroids the centroids; assign
+ * reads them and update replaces them in place.  All calls of a run pass the same N, D, K, metric and workspace.
+ *   pn_kmeans_prepare        prepared rows, liveness, q_r; counts[0] (int64, may be NULL) = rows that are not live
+ *   pn_kmeans_set_centroids  the working centroids = the caller's [K, D] (row stride ldc >= D), as they are
+ *   pn_kmeans_seed           k-means++ on the device, nothing read back.  Round j of restart rho draws
+ *                            w = philox4(seed, ((uint64)rho << 32) | j, PN_KMEANS_STREAM) (the dropout masks' hash, a stream of
+ *                            its own) and r53 = ((w.x | (uint64)w.y << 32) >> 11).  Round 0 weighs every live row 1; round
+ *                            j >= 1 weighs row r with mind_r = min_{i < j} d(r, chosen_i), d as above on the key
+ *                            <z_r, z_c> - h_c with the products and sums in fp64 (per residue of d mod 64 in ascending d, the 64
+ *                            residues by an xor butterfly 32, 16, .. 1; h_c = q_c / 2).  Prefix sums P of the weights are fp64
+ *                            in a fixed two-level order: within blocks of 256 rows in ascending order, then the block sums in
+ *                            ascending order; P_r = (sum of the earlier blocks) + (the prefix inside r's block).
+ *                            t = ((double)r53 * 2^-53) * P_total, one multiplication; the pick is the first row with P_r > t
+ *                            (t rounded up to P_total: the highest row with a weight).  If P_total is 0 or not finite: the
+ *                            lowest live row not yet chosen; if none remains, the lowest live row; if no row is live at all,
+ *                            zeros as the centroid and -1 as chosen[j].  The working centroids become copies of the prepared
+ *                            rows; centroid (fp32 [K, D], contiguous) and chosen (int64 [K]) receive copies, each may be NULL.
+ *                            Cost: K passes over N x D.
+ *   pn_kmeans_assign         one workgroup per row tile of 64 walks all ceil(K / 128) column tiles and keeps one (key, index)
+ *                            best per row in registers.  out: label int32 or int64 [N] by label_bits, key fp64 [N] (-inf
+ *                            for dead rows), moved int64 [1], inertia fp64 [1], iterations int32 [1] (+= 1), each may be NULL.
+ *                            prev_label (same width, or NULL) may be the label array itself.  done (dev int32 [1] or NULL):
+ *                            the call returns at once, every output byte untouched, when it is set, and sets it when
+ *                            moved == 0.
+ *   pn_kmeans_update         sort, then the segmented sums above from `label`.  centroid (fp32 [K, D], a copy of the working
+ *                            centroids afterwards), count int64 [K], empty int64 [1], each may be NULL.  Obeys `done`: nothing
+ *                            but the private sort scratch is written when it is set.
+ *   pn_kmeans_run            the loop in one call, nothing read back: prepare; per restart rho: seed (or, with init, the caller's
+ *                            centroids; then restarts must be 1), then for t = 1 .. iters: assign, and if t < iters, update.
+ *                            Kernels after a converged assign are no-ops by the device flag, so a run always ends on an assign:
+ *                            the returned labels are the nearest centroids of the returned centroids and inertia belongs to
+ *                            exactly that pair.  After restart rho the result takes its labels, centroids, counts, inertia,
+ *                            iterations and moved history when its inertia is lower than the one held: a non-finite inertia
+ *                            loses to any finite one, on equal values the earlier restart stays.  iterations = the assigns that
+ *                            did work; moved[t] = -1 for an assign that did none.
+ * Why assign is a kernel of its own and not pn_knn_search(k = 1): the search re-normalises both operands on every call, keeps
+ * k-best lists in LDS and merges splits, and has no per-column offset, no previous-label compare and no cost sum, while a run
+ * calls assign up to iters x restarts times over the same rows.  What the two share is the tile, and it stays shared.
+ *
+ * pn_cluster_scores(pred int64 [S], K, truth int64 [S], C): table int64 [K, C] += 1 at [pred, truth] by integer atomics (the
+ * caller zeroes it or keeps it across calls, as with the confusion matrices); skipped[0] += 1 (may be NULL) for a pair with
+ * either side outside its range.  Then, with scores != NULL, a one-workgroup finish in fp64 over the WHOLE table, terms
+ * added in row-major order of the table, writes scores fp64 [4] = {nmi, ari, purity, n}; a_i, b_j the row and column sums:
+ *   nmi    = MI / ((H_pred + H_true) / 2) in natural logs, MI = sum (n_ij / n) log((n n_ij) / (a_i b_j)); 1 when both entropies
+ *            are 0
+ *   ari    = (sum C(n_ij, 2) - E) / ((A + B) / 2 - E), A = sum C(a_i, 2), B = sum C(b_j, 2), E = A B / C(n, 2); the three
+ *            binomial sums are exact int64; 1 when the denominator is 0
+ *   purity = sum_i max_j n_ij / n
+ * n == 0 gives NaN scores.
+ *
+ * Limits, refused with PN_ERR_ARG before any device call, outputs untouched: N outside [0, 2^31), D outside 1 .. 8192, K
+ * outside 1 .. PN_KMEANS_MAX_K, an unknown metric, label_bits other than 32 or 64, a stride below D, a NULL, short or misaligned
+ * workspace, NULLs where something would be read (X with N > 0, centroids to set, labels to update from, the output
+ * description), iters outside 1 .. 65536 or restarts < 1 in pn_kmeans_run, restarts != 1 with init, a negative restart index;
+ * in the scores S outside [0, 2^31), K outside 1 .. 1024, C outside 1 .. 4096, a NULL table, NULL pred / truth with S > 0.
+ * N == 0 launches only what fills the outputs.  Asynchronous on `stream`, nothing allocated, nothing read back.
+ *
+ * The workspace, 8-byte aligned, private, nothing in it N x K; with r8(b) = b rounded up to 8 and T = ceil(N / 64):
+ *   pn_kmeans_workspace_bytes(N, D, K, iters) = 64 + r8(4 (N + K) D) + 6 r8(4 N) + 24 N + 16 K + 8 ceil(N / 256) + r8(4 T)
+ *                                               + r8(N) + 8 iters + 2 r8(4 (K + 2)) + 8 (T + K) D + r8(20 N) + 8 MiB
+ * (iters: that of pn_kmeans_run, 0 for the single steps; the last two terms are the radix sort's reserve).
+ * pn_kmeans_plan: out = {workgroups of assign, row tile, column tile, K chunk, update chunk, inertia block}.  Neither needs a
+ * device. */
+#define PN_KMEANS_COSINE 0
+#define PN_KMEANS_EUCLIDEAN 1
+#define PN_KMEANS_MAX_K 1024
+#define PN_KMEANS_STREAM 0x4B4Du    /* philox4's stream word; the dropout masks use 1 and 2 */
+typedef struct pn_kmeans_assign_out { /* device pointers, caller-owned, each may be NULL */
+    void *label;                    /* [N] int32 or int64 */
+    double *key;                    /* [N] */
+    int64_t *moved;                 /* [1], written */
+    double *inertia;                /* [1], written */
+    int32_t *iterations;            /* [1], += 1 */
+} pn_kmeans_assign_out;
+typedef struct pn_kmeans_out {      /* device pointers, caller-owned, each may be NULL */
+    void *label;                    /* [N] int32 or int64 */
+    float *centroid;                /* [K, D] */
+    int64_t *count;                 /* [K] members of the returned labels */
+    double *inertia;                /* [1] */
+    int32_t *iterations;            /* [1] */
+    int64_t *moved;                 /* [iters] */
+    int64_t *counts;                /* [1] = {rows that are not live} */
+    int32_t *restart;               /* [1] the restart the result is from */
+} pn_kmeans_out;
+int pn_kmeans_workspace_bytes(int64_t N, int32_t D, int32_t K, int32_t iters, int64_t *bytes);
+int pn_kmeans_plan(int64_t N, int32_t D, int32_t K, int64_t out[6]);
+int pn_kmeans_prepare(pn_context *ctx, const float *X, int64_t ldx, int64_t N, int32_t D, int32_t K, int32_t metric,
+                      const uint8_t *valid /* dev [N] or NULL */, void *workspace, int64_t workspace_bytes,
+                      int64_t *counts /* dev [1] or NULL */, void *stream);
+int pn_kmeans_set_centroids(pn_context *ctx, const float *centroid, int64_t ldc, int64_t N, int32_t D, int32_t K,
+                            void *workspace, int64_t workspace_bytes, void *stream);
+int pn_kmeans_seed(pn_context *ctx, int64_t N, int32_t D, int32_t K, int32_t metric, uint64_t seed, int32_t restart,
+                   void *workspace, int64_t workspace_bytes, float *centroid, int64_t *chosen, void *stream);
+int pn_kmeans_assign(pn_context *ctx, int64_t N, int32_t D, int32_t K, int32_t metric, void *workspace, int64_t workspace_bytes,
+                     const void *prev_label, int32_t label_bits, const pn_kmeans_assign_out *out, int32_t *done, void *stream);
+int pn_kmeans_update(pn_context *ctx, int64_t N, int32_t D, int32_t K, int32_t metric, void *workspace, int64_t workspace_bytes,
+                     const void *label, int32_t label_bits, float *centroid, int64_t *count, int64_t *empty,
+                     const int32_t *done, void *stream);
+int pn_kmeans_run(pn_context *ctx, const float *X, int64_t ldx, int64_t N, int32_t D, int32_t K, int32_t metric,
+                  const uint8_t *valid /* dev [N] or NULL */, const float *init /* dev [K, D] or NULL */, int64_t ld_init,
+                  int32_t iters, int32_t restarts, uint64_t seed, void *workspace, int64_t workspace_bytes, int32_t label_bits,
+                  const pn_kmeans_out *out, void *stream);
+int pn_cluster_scores(pn_context *ctx, const int64_t *pred, int32_t K, const int64_t *truth, int32_t C, int64_t S, int64_t *table,
+                      int64_t *skipped, double *scores, void *stream);
+
 /* ---- explanations: exact path and group occlusion (pn_explain.hip) --------------------------------------------------------
  * What would the model say without some of a node's paths, or with those paths alone?  pn_path_weights answers with one
  * forward per question.  None of that is needed: the recurrence never sees the pooling, leaving members out of a row changes

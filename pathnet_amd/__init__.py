@@ -16,6 +16,9 @@
                         products and no [2S, 2S] array; model.pretrain() / trainer.pretrain() for unlabelled nodes
   pathnet_amd.neighbours  knn: exact k nearest neighbours of embeddings (cosine / dot) with a total order and no [Sq, N] array;
                         knn_classify: the weighted k-NN vote; model.embed() / model.knn_probe(), the label-free monitor
+  pathnet_amd.cluster   kmeans: k-means++ / Lloyd clustering of embeddings (cosine / euclidean) with defined ties, fp64 means in
+                        a fixed order and no [N, K] array; cluster_scores: contingency table, NMI, ARI, purity;
+                        model.cluster_probe(), the judgement that needs no labels at all
   pathnet_amd.explain   which paths, nodes or edges a prediction rests on: exact occlusion of path groups (disjoint or
                         overlapping) on the GPU, model.explain(), NodeTotals
   pathnet_amd.synth     path-pattern census: the labels of the synthetic experiment (the gen_*_syn CLI)
@@ -32,6 +35,7 @@ from .ensemble import Ensemble, Prediction  # noqa: F401
 from .calibration import Calibration, Temperature, fit_temperature  # noqa: F401
 from .contrast import Contrast, contrastive_loss  # noqa: F401
 from .neighbours import KnnVote, Neighbours, knn, knn_classify  # noqa: F401
+from .cluster import Clusters, ClusterScores, cluster_scores, kmeans  # noqa: F401
 from .explain import (Explanation, NodeTotals, explain, explain_groups, explain_overlap, explain_units,  # noqa: F401
                       member_nodes)
 from .pathprob import PathProb, importance_weights  # noqa: F401

@@ -121,8 +121,23 @@ class KnnOut(ctypes.Structure):
     _fields_ = [(k, vp) for k in FIELDS]
 
 
+class KmeansAssignOut(ctypes.Structure):
+    """struct pn_kmeans_assign_out: device pointers, None = not wanted"""
+    FIELDS = ("label", "key", "moved", "inertia", "iterations")
+    _fields_ = [(k, vp) for k in FIELDS]
+
+
+class KmeansOut(ctypes.Structure):
+    """struct pn_kmeans_out: device pointers, None = not wanted"""
+    FIELDS = ("label", "centroid", "count", "inertia", "iterations", "moved", "counts", "restart")
+    _fields_ = [(k, vp) for k in FIELDS]
+
+
 KNN_COSINE, KNN_DOT = 0, 1        # pn_knn_search, metric
 KNN_MAX_K = 64                    # PN_KNN_MAX_K
+KMEANS_COSINE, KMEANS_EUCLIDEAN = 0, 1      # pn_kmeans_*, metric
+KMEANS_MAX_K = 1024               # PN_KMEANS_MAX_K
+KMEANS_STREAM = 0x4B4D            # PN_KMEANS_STREAM
 ENSEMBLE_ROUTE_NONE, ENSEMBLE_ROUTE_THREAD, ENSEMBLE_ROUTE_WAVE, ENSEMBLE_ROUTE_BLOCK = 0, 1, 2, 3   # pn_ensemble_route
 
 
@@ -340,6 +355,22 @@ SIGNATURES = {
                                      ctypes.POINTER(KnnOut), vp]),
     "pn_knn_vote": (ctypes.c_int, [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int64, ctypes.c_int32,
                                    ctypes.c_double, vp, vp, vp, vp, vp, vp]),
+    "pn_kmeans_workspace_bytes": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_i64p]),
+    "pn_kmeans_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, c_i64p]),
+    "pn_kmeans_prepare": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         vp, vp, ctypes.c_int64, vp, vp]),
+    "pn_kmeans_set_centroids": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, vp,
+                                               ctypes.c_int64, vp]),
+    "pn_kmeans_seed": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                      ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp]),
+    "pn_kmeans_assign": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int64,
+                                        vp, ctypes.c_int32, ctypes.POINTER(KmeansAssignOut), vp, vp]),
+    "pn_kmeans_update": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp, ctypes.c_int64,
+                                        vp, ctypes.c_int32, vp, vp, vp, vp, vp]),
+    "pn_kmeans_run": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp,
+                                     vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, vp, ctypes.c_int64,
+                                     ctypes.c_int32, ctypes.POINTER(KmeansOut), vp]),
+    "pn_cluster_scores": (ctypes.c_int, [vp, vp, ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_int64, vp, vp, vp, vp]),
     "pn_explain_route": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         c_i32p]),
     "pn_explain_groups": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

@@ -1098,6 +1098,36 @@ class _Aggregator(nn.Module):
         found = nb.knn(zq, zb, k, metric=metric, bank_valid=(bl >= 0) & (bl < C), exclude=nb.exclude_of(query32, bank32, N))
         return nb.knn_classify(found, bl, C, temperature=temperature, labels=ql)
 
+    def cluster_probe(self, X, paths, num_w, walk_len, nodes=None, labels=None, clusters=None, *, metric="cosine", iters=50,
+                      restarts=4, seed=0, samples=1, first_epoch=0, batch_nodes=None, head=None):
+        """k-means of this model's embeddings, the judgement of contrastive pretraining that needs no labels at all ->
+        ``(pathnet_amd.Clusters, pathnet_amd.ClusterScores or None)`` of device tensors, one label per node of `nodes`.
+
+        It is ``kmeans(embed(nodes), clusters, metric, iters, restarts, seed)`` and, with labels,
+        ``cluster_scores(found.label, labels, clusters, out_size)``: samples, seed, first_epoch, batch_nodes and head are
+        embed()'s (seed also seeds k-means++).  clusters defaults to the model's out_size.  labels: per node of X or per
+        node of the list; N labels are always read as per node of X and picked by node id (knn_probe()'s rule).  A label
+        outside [0, out_size) -- an unlabelled node's -1 -- is counted in ``skipped``, as is a dead row.  Nothing is read
+        back; ``scores.summary()`` adds the matched accuracy on the host.  For PathNet (the hetero class) an embedding belongs
+        to (node, batch) -- embed()'s doc string."""
+        from . import cluster as cl
+        from . import ensemble as ens
+        dev, N = X.device, int(X.shape[0])
+        nodes32 = ens._node_list(nodes, N, dev)
+        K = int(self.out_size if clusters is None else clusters)
+        if labels is not None:
+            labels = torch.as_tensor(labels).reshape(-1).to(dev)
+            if labels.numel() == N:
+                labels = labels.index_select(0, nodes32.long())
+            elif labels.numel() != nodes32.numel():
+                raise ValueError("cluster_probe: %d labels for %d nodes (of %d)" % (labels.numel(), nodes32.numel(), N))
+        z = self.embed(X, paths, num_w, walk_len, nodes32, samples=samples, seed=seed, first_epoch=first_epoch,
+                       batch_nodes=batch_nodes, head=head)
+        found = cl.kmeans(z, K, metric=metric, iters=iters, restarts=restarts, seed=seed)
+        if labels is None:
+            return found, None
+        return found, cl.cluster_scores(found.label, labels.long(), K, int(self.out_size))
+
     def explain(self, X, neis, num_w, walk_len, indices, layer_type, *, groups="path", num_groups=None, target=None,
                 path_weights=None, path_weight_norm="sum", batch_nodes=None, logits=False, contribution=False, totals=None,
                 exclude_self=True):
